@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the PME hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S1|S2|S3] [--no-scale] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S1|S2|S3] [--dump-outputs DIR]
+                    [--full [--no-scale] [--no-cpu] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs: energy.npy,
+grad.npy, U_ind.npy -- what get_forces returns and the induced dipoles it leaves on the calculator) and prints the result
+line: the headline figure and the configuration it was measured on.  --full adds everything else described below (roofline,
+per-kernel breakdown, list rebuild time, the scf_tight / predictor / static / md_all_terms extras, the CPU baseline with the
+oracle comparison, the at_scale and reference_rule_mesh legs; N > 1: per-kernel and per-collective figures and the extras);
+--no-scale / --no-cpu / --no-extras drop parts of it.
 
 A "step" is one `ADMPPmeForce.get_forces` call (electrostatics incl. the induced-dipole SCF started from the
 previous step's dipoles, fixed pair list) = one MD step's worth of the hot path.  The reference has no
@@ -18,7 +26,7 @@ dispersion PME + Tang-Toennies on the moving frames with a Verlet list (skin 1 A
 
 Default workload (N = 1): S1 = BASELINE.json configs[1] -- 1024 polarizable MPID waters, double precision,
 on the seeded synthetic liquid box (the shipped water1024.pdb geometry has 0.67 A contacts on which the
-reference's own Jacobi SCF diverges), plus an `at_scale` leg on S3 (1 048 575 atoms, f32).
+reference's own Jacobi SCF diverges), plus (--full) an `at_scale` leg on S3 (1 048 575 atoms, f32).
 
 N > 1 (`--gpus N`): the path shards, so the value is the SLAB-DECOMPOSED step of BASELINE configs[3]
 (S3: 1 048 575 polarizable atoms, K = 256, f32) over the N GPUs -- x-slabs of the mesh and of space, RCCL issued by the
@@ -29,7 +37,7 @@ touched the GPU yet -- start N fresh child ranks (one per device, 127.0.0.1 rend
 rank makes the run exit non-zero.  ADMP_BENCH_BACKEND=gloo (+ ADMP_BENCH_SCALE=S2) is the functional rehearsal of several
 ranks on one GPU (host-staged collectives, timings not representative).
 
-One JSON line is printed by rank 0 (contract in the task statement), with `roofline` (real-space pair
+One JSON line is printed by rank 0, with (--full) `roofline` (real-space pair
 kernel, measured with HIP events inside the timed region) and `cpu_baseline` (the float64 oracle timed on
 the host cores on a frame of the same trajectory, SCF warm-started like the GPU step).
 """
@@ -192,13 +200,14 @@ def step(f, a, U, positions=None, pairs='fixed'):
                         a['pScales'], a['dScales'], U_init=U)
 
 
-def run_timed(f, a, steps, warmup, frames=None, barrier=None, only='pair_full', thresh=None, predictor=False):
+def run_timed(f, a, steps, warmup, frames=None, barrier=None, only='pair_full', thresh=None, predictor=False, last=None):
     """Timed region.  frames = ThermalFrames: step k evaluates frame k of the moving trajectory (None: the same geometry
     every step).  Only the roofline kernel is bracketed by HIP events (two event records per launch); the full
     per-kernel breakdown comes from `kernel_breakdown` afterwards, outside the timed region.
     predictor: start the SCF of step n from 2 U(n-1) - U(n-2) instead of U(n-1) (a labelled extra, not the headline: the
     reference's drivers pass the previous step's dipoles, examples/water_pol_1024/run_admp.py:139); the two small tensor
-    operations are inside the timed region."""
+    operations are inside the timed region.
+    last: a dict that receives what the last timed step returned (energy, grad) and the dipoles it left (U_ind)."""
     import torch
     from admp_amd import settings
     old = settings.POL_CONV
@@ -229,7 +238,7 @@ def run_timed(f, a, steps, warmup, frames=None, barrier=None, only='pair_full', 
             updates = 0
             marks = [t0]
             for k in range(warmup, warmup + steps):
-                step(f, a, start(), seq[k])
+                res = step(f, a, start(), seq[k])
                 U = f.U_ind
                 updates += f.n_cycle
                 if predictor:
@@ -243,6 +252,8 @@ def run_timed(f, a, steps, warmup, frames=None, barrier=None, only='pair_full', 
             gc.enable()
         rep = f.profile_report()
         f.profile(False)
+        if last is not None:
+            last.update(energy=res[0], grad=res[1], U_ind=U)
     finally:
         settings.POL_CONV = old
     # n_cycle = Jacobi updates done before the check that passed; every update is preceded by one field evaluation
@@ -597,6 +608,24 @@ def aggregate_ns_per_day(t_step_s, world):
     return world * 0.0864 * DT_FS / t_step_s
 
 
+DUMP_MAX_BYTES = 64 << 20      # the largest workload (S3, f32) writes 25 MB
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every array of `outputs` (run_timed's `last`) as path/<name>.npy, float64 where the path computed in
+    double precision, float32 otherwise, so that two builds can be compared output for output on the same inputs."""
+    arrays = {}
+    for name, x in outputs.items():
+        x = np.atleast_1d(x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x))
+        arrays[name] = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError('--dump-outputs: %d bytes of outputs, more than the %d allowed' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), x)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: this process has not touched the GPU (torch is not even imported yet);
     it starts N fresh child ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, one per device) and
@@ -685,24 +714,29 @@ def main_slab(opt, rank, world):
     f.update_neighbors(a['positions'], w['box'])
     a['pairs'] = None
     frames = ThermalFrames(w, dev)
-    dt, _, cyc = run_timed(f, a, opt.steps, opt.warmup, frames, dist.barrier, only=False)
+    last = {}
+    dt, _, cyc = run_timed(f, a, opt.steps, opt.warmup, frames, dist.barrier, only=False, last=last)
+    if opt.dump_outputs and rank == 0:
+        dump_outputs(opt.dump_outputs, last)        # what rank 0's caller received (outputs='home': other rows zero)
     dt = reduce_max_seconds(dt, dist, rdev)
     t_step = dt / opt.steps
-    # per-kernel and per-collective times of this rank (HIP events around every launch / collective: a pass of its own)
-    comm.reset_stats()
-    if hasattr(comm, 'profile'):
-        comm.profile = True
-    nb = min(opt.steps, 5)
-    kb, counts, rep = kernel_breakdown(f, a, frames, opt.warmup + opt.steps, nb)
-    if hasattr(comm, 'refresh_stats'):
-        comm.refresh_stats()
-    sent = {k: int(v / nb) for k, v in sorted(comm.bytes_sent.items())}
-    coll_py = comm.report(nb)
+    if opt.full:
+        # per-kernel and per-collective times of this rank (HIP events around every launch / collective: a pass of its own)
+        comm.reset_stats()
+        if hasattr(comm, 'profile'):
+            comm.profile = True
+        nb = min(opt.steps, 5)
+        kb, counts, rep = kernel_breakdown(f, a, frames, opt.warmup + opt.steps, nb)
+        if hasattr(comm, 'refresh_stats'):
+            comm.refresh_stats()
+        sent = {k: int(v / nb) for k, v in sorted(comm.bytes_sent.items())}
+        coll_py = comm.report(nb)
     n_atoms = 3 * w['n_mol']
+    extras = opt.full and not opt.no_extras
     # what the reference's calling convention (every caller receives the full gradient / dipole arrays) costs on top: one SUM
     # all-reduce of (Na, 3) per output array and call -- the same object with outputs='replicated', a short leg of its own
     replicated = None
-    if not opt.no_extras and outputs == 'home':
+    if extras and outputs == 'home':
         try:
             f.outputs = 'replicated'
             kr = min(opt.steps, 5)
@@ -717,7 +751,7 @@ def main_slab(opt, rank, world):
             f.outputs = outputs
     # the labelled extra: N independent replicas of the single-GPU headline workload (what a 3072-atom box can do with N GPUs)
     replicas = None
-    if not opt.no_extras:
+    if extras:
         try:
             w1 = make_workload('S1')
             f1, a1 = make_force(w1)
@@ -733,7 +767,7 @@ def main_slab(opt, rank, world):
     # the SAME workload on one GPU (rank 0 alone, the others wait): what `value` has to be compared with -- the driver's own
     # N = 1 run measures the S1 headline, another workload
     single = None
-    if not opt.no_extras:
+    if extras:
         try:
             if rank == 0:
                 fs, as_ = make_force(w)
@@ -748,8 +782,6 @@ def main_slab(opt, rank, world):
             single = {'error': repr(e)}
         dist.barrier()
     if rank == 0:
-        comm_ms = {k: v for k, v in kb.items() if k.startswith('comm_')}
-        kern_ms = {k: v for k, v in kb.items() if not k.startswith('comm_')}
         cfg = {'workload': w['desc'], 'n_atoms': n_atoms, 'n_pairs': n_pairs_all, 'pme_grid': [f.K1, f.K2, f.K3],
                'kappa': round(float(f.kappa), 6), 'dt_fs': DT_FS, 'geometry': 'MOVING: ' + frames.describe(),
                'scf': 'Jacobi, warm-started from the previous step\'s dipoles, POL_CONV = 10 kJ/mol/(e A)',
@@ -764,16 +796,19 @@ def main_slab(opt, rank, world):
         out = {'metric': 'ns/day (electrostatics get_forces per 1 fs step, polarizable PME incl. SCF, moving atoms)',
                'value': round(0.0864 * DT_FS / t_step, 4), 'unit': 'ns/day', 'n_gpus': world, 'steps': opt.steps,
                'warmup': opt.warmup, 'ms_per_step': round(t_step * 1e3, 5), 'higher_is_better': True, 'scaling': 'strong',
-               'vs_baseline': None, 'dtype': 'f32' if w['prec'] == 'single' else 'f64', 'data': 'synthetic', 'config': cfg,
-               'roofline': roofline_of(rep, w, n_pairs_all, None, share=f.n_home / float(n_atoms)),
-               'rank0_kernel_ms_per_step': kern_ms,
-               'rank0_kernel_ms_sum': round(sum(kern_ms.values()), 4),
-               'rank0_collective_ms_per_step': comm_ms if comm_ms else coll_py,
-               'rank0_collective_ms_sum': round(sum((comm_ms if comm_ms else coll_py).values()), 4),
-               'rank0_launches_per_step': counts,
-               'rank0_bytes_sent_per_step': sent,
-               'recip_kernels_rank0': None,
-               'cpu_baseline': None}
+               'vs_baseline': None, 'dtype': 'f32' if w['prec'] == 'single' else 'f64', 'data': 'synthetic', 'config': cfg}
+        if opt.full:
+            comm_ms = {k: v for k, v in kb.items() if k.startswith('comm_')}
+            kern_ms = {k: v for k, v in kb.items() if not k.startswith('comm_')}
+            out.update({'roofline': roofline_of(rep, w, n_pairs_all, None, share=f.n_home / float(n_atoms)),
+                        'rank0_kernel_ms_per_step': kern_ms,
+                        'rank0_kernel_ms_sum': round(sum(kern_ms.values()), 4),
+                        'rank0_collective_ms_per_step': comm_ms if comm_ms else coll_py,
+                        'rank0_collective_ms_sum': round(sum((comm_ms if comm_ms else coll_py).values()), 4),
+                        'rank0_launches_per_step': counts,
+                        'rank0_bytes_sent_per_step': sent,
+                        'recip_kernels_rank0': None,
+                        'cpu_baseline': None})
         if single is not None:
             out['single_gpu_same_workload'] = single
             if 'ms_per_step' in single:
@@ -797,9 +832,12 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--workload', default='S1', choices=sorted(WORKLOADS))
-    ap.add_argument('--no-scale', action='store_true', help='skip the extra 1M-atom measurement (N=1 only)')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
-    ap.add_argument('--no-extras', action='store_true', help='headline only (no scf_tight / static / md_all_terms legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='everything besides the headline: roofline, per-kernel breakdown, '
+                                                        'extras, CPU baseline, at-scale legs (see the module docstring)')
+    ap.add_argument('--no-scale', action='store_true', help='with --full: skip the extra 1M-atom measurement (N=1 only)')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline leg')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: no scf_tight / static / md_all_terms legs')
     opt = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and opt.gpus > 1:
@@ -824,25 +862,19 @@ def main():
     # (up to 200 000 atoms the timed region carries no events: from 4096 atoms on the kernel runs on a side stream next to the
     # mesh chain, and below that two event records per launch cost 6 % of a 0.19 ms step -- 0.2046 against 0.1925 ms at S1)
     side = n_atoms <= int(os.environ.get('ADMP_OVERLAP_MAX', '200000'))
-    dt, rep, cyc = run_timed(f, a, opt.steps, opt.warmup, frames, only=False if side else 'pair_full')
+    last = {}
+    dt, rep, cyc = run_timed(f, a, opt.steps, opt.warmup, frames, only=False if side else 'pair_full', last=last)
+    if opt.dump_outputs:
+        dump_outputs(opt.dump_outputs, last)
     t_step = dt / opt.steps
     value = aggregate_ns_per_day(t_step, 1)
-    last = opt.warmup + opt.steps            # index of the next frame of the trajectory
-    U_last = f.U_ind
-    kb, counts, rep_serial = kernel_breakdown(f, a, frames, last)
-    head = dict(n_pairs=int(f.n_pairs), grid=[f.K1, f.K2, f.K3], kappa=round(float(f.kappa), 6),
-                roofline=roofline_of(rep, w, f.n_pairs, rep_serial), kernels=kb, counts=counts)
-    head['rebuild_ms'] = time_list_rebuild(f, w)
-    f.set_pairs(a['pairs'])
 
-    cfg = {'workload': w['desc'], 'n_atoms': n_atoms, 'n_pairs': head['n_pairs'],
-           'pme_grid': head['grid'], 'kappa': head['kappa'], 'dt_fs': DT_FS,
+    cfg = {'workload': w['desc'], 'n_atoms': n_atoms, 'n_pairs': int(f.n_pairs),
+           'pme_grid': [f.K1, f.K2, f.K3], 'kappa': round(float(f.kappa), 6), 'dt_fs': DT_FS,
            'geometry': 'MOVING: ' + frames.describe(),
            'scf': 'Jacobi, warm-started from the previous step\'s dipoles, POL_CONV = 10 kJ/mol/(e A) '
                   '(reference default, admp/settings.py:29)',
-           'pair_list': 'fixed during the timed steps; GPU cell-list search + table compile = %.3f ms per rebuild '
-                        '(value with a rebuild every 10 steps: %.2f ns/day)' % (
-                            head['rebuild_ms'], 0.0864 / (t_step + head['rebuild_ms'] * 1e-4)),
+           'pair_list': 'fixed during the timed steps',
            'parallelism': 'single GPU'}
     cfg.update(cyc)
     out = {
@@ -851,12 +883,33 @@ def main():
         'ms_per_step': round(t_step * 1e3, 5), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': 'f64' if w['prec'] == 'double' else 'f32', 'data': 'synthetic',
         'config': cfg,
+    }
+    if opt.full:
+        full_legs(opt, out, w, f, a, frames, dev, rep, t_step, last['U_ind'])
+    print(json.dumps(out))
+    return 0
+
+
+def full_legs(opt, out, w, f, a, frames, dev, rep, t_step, U_last):
+    """--full: what the line carries besides the headline, measured after the timed region of `main` on the same calculator
+    and trajectory (rep: the timed region's profile report, U_last: the dipoles its last step left)."""
+    import torch
+    last = opt.warmup + opt.steps            # index of the next frame of the trajectory
+    kb, counts, rep_serial = kernel_breakdown(f, a, frames, last)
+    head = dict(n_pairs=int(f.n_pairs), grid=[f.K1, f.K2, f.K3], kappa=round(float(f.kappa), 6),
+                roofline=roofline_of(rep, w, f.n_pairs, rep_serial), kernels=kb, counts=counts)
+    head['rebuild_ms'] = time_list_rebuild(f, w)
+    f.set_pairs(a['pairs'])
+    out['config']['pair_list'] = ('fixed during the timed steps; GPU cell-list search + table compile = %.3f ms per rebuild '
+                                  '(value with a rebuild every 10 steps: %.2f ns/day)' % (
+                                      head['rebuild_ms'], 0.0864 / (t_step + head['rebuild_ms'] * 1e-4)))
+    out.update({
         'roofline': head['roofline'],
         'kernel_ms_per_step': head['kernels'],
         'kernel_launches_per_step': head['counts'],
         'kernel_ms_note': 'breakdown pass: every launch bracketed by HIP events, side stream off (steps slower than the timed ones)',
         'recip_kernels': recip_kernel_rooflines(head['kernels'], head['counts'], w, head['grid']),
-    }
+    })
     if not opt.no_extras:
         try:
             k2 = min(opt.steps, 20)
@@ -950,8 +1003,6 @@ def main():
                     static_geometry_ms_per_step=round(dts / 10 * 1e3, 3), **cycm)
             except Exception as e:
                 out['reference_rule_mesh'] = {'error': repr(e)}
-    print(json.dumps(out))
-    return 0
 
 
 if __name__ == '__main__':

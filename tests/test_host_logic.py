@@ -123,6 +123,23 @@ def test_bench_pair_kernel_bytes_formula():
     assert abs(per_pair - 145.7) < 0.1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per output, float64 kept, every other dtype as float32, the energy (a host
+    scalar) as a 1-element array; more than 64 MB in all is refused before anything is written."""
+    import torch
+    import bench
+    g = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    u = torch.ones((4, 3), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'out'), {'energy': np.float64(-1.5), 'grad': g, 'U_ind': u})
+    got = {n: np.load(str(tmp_path / 'out' / (n + '.npy'))) for n in ('energy', 'grad', 'U_ind')}
+    assert got['energy'].dtype == np.float64 and got['energy'].tolist() == [-1.5]
+    assert got['grad'].dtype == np.float32 and np.array_equal(got['grad'], g.numpy())
+    assert got['U_ind'].dtype == np.float64 and np.array_equal(got['U_ind'], u.numpy())
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros((bench.DUMP_MAX_BYTES // 8 + 1,))})
+    assert not (tmp_path / 'big').exists()
+
+
 def test_fft_friendly_mesh_is_opt_in():
     """settings.FFT_FRIENDLY_MESH rounds the reference's K up to a 7-smooth size; off by default (reference mesh)."""
     from admp_amd import settings

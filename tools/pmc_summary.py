@@ -13,7 +13,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'gpurun_out')
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'profile_out')      # tools/profile_round.sh
 tag = sys.argv[2] if len(sys.argv) > 2 else 'r01'
 out = {}
 rows_out = []
