@@ -269,8 +269,11 @@ class HipForceBase:
         self._pairs_keep = None
 
     def set_cutoff(self, rc):
-        """Skip the pairs of the list beyond `rc` (minimum image) in the pair kernels: for Verlet lists built with a skin.
-        0 = evaluate every listed pair (default; what the reference does).  Dispersion and pair-potential calculators."""
+        """Skip the pairs of the list beyond `rc` (minimum image) in the pair kernels: for Verlet lists built with a skin,
+        the result is then the one of the exact-rc list whatever the age of the list.  0 = evaluate every listed pair
+        (default; what the reference does).  Every calculator: dispersion and pair potentials test each partner; multipolar
+        PME walks, in every pair pass of a call, the inner table of the list written at the call's positions (energies,
+        gradient, induced dipoles, dE/dQ_local and the derivatives on request are those of the cut energy)."""
         _lib.check(self._h, self._L.admp_set_cutoff(self._h, float(rc)), 'admp_set_cutoff')
 
     def set_side_stream(self, on=True):

@@ -569,6 +569,15 @@ struct Engine : EngineBase {
   void* onehot_for = nullptr;    // ... built in this allocation
   DevBuf act_d, isites, mesh2;   // incremental SCF: polarizable-site list, their compact delta rows, the increment's mesh
   IndTable ind;                  // ... and the polarizable-polarizable part of the neighbour table
+  // admp_set_cutoff (a Verlet list with a skin): each evaluation with a cutoff first writes the inner table of the table it walks
+  // (nbr: owned, borrowed or pruned) at its own site rows, and all its multipolar pair passes walk that copy (build_cut_table).
+  // Allocated on the first such evaluation; cutoff 0 walks nbr / ind as before.
+  DevBuf cut_end, cut_col, cut_iend, cut_icol;
+  NbrTable cut_nbr;
+  IndTable cut_ind;
+  bool cut_on = false;           // this evaluation walks cut_nbr / cut_ind
+  const NbrTable& wnbr() const { return cut_on ? cut_nbr : nbr; }
+  const IndTable& wind() const { return cut_on ? cut_ind : ind; }
   long act_gen = 0, act_top_na = -1;   // act_gen: bumped when the list is rebuilt; the list belongs to a topology of act_top_na atoms
   int act_n = -1;                // its length once the host has seen it (-1: not yet)
   bool act_fresh = false;        // this evaluation rebuilt the list (count still on the device)
@@ -603,7 +612,8 @@ struct Engine : EngineBase {
     for (DevBuf* b : {&sites, &grad, &pot, &fld_pair, &fld_recip, &field, &energies_d, &s_pos, &s_Q, &s_pol,
                       &s_thole, &s_U, &s_out, &s_dQ, &s_par, &mesh, &spec, &gtabs[0], &gtabs[1], &gtabs[2], &gtabs[3], &fft_work, &binv_d, &scan_scratch, &bin_cells,
                       &bin_sorted, &bin_scan, &home_list, &dft_tw, &bases_d, &vir_d, &act_d, &isites, &mesh2, &act_tmp,
-                      &rq_d, &pfa_tw, &pfa_fmap, &pfa_ptab, &gtab_nat, &fx_tw, &bin_cells_ind, &bin_sorted_ind, &srow_d, &onehot_d, &tcount_d, &prune_rowptr, &prune_cnt, &prune_col})
+                      &rq_d, &pfa_tw, &pfa_fmap, &pfa_ptab, &gtab_nat, &fx_tw, &bin_cells_ind, &bin_sorted_ind, &srow_d, &onehot_d, &tcount_d, &prune_rowptr, &prune_cnt, &prune_col,
+                      &cut_end, &cut_col, &cut_iend, &cut_icol})
       b->release();
     free_topology();
     if (ind.end) (void)hipFree(ind.end);
@@ -1324,6 +1334,7 @@ struct Engine : EngineBase {
       if (tracked) exchange_migrants();
       if (lpol) exchange_U(0);
       ev.active = true;
+      cut_pass();
       return ev.n_home;
     }
     {
@@ -1379,7 +1390,30 @@ struct Engine : EngineBase {
       ev.home = nullptr;
     }
     ev.active = true;
+    cut_pass();
     return ev.n_home;
+  }
+  // the inner table of this evaluation (see cut_nbr): the rows its pair kernels walk, at the sites just prepared
+  void cut_pass() {
+    cut_on = cutoff > 0.0;
+    if (!cut_on) return;
+    const size_t na = (size_t)top.na, entries = (size_t)std::max<int64_t>(nbr.cap, 1);
+    cut_end.need(sizeof(int) * na);
+    cut_col.need(sizeof(int) * entries);
+    cut_nbr = nbr;
+    cut_nbr.col = cut_col.as<int>();
+    cut_nbr.rowend = cut_end.as<int>();
+    if (lpol) {
+      cut_iend.need(sizeof(int) * na);
+      cut_icol.need(sizeof(int) * entries);
+      cut_ind.beg = nbr.rowptr; cut_ind.end = cut_iend.as<int>(); cut_ind.col = cut_icol.as<int>();
+      cut_ind.cap = (int64_t)entries; cut_ind.na_cap = (int)na;
+    }
+    TIMED("cut_table");
+    const int rc = build_cut_table<T>(stream, ev.n_home, pair_rows(), nbr, sites.as<Site<T>>(), ev.bx, cutoff,
+                                      cut_end.as<int>(), cut_col.as<int>(), lpol ? cut_iend.as<int>() : nullptr,
+                                      lpol ? cut_icol.as<int>() : nullptr);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_cut_table: ") + hipGetErrorString((hipError_t)rc)};
   }
 
   void need_eval() { ARG_CHECK(ev.active, "internal: no evaluation in progress"); }
@@ -1476,7 +1510,7 @@ struct Engine : EngineBase {
     slot_clean[E_REAL] = false;
     check_mono_inputs(mono_ok);
     TIMED("pair_full");
-    launch_pair_full<T>(stream, ev.n_home, nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(),
+    launch_pair_full<T>(stream, ev.n_home, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(),
                         Ed_cur(), pair_rows(), fld_out, mono_ok ? 1 : 0, cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole);
   }
   // with_field_finish: the gather also forms the total dE/dU and its maximum (launch_field_finish's work, fused)
@@ -1573,7 +1607,7 @@ struct Engine : EngineBase {
   void first_pair_field() {          // real-space dE/dU of the polarizable rows, all partners
     check_mono_inputs(true);         // (the flag word handed over below switches the charge-only form on)
     TIMED("pair_field");
-    launch_pair_field<T>(stream, nact_rows(), nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
+    launch_pair_field<T>(stream, nact_rows(), wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
                          act_list(), nact_arg(), cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole);
   }
   void first_gather_field(const FieldFin<T>& ff) {   // reciprocal dE/dU of the polarizable rows from phi
@@ -1651,18 +1685,19 @@ struct Engine : EngineBase {
       if (!ride)
         on_side([&] {
           TIMED("pair_field_ind");
-          launch_pair_field_ind<T>(stream, n_act, ind, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
+          launch_pair_field_ind<T>(stream, n_act, wind(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
                                    act_list());
         });
       if (extra_side) on_side(extra_side);
     };
-    if (ind_nbr_gen != nbr_gen || ind_act_gen != act_gen) {      // neighbour table or polarizable set changed
+    if (!cut_on && (ind_nbr_gen != nbr_gen || ind_act_gen != act_gen)) {   // neighbour table or polarizable set changed
+                                                                          // (cut_ind is written by every evaluation)
       TIMED("ind_table");
       int rc = build_ind_table<T>(stream, top.na, nbr, sites.as<Site<T>>(), ind);
       if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
       ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
     }
-    ride = rider_ok() && field_rider_ind<T>(fr, n_act, ind, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
+    ride = rider_ok() && field_rider_ind<T>(fr, n_act, wind(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
                                             act_list());
     if (first) side_work();
     const size_t nreal = nreal_local();
@@ -1753,7 +1788,7 @@ struct Engine : EngineBase {
     FieldRider<T> fr;
     if (rider_ok()) {
       check_mono_inputs(true);
-      if (field_rider_full<T>(fr, nact_rows(), nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(), act_list(),
+      if (field_rider_full<T>(fr, nact_rows(), wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(), act_list(),
                               nact_arg(), cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole)) {
         recip_pass(slot, [] {}, &fr);
         return;
@@ -2128,7 +2163,7 @@ struct Engine : EngineBase {
     upload_binv(inv);
     double* acc = vir_begin();
     stage_pair_full(gbuf);
-    launch_pair_virial<T>(stream, na, nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW, pair_rows(), ev.n_home);
+    launch_pair_virial<T>(stream, na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW, pair_rows(), ev.n_home);
     stage_spread(mesh.as<T>());
     if (!slot_clean[E_RECIP]) HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
     slot_clean[E_RECIP] = false;
@@ -2167,7 +2202,7 @@ struct Engine : EngineBase {
     upload_binv(inv);
     double* acc = vir_begin();
     stage_pair_full(gbuf);
-    launch_pair_virial<T>(stream, na, nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW);
+    launch_pair_virial<T>(stream, na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW);
     vs_n = na; vs_sites = sites.as<Site<T>>(); vs_g = ev.g;
     if (!slot_clean[E_RECIP]) HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
     slot_clean[E_RECIP] = false;
@@ -2910,7 +2945,7 @@ struct Engine : EngineBase {
     HIP_TRY(hipSetDevice(device));
     stage_begin(pos, box, Ql, pol, thole, ns, mS, pS, const_cast<void*>(U));
     // (slab rank: the sums of its home rows -- per-atom outputs like the gradient: the home rows are this rank's results)
-    { TIMED("thole_sums"); launch_thole_sums<T>(stream, top.na, nbr, sites.as<Site<T>>(), ev.bx, ev.tab, (T*)sumX, (T*)sumXw,
+    { TIMED("thole_sums"); launch_thole_sums<T>(stream, top.na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T*)sumX, (T*)sumXw,
                                                 snranks > 1 ? pair_rows() : nullptr, ev.n_home); }
     ev.active = false;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -2925,7 +2960,7 @@ struct Engine : EngineBase {
     vir_d.need(V_WORDS * sizeof(double));
     double* cls = vir_d.as<double>();
     HIP_TRY(hipMemsetAsync(cls, 0, 16 * sizeof(double), stream));
-    { TIMED("pscale_grad"); launch_pscale_sums<T>(stream, top.na, nbr, sites.as<Site<T>>(), ev.bx, ev.tab, cls,
+    { TIMED("pscale_grad"); launch_pscale_sums<T>(stream, top.na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, cls,
                                                   snranks > 1 ? pair_rows() : nullptr, ev.n_home); }
     if (snranks > 1) { TIMED("comm_energies"); c_all_reduce(cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     ev.active = false;

@@ -26,6 +26,10 @@ struct ScaleTab {
 struct NbrTable {
   int* rowptr = nullptr;   // na + 1
   int* col = nullptr;      // 2 * n_half
+  // An evaluation's inner table (admp_set_cutoff on a multipolar handle, build_cut_table): a copy of the walked table's struct
+  // whose col holds, at each row's own offset rowptr[i], the entries below the cutoff, and whose row i ends at rowend[i].
+  // nullptr: row i ends at rowptr[i + 1] (every table a handle owns or borrows).  Never owned by the struct.
+  int* rowend = nullptr;   // na
   int64_t n_half = 0;
   int64_t cap = 0;         // allocated entries of col
   int* order = nullptr;    // na: rows sorted by length inside windows of kRowWindow rows (launch_row_order), or nullptr
@@ -319,6 +323,14 @@ void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spe
 template <class T>
 int prune_table(hipStream_t st, int na, const NbrTable& full, const T* pos, const Box<T>& box, double rc, int* rowptr_out,
                 int* cnt, int* col_out, void** scratch, size_t* scratch_bytes, int64_t* total);
+// (nbr_kernels.hip) inner table of one evaluation with a cutoff (admp_set_cutoff on a multipolar handle): for the n rows
+// `rows` (nullptr: rows 0 .. n-1) the entries of `nb` whose minimum-image distance at the site rows is below rc, written at the
+// row's own offset nb.rowptr[i] in the order of nb (class runs survive): col_out[nb.rowptr[i] .. end_out[i]).  With iend /
+// icol also the polarizable-polarizable part of those entries (the sub-table of build_ind_table, below rc).  col_out and icol
+// hold as many entries as nb.col.  No atomics, no host synchronisation; hipError_t as int.
+template <class T>
+int build_cut_table(hipStream_t st, int n, const int* rows, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
+                    double rc, int* end_out, int* col_out, int* iend, int* icol);
 // (nbr_kernels.hip) ascending in-place sort of n ints; keys_tmp = n ints of scratch.  hipError_t as int.
 int sort_ints(hipStream_t st, int* keys, int* keys_tmp, int n, void** scratch, size_t* scratch_bytes);
 // (nbr_kernels.hip) it <- the polarizable-polarizable entries of nb; rows keyed by atom, empty for non-polarizable atoms.

@@ -293,6 +293,71 @@ int build_ind_table(hipStream_t st, int na, const NbrTable& nb, const Site<T>* s
 template int build_ind_table<float>(hipStream_t, int, const NbrTable&, const Site<float>*, IndTable&);
 template int build_ind_table<double>(hipStream_t, int, const NbrTable&, const Site<double>*, IndTable&);
 
+// ---- inner table of one evaluation (admp_set_cutoff on a multipolar handle) ------------------------------------------------
+// A Verlet list with a skin lists (rc + skin)^3 / rc^3 times the pairs below rc, and the multipolar kernels wait on the fetch
+// chain entry -> partner site, not on their arithmetic: a test per partner inside them skips little.  Instead one pass per
+// evaluation, at its site rows, keeps the entries below rc -- at the row's own offset, in the row's order (general entries
+// before kColMono ones, as in admp_prune_pairs), the row's end in end_out -- and every pair pass of the evaluation (the SCF
+// repeats its field passes) walks that copy.  The distance is the pair arithmetic's (r_I - r_J of the site rows, min_image),
+// so both directions of a pair are classified alike.  With icol the polarizable-polarizable entries among the kept ones go to
+// the sub-table of the incremental SCF as well (k_ind_table's rule: row and partner with p6 > 0).  8 lanes per row, as there.
+template <class T>
+__global__ __launch_bounds__(256) void k_cut_table(int n, const int* __restrict__ rows, const int* __restrict__ rowptr,
+                                                   const int* __restrict__ col, const Site<T>* __restrict__ sites, Box<T> box,
+                                                   T rc2, int* __restrict__ cend, int* __restrict__ ccol,
+                                                   int* __restrict__ iend, int* __restrict__ icol) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const int slot = (int)(t >> 3), sub = (int)(t & 7);
+  const bool live = slot < n;
+  const int row = live ? (rows ? rows[slot] : slot) : 0;
+  const int beg = live ? rowptr[row] : 0, end = live ? rowptr[row + 1] : 0;
+  T ri[3] = {0, 0, 0};
+  bool ipol = false;
+  if (live) {
+    ri[0] = sites[row].r[0]; ri[1] = sites[row].r[1]; ri[2] = sites[row].r[2];
+    ipol = icol && sites[row].p6 > T(0);
+  }
+  const int g0 = (threadIdx.x & 63) & ~7;
+  int base = beg, ibase = beg;
+  for (int k0 = beg; k0 < end; k0 += 8) {      // the 8 lanes of a row share the trip count; the ballots are read per group
+    const int k = k0 + sub;
+    const int c = k < end ? col[k] : 0;
+    bool keep = false, ikeep = false;
+    if (k < end) {
+      const Site<T>& J = sites[c & kColMask];
+      T d[3] = {ri[0] - J.r[0], ri[1] - J.r[1], ri[2] - J.r[2]};
+      min_image(box, d);
+      keep = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] < rc2;
+      ikeep = keep && ipol && J.p6 > T(0);
+    }
+    const unsigned grp = (unsigned)((__ballot(keep) >> g0) & 0xffull);
+    if (keep) ccol[base + __popc(grp & ((1u << sub) - 1u))] = c;
+    base += __popc(grp);
+    if (icol) {
+      const unsigned igrp = (unsigned)((__ballot(ikeep) >> g0) & 0xffull);
+      if (ikeep) icol[ibase + __popc(igrp & ((1u << sub) - 1u))] = c;
+      ibase += __popc(igrp);
+    }
+  }
+  if (live && sub == 0) {
+    cend[row] = base;
+    if (iend) iend[row] = ibase;
+  }
+}
+template <class T>
+int build_cut_table(hipStream_t st, int n, const int* rows, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
+                    double rc, int* end_out, int* col_out, int* iend, int* icol) {
+  if (n <= 0) return 0;
+  const unsigned grid = (unsigned)(((long)n * 8 + 255) / 256);
+  k_cut_table<T><<<grid, 256, 0, st>>>(n, rows, nb.rowptr, nb.col, sites, box, (T)(rc * rc), end_out, col_out, iend, icol);
+  NB_CHECK(hipGetLastError());
+  return 0;
+}
+template int build_cut_table<float>(hipStream_t, int, const int*, const NbrTable&, const Site<float>*, const Box<float>&, double,
+                                    int*, int*, int*, int*);
+template int build_cut_table<double>(hipStream_t, int, const int*, const NbrTable&, const Site<double>*, const Box<double>&,
+                                     double, int*, int*, int*, int*);
+
 // ---- inner list of an MD loop (round 4, admp_prune_pairs) ------------------------------------------------------------------
 // A Verlet list with a skin holds (rc + skin)^3 / rc^3 times the pairs inside rc (rc 4 + 1 A: 1.95 x) and the multipolar kernels
 // evaluate every listed pair.  Between two rebuilds of that OUTER table the calculators can walk an INNER one: the entries of

@@ -39,9 +39,12 @@ __device__ __forceinline__ void stage_tab(const ScaleTab<T>& tab, T* s) {
   __syncthreads();
 }
 
-template <class T, bool LPOL, int LPR, int MINW>
+// CUT (admp_set_cutoff on a multipolar handle): the kernel walks the evaluation's inner table (build_cut_table: the entries
+// below the cutoff at this call's sites, at the rows' own offsets) and a row ends at rowend[row]; without it at rowptr[row + 1],
+// exactly as before the option existed (rowend unused).
+template <class T, bool LPOL, int LPR, int MINW, bool CUT>
 __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const int* __restrict__ rowptr,
-                                                          const int* __restrict__ col,
+                                                          const int* __restrict__ rowend, const int* __restrict__ col,
                                                           const Site<T>* __restrict__ sites, Box<T> box,
                                                           ScaleTab<T> tab, T kappa, T* __restrict__ grad,
                                                           T* __restrict__ pot, double* energies,
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
   double e = 0.0;
   if (slot < na) {
     const Site<T> I = sites[row];
-    const int beg = rowptr[row] + sub, end = rowptr[row + 1];
+    const int beg = rowptr[row] + sub, end = CUT ? rowend[row] : rowptr[row + 1];
     T* Fp = (LPOL && fld) ? F : nullptr;
     // Charge-only sites (pme_math.h).  The neighbour table was compiled with the atoms' classes (NbrTable::cls): the entries
     // of a row whose partner is charge-only carry kColMono and stand behind the others, and `rows` groups the rows by class
@@ -152,9 +155,9 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
 
 // (bid: the workgroup's index in a launch of its own -- blockIdx.x of k_pair_field, or its rank among the field workgroups
 // that ride in an x pass of the mesh convolution, k_xconv_pair below)
-template <class T, int LPR>
+template <class T, int LPR, bool CUT>
 __device__ __forceinline__ void pair_field_block(unsigned bid, int na, const int* __restrict__ rowptr,
-                                                 const int* __restrict__ col, const Site<T>* __restrict__ sites,
+                                                 const int* __restrict__ rowend, const int* __restrict__ col, const Site<T>* __restrict__ sites,
                                                  const Box<T>& box, const ScaleTab<T>& tab, T kappa, T* __restrict__ fld,
                                                  const int* __restrict__ rows, unsigned nblocks, const int* __restrict__ n_dev,
                                                  const int* __restrict__ cls_flags, const RQ4<T>* __restrict__ rq,
@@ -172,7 +175,7 @@ __device__ __forceinline__ void pair_field_block(unsigned bid, int na, const int
   T F[3] = {0, 0, 0};
   if (slot < na) {
     const Site<T> I = sites[row];
-    const int end = rowptr[row + 1];
+    const int end = CUT ? rowend[row] : rowptr[row + 1];      // (CUT: see k_pair_full)
     // two runs per row, as in k_pair_full: partners with higher moments, then (kColMono) the charge-only ones, whose field
     // is one radial coefficient along the pair axis; both loops fetch ahead (see k_pair_full)
     const bool use = cls_flags && !(*cls_flags & CLS_STALE);
@@ -211,16 +214,17 @@ __device__ __forceinline__ void pair_field_block(unsigned bid, int na, const int
     fld[3 * row] = F[0]; fld[3 * row + 1] = F[1]; fld[3 * row + 2] = F[2];
   }
 }
-template <class T, int LPR>
+template <class T, int LPR, bool CUT>
 __global__ __launch_bounds__(kPairBlock) void k_pair_field(int na, const int* __restrict__ rowptr,
-                                                           const int* __restrict__ col,
+                                                           const int* __restrict__ rowend, const int* __restrict__ col,
                                                            const Site<T>* __restrict__ sites, Box<T> box,
                                                            ScaleTab<T> tab, T kappa, T* __restrict__ fld,
                                                            const int* __restrict__ rows, unsigned nblocks,
                                                            const int* __restrict__ n_dev,
                                                            const int* __restrict__ cls_flags,
                                                            const RQ4<T>* __restrict__ rq, const T* __restrict__ tholes) {
-  pair_field_block<T, LPR>(blockIdx.x, na, rowptr, col, sites, box, tab, kappa, fld, rows, nblocks, n_dev, cls_flags, rq, tholes);
+  pair_field_block<T, LPR, CUT>(blockIdx.x, na, rowptr, rowend, col, sites, box, tab, kappa, fld, rows, nblocks, n_dev, cls_flags, rq,
+                                tholes);
 }
 
 // Incremental SCF (engine.hip): fld[row] += sum over the polarizable partners of T_ij . dU_j, rows = the polarizable
@@ -274,7 +278,8 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_field_ind(int na, const int
 // appended to the grid of the x pass (same block size; 124 and 134-164 registers): the launch runs both kinds side by side.
 // Workgroups with blockIdx.x < nbx are x-pass tiles (dft_lines.h), the others field workgroups number
 // (blockIdx.x - nbx) * gridDim.y + blockIdx.y.
-template <class T, int LPR>
+// (CUT: kind 1 walks an inner table, see k_pair_full; kind 2 takes its row ends from the sub-table in either case)
+template <class T, int LPR, bool CUT>
 __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, FieldRider<T> fr, int nbx) {
   static_assert(kPairBlock == kDftBlock, "the two kinds of workgroups share one launch");
   if ((int)blockIdx.x < nbx) {
@@ -284,7 +289,7 @@ __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, Fiel
   const unsigned bid = (blockIdx.x - (unsigned)nbx) * gridDim.y + blockIdx.y;
   if (bid >= fr.grid) return;                          // workgroup-uniform
   if (fr.kind == 1)
-    pair_field_block<T, LPR>(bid, fr.na, fr.rowptr, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows, fr.nblocks,
+    pair_field_block<T, LPR, CUT>(bid, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows, fr.nblocks,
                              fr.n_dev, fr.cls_flags, fr.rq, fr.tholes);
   else
     pair_field_ind_block<T, LPR>(bid, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows);
@@ -427,7 +432,9 @@ void launch_scalar_pair_pgrad(hipStream_t st, int tt, int na, const NbrTable& nb
 // nb = 0..15 the sum over its pairs of d(pair energy)/d(mscale).  KIND 0: multipolar PME (bare multipole interaction,
 // pair_bare_energy), 1: dispersion (sum_p c_p,i c_p,j / r^p), 2: Tang-Toennies (the kernel without its m factor).
 // Non-bonded pairs (class 0, almost all of them) accumulate in a register, the bonded classes through LDS atomics.
-template <class T, int KIND>
+// CUT (KIND 0 with admp_set_cutoff; the scalar kinds test rc2 > 0 at run time): listed pairs beyond the cutoff are skipped.
+// This call prepares its own sites and has no inner table: the test is the one of build_cut_table, on the same d.
+template <class T, int KIND, bool CUT>
 __global__ __launch_bounds__(kPairBlock) void k_pair_mgrad(int na, const int* __restrict__ rowptr,
                                                            const int* __restrict__ col, const Site<T>* __restrict__ sites,
                                                            const T* __restrict__ pos, const T* __restrict__ par, Box<T> box,
@@ -456,10 +463,11 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_mgrad(int na, const int* __
       const int nb = col_nb(c), j = c & kColMask;
       T v;
       if (KIND == 0) {
+        if (CUT && !pair_inside(box, I.r, sites[j].r, rc2)) continue;
         v = pair_bare_energy<T>(box, I, sites[j]);
       } else {
         T rj[3] = {pos[3 * j], pos[3 * j + 1], pos[3 * j + 2]}, pj[4] = {0, 0, 0, 0}, g[3] = {0, 0, 0};
-        if (!pair_inside(box, ri, rj, rc2)) continue;      // (the multipolar kernels evaluate every listed pair: KIND 0 has no cutoff)
+        if (!pair_inside(box, ri, rj, rc2)) continue;
         for (int q = 0; q < NP; ++q) pj[q] = par[NP * j + q];
         if (KIND == 1) {   // disp_pair is linear in mm: E(mm = 1) - E(mm = 0)
           v = disp_pair(box, ri, rj, pi, pj, T(1), T(0), pmax, g) - disp_pair(box, ri, rj, pi, pj, T(0), T(0), pmax, g);
@@ -478,8 +486,10 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_mgrad(int na, const int* __
 }
 
 // dE/dpScales: per covalent class the sum over its pairs of pair_pscale_deriv (polarizable handle, dipoles given)
-template <class T>
-__global__ __launch_bounds__(kPairBlock) void k_pair_pgrad(int na, const int* __restrict__ rowptr, const int* __restrict__ col,
+// (CUT here and in k_pair_tholegrad / k_pair_virial: the evaluation's inner table, rows end at rowend -- see k_pair_full)
+template <class T, bool CUT>
+__global__ __launch_bounds__(kPairBlock) void k_pair_pgrad(int na, const int* __restrict__ rowptr,
+                                                           const int* __restrict__ rowend, const int* __restrict__ col,
                                                            const Site<T>* __restrict__ sites, Box<T> box, ScaleTab<T> tab,
                                                            double* __restrict__ cls, const int* __restrict__ rows) {
   __shared__ T s_tab[48];
@@ -494,7 +504,7 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_pgrad(int na, const int* __
   double e0 = 0.0;
   if (slot < na) {
     const Site<T> I = sites[row];
-    const int end = rowptr[row + 1];
+    const int end = CUT ? rowend[row] : rowptr[row + 1];
     for (int k = rowptr[row] + sub; k < end; k += LPR) {
       const int c = col[k];
       const int nb = col_nb(c);
@@ -515,7 +525,8 @@ void launch_pscale_sums(hipStream_t st, int na, const NbrTable& nb, const Site<T
   if (rows) na = n_rows;
   if (na <= 0) return;
   const unsigned grid = (unsigned)(((long)na * 8 + kPairBlock - 1) / kPairBlock);
-  k_pair_pgrad<T><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, box, tab, cls16, rows);
+  if (nb.rowend) k_pair_pgrad<T, true><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, cls16, rows);
+  else k_pair_pgrad<T, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nullptr, nb.col, sites, box, tab, cls16, rows);
 }
 template void launch_pscale_sums<float>(hipStream_t, int, const NbrTable&, const Site<float>*, const Box<float>&,
                                         const ScaleTab<float>&, double*, const int*, int);
@@ -523,9 +534,9 @@ template void launch_pscale_sums<double>(hipStream_t, int, const NbrTable&, cons
                                          const ScaleTab<double>&, double*, const int*, int);
 
 // per-atom sums of d(pair energy)/d ln(au) (pair_thole_logderiv): sumX[i] = sum_j X_ij, sumXw[i] = sum_j X_ij wth_ij
-template <class T>
+template <class T, bool CUT>
 __global__ __launch_bounds__(kPairBlock) void k_pair_tholegrad(int na, const int* __restrict__ rowptr,
-                                                               const int* __restrict__ col,
+                                                               const int* __restrict__ rowend, const int* __restrict__ col,
                                                                const Site<T>* __restrict__ sites, Box<T> box,
                                                                ScaleTab<T> tab, T* __restrict__ sumX, T* __restrict__ sumXw,
                                                                const int* __restrict__ rows) {
@@ -538,7 +549,7 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_tholegrad(int na, const int
   T sx = 0, sw = 0;
   if (slot < na) {
     const Site<T> I = sites[row];
-    const int end = rowptr[row + 1];
+    const int end = CUT ? rowend[row] : rowptr[row + 1];
     for (int k = rowptr[row] + sub; k < end; k += LPR) {
       const int c = col[k];
       const int nb = col_nb(c);
@@ -559,7 +570,8 @@ void launch_thole_sums(hipStream_t st, int na, const NbrTable& nb, const Site<T>
   if (rows) na = n_rows;
   if (na <= 0) return;
   const unsigned grid = (unsigned)(((long)na * 8 + kPairBlock - 1) / kPairBlock);
-  k_pair_tholegrad<T><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, box, tab, sumX, sumXw, rows);
+  if (nb.rowend) k_pair_tholegrad<T, true><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, sumX, sumXw, rows);
+  else k_pair_tholegrad<T, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nullptr, nb.col, sites, box, tab, sumX, sumXw, rows);
 }
 
 template <class T>
@@ -569,9 +581,11 @@ void launch_mscale_sums(hipStream_t st, int kind, int na, const NbrTable& nb, co
   if (na <= 0) return;
   const unsigned grid = (unsigned)(((long)na * 8 + kPairBlock - 1) / kPairBlock);
   const T rc2 = (T)(cutoff * cutoff);
-  if (kind == 0) k_pair_mgrad<T, 0><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, T(0), rows);
-  else if (kind == 1) k_pair_mgrad<T, 1><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, rc2, rows);
-  else k_pair_mgrad<T, 2><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, rc2, rows);
+  if (kind == 0 && cutoff > 0.0)
+    k_pair_mgrad<T, 0, true><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, rc2, rows);
+  else if (kind == 0) k_pair_mgrad<T, 0, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, T(0), rows);
+  else if (kind == 1) k_pair_mgrad<T, 1, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, rc2, rows);
+  else k_pair_mgrad<T, 2, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, pos, par, box, pmax, cls16, rc2, rows);
 }
 
 // ---- box gradient, real-space part (jax.grad(get_energy, argnums=1) in the reference) -----------------------
@@ -587,9 +601,9 @@ __device__ __forceinline__ void block_add9(double acc[9], double scale, double* 
   }
 }
 
-template <class T, bool LPOL>
+template <class T, bool LPOL, bool CUT>
 __global__ __launch_bounds__(kPairBlock) void k_pair_virial(int na, const int* __restrict__ rowptr,
-                                                            const int* __restrict__ col, const Site<T>* __restrict__ sites,
+                                                            const int* __restrict__ rowend, const int* __restrict__ col, const Site<T>* __restrict__ sites,
                                                             Box<T> box, ScaleTab<T> tab, T kappa, double* vir,
                                                             const int* __restrict__ rows) {
   __shared__ T s_tab[48];
@@ -601,7 +615,7 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_virial(int na, const int* _
   if (slot < na) {
     const int row = rows ? rows[slot] : slot;           // (slab rank: its home rows)
     const Site<T> I = sites[row];
-    const int end = rowptr[row + 1];
+    const int end = CUT ? rowend[row] : rowptr[row + 1];
 #pragma unroll 1
     for (int k = rowptr[row] + sub; k < end; k += LPR) {
       const int c = col[k];
@@ -667,8 +681,12 @@ void launch_pair_virial(hipStream_t st, int na, const NbrTable& nb, const Site<T
   if (rows) na = n_rows;
   if (na <= 0) return;
   const unsigned grid = (unsigned)(((long)na * 8 + kPairBlock - 1) / kPairBlock);
-  if (lpol) k_pair_virial<T, true><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, box, tab, kappa, vir, rows);
-  else k_pair_virial<T, false><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, box, tab, kappa, vir, rows);
+#define VCALL(LP, CUT) \
+  k_pair_virial<T, LP, CUT><<<grid, kPairBlock, 0, st>>>(na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, kappa, vir, rows)
+  if (nb.rowend) { if (lpol) VCALL(true, true); else VCALL(false, true); }
+  else if (lpol) VCALL(true, false);
+  else VCALL(false, false);
+#undef VCALL
 }
 template <class T>
 void launch_scalar_pair_virial(hipStream_t st, int tt, int na, const NbrTable& nb, const T* pos, const T* par,
@@ -770,21 +788,18 @@ void launch_pair_full(hipStream_t st, int na, const NbrTable& nb, const Site<T>*
   const int minw = pair_min_waves<T>();
   static const bool mono_off = [] { const char* e = getenv("ADMP_PAIR_MONO"); return e && atoi(e) == 0; }();
   if (mono_off || !cls_flags || !rq) use_mono = 0;
+#define FULL(LP, L, MW, CUT)                                                                                           \
+  k_pair_full<T, LP, L, MW, CUT><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                    \
+      na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L),      \
+      use_mono, cls_flags, rq, tholes)
 #define CALL(L)                                                                                                        \
-  if (lpol && minw >= 2)                                                                                               \
-    k_pair_full<T, true, L, 2><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                      \
-        na, nb.rowptr, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L), use_mono,     \
-        cls_flags, rq, tholes);                                                                                        \
-  else if (lpol)                                                                                                       \
-    k_pair_full<T, true, L, 1><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                      \
-        na, nb.rowptr, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L), use_mono,     \
-        cls_flags, rq, tholes);                                                                                        \
-  else                                                                                                                 \
-    k_pair_full<T, false, L, 2><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                     \
-        na, nb.rowptr, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L), use_mono, cls_flags, rq,    \
-        tholes)
+  if (lpol && minw >= 2) { if (nb.rowend) FULL(true, L, 2, true); else FULL(true, L, 2, false); }                      \
+  else if (lpol) { if (nb.rowend) FULL(true, L, 1, true); else FULL(true, L, 1, false); }                              \
+  else if (nb.rowend) FULL(false, L, 2, true);                                                                         \
+  else FULL(false, L, 2, false)
   ADMP_LPR_SWITCH(lpr, CALL)
 #undef CALL
+#undef FULL
 }
 
 template <class T>
@@ -795,12 +810,14 @@ void launch_pair_field(hipStream_t st, int na, const NbrTable& nb, const Site<T>
   if (mono_off || !rq) cls_flags = nullptr;
   if (na <= 0) return;
   const int lpr = field_lanes_per_row(na, false);
-#define CALL(L)                                                                                              \
-  k_pair_field<T, L><<<xcd_grid(grid_for(na, L)), kPairBlock, 0, st>>>(na, nb.rowptr, nb.col, sites, box, tab, kappa, \
-                                                                       fld, rows, grid_for(na, L), n_dev, cls_flags, \
-                                                                       rq, tholes)
+#define FIELD(L, CUT)                                                                                                  \
+  k_pair_field<T, L, CUT><<<xcd_grid(grid_for(na, L)), kPairBlock, 0, st>>>(na, nb.rowptr, nb.rowend, nb.col, sites, box, \
+                                                                            tab, kappa, fld, rows, grid_for(na, L), n_dev, \
+                                                                            cls_flags, rq, tholes)
+#define CALL(L) if (nb.rowend) FIELD(L, true); else FIELD(L, false)
   ADMP_LPR_SWITCH(lpr, CALL)
 #undef CALL
+#undef FIELD
 }
 // the field kernels as riders of an x pass (k_xconv_pair): false = this launch cannot ride (no rows, another lane count)
 constexpr int kRiderLpr = 16;
@@ -811,7 +828,7 @@ bool field_rider_full(FieldRider<T>& r, int na, const NbrTable& nb, const Site<T
   static const bool mono_off = [] { const char* e = getenv("ADMP_PAIR_MONO"); return e && atoi(e) == 0; }();
   if (mono_off || !rq) cls_flags = nullptr;
   if (na <= 0 || field_lanes_per_row(na, false) != kRiderLpr) return false;
-  r.kind = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nullptr; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
+  r.kind = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nb.rowend; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
   r.kappa = kappa; r.fld = fld; r.rows = rows; r.nblocks = grid_for(na, kRiderLpr); r.grid = xcd_grid(r.nblocks);
   r.n_dev = n_dev; r.cls_flags = cls_flags; r.rq = rq; r.tholes = tholes;
   return true;
@@ -836,7 +853,9 @@ void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spe
   const unsigned extra = (fr.grid + (unsigned)K[1] - 1) / (unsigned)K[1];
   const XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
                         reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
-  k_xconv_pair<T, kRiderLpr><<<dim3((unsigned)nbx + extra, (unsigned)K[1], 1), kPairBlock, sh, st>>>(xa, fr, nbx);
+  const dim3 grid((unsigned)nbx + extra, (unsigned)K[1], 1);
+  if (fr.kind == 1 && fr.rowend) k_xconv_pair<T, kRiderLpr, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+  else k_xconv_pair<T, kRiderLpr, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
 }
 
 template <class T>

@@ -52,6 +52,8 @@ def main():
     ap.add_argument('--prune', type=int, default=0, help='steps between prunings of an inner list (admp_prune_pairs; 0: walk the whole skin '
                     'list).  Pays from ~200k atoms on; the drift of an NVE run grows with it: the multipolar kernels evaluate every listed '
                     'pair, and the set of pairs beyond rc changes at every prune')
+    ap.add_argument('--cut', action='store_true', help='set_cutoff(rc) on the three calculators: every term is then the one of the '
+                    'exact-rc list whatever the age of the skin list (default off: every listed pair counts, as in the reference)')
     ap.add_argument('--minimize', type=int, default=200)
     ap.add_argument('--temp', type=float, default=300.0)
     ap.add_argument('--mesh', type=int, default=0, help='PME mesh size per dimension (0: the reference rule)')
@@ -85,6 +87,9 @@ def main():
                 obj.update_env(k, opt.mesh)
     tt_obj = generate_pairwise_interaction(TT_damping_qq_c6_kernel, cov, static_args={})
     tt = value_and_grad(tt_obj)
+    if opt.cut:
+        for obj in (pme, disp, tt_obj):
+            obj.set_cutoff(rc)
     o = 3 * np.arange(n_mol)
     bonds = np.stack([np.concatenate([o, o]), np.concatenate([o + 1, o + 2])], axis=1)
     angles = np.stack([o + 1, o, o + 2], axis=1)

@@ -96,18 +96,22 @@ int64_t admp_num_pairs(const admp_handle* h);   /* pairs kept (i < j) */
 /* Verlet lists with a skin (MD drivers rebuild the list every few steps with rc + skin): pairs of the list whose
  * minimum-image distance is >= rc are skipped by the pair kernels, so that the result is the one of the exact-rc list
  * whatever the skin.  rc = 0 (default): every listed pair is evaluated -- what the reference does with whatever list it is
- * handed (admp/pme.py:671-729 has no distance test).  Not a speed option (the kernels wait on the partner fetches, not on
- * the pair arithmetic).  Honoured by the dispersion and Tang-Toennies pair kernels and by everything derived from them
- * (admp_disp_energy_grad, admp_tt_energy_grad, their box gradients, admp_disp_param_grad, admp_tt_param_grad, admp_mscale_grad
- * kinds 1 and 2: the derivatives are those of the energy the calculator returns); the multipolar PME kernels evaluate
- * every listed pair. */
+ * handed (admp/pme.py:671-729 has no distance test).  Honoured by every pair kernel and everything derived from them: the
+ * dispersion and Tang-Toennies kernels test each partner (admp_disp_energy_grad, admp_tt_energy_grad, their box gradients,
+ * admp_disp_param_grad, admp_tt_param_grad, admp_mscale_grad kinds 1 and 2); a multipolar PME evaluation with rc > 0 first
+ * writes the inner table of the table it walks (owned, borrowed or pruned) at its own sites -- the entries below rc, rows in
+ * place order, no host synchronisation -- and every pair pass of the call walks that (admp_pme_energy_grad with all its SCF
+ * forms, admp_pme_energy_fixed_dipoles, admp_pme_box_grad, admp_thole_sums, admp_pscale_grad; admp_mscale_grad kind 0 tests
+ * each partner).  The derivatives are those of the energy the calculator returns. */
 int admp_set_cutoff(admp_handle* h, double rc);
 /* MD loops with a Verlet skin (no counterpart in the reference, which evaluates whatever list it is given): until the next
  * list build the calculators of `h` -- and of every handle that borrows its table -- walk an INNER table: the entries of the
  * current one whose minimum-image distance at `positions` (DEVICE pointer, (Na,3) real) is below rc, rows compacted in place
  * order.  A driver that rebuilds the outer list (rc + skin) every n steps prunes it to rc + skin_inner every m < n steps,
- * skin_inner = twice what an atom can move in m steps: the multipolar kernels, which evaluate every listed pair, then do
- * (rc + skin_inner)^3 / (rc + skin)^3 of the work, and so do the cutoff-testing dispersion / pair-potential kernels.  Pruning
+ * skin_inner = twice what an atom can move in m steps: the multipolar kernels then do (rc + skin_inner)^3 / (rc + skin)^3 of
+ * the work, and so do the cutoff-testing dispersion / pair-potential kernels.  Without admp_set_cutoff the multipolar kernels
+ * evaluate every entry of the inner table (pairs between rc and rc + skin_inner included); with it they walk the entries below
+ * rc of the inner table, and pruning only saves the per-call pass that finds them.  Pruning
  * always starts from the table as built; rc <= 0 goes back to it.  Single-rank handles that own their table.  One host
  * synchronisation. */
 int admp_prune_pairs(admp_handle* h, const void* positions, const double* box, double rc);
