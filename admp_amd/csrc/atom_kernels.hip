@@ -727,12 +727,10 @@ void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<
                    const int* list, int nlist, const FieldFin<T>& ff, const int* slab_bits) {
   // molecular liquid at scale: one thread per frame group (below ~8k atoms the 4-lane pull form is faster: latency bound).
   // ADMP_FINISH_GROUPS_MIN overrides the threshold; read per call so that the parity tests can force either form.
-  const char* gmin_env = getenv("ADMP_FINISH_GROUPS_MIN");
-  const int gmin = gmin_env ? atoi(gmin_env) : 8192;
+  const int gmin = env_int("ADMP_FINISH_GROUPS_MIN", 8192);
   if ((!list || slab_bits) && top.ngroups > 0 && top.na > gmin) {
     // ADMP_FINISH_ROWS=0: the one-thread-per-group form of round 2 (A/B, tests)
-    const char* rows_env = getenv("ADMP_FINISH_ROWS");
-    if (top.rows_blk && !(rows_env && atoi(rows_env) == 0))
+    if (top.rows_blk && env_flag("ADMP_FINISH_ROWS", true))      // (per call as well)
       k_finish_rows<T><<<top.nrowblk < 1024 ? top.nrowblk : 1024, kFinishBlock, 0, st>>>(top, box, sites, pol, lpol, kappa, pot, grad,
                                                                                          dQlocal, energies, ff,
                                                                                          list ? slab_bits : nullptr);
@@ -743,7 +741,7 @@ void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<
   }
   if (!list && top.inv_ptr)   // single GPU: pull formulation, no atomics
   {
-    static const int lanes4_max = [] { const char* e = getenv("ADMP_FINISH4_MAX"); return e ? atoi(e) : 8192; }();
+    static const int lanes4_max = env_int("ADMP_FINISH4_MAX", 8192);
     if (top.na <= lanes4_max)   // 3072 atoms: 9.6 vs 14.5 us; 30k atoms: 19.9 vs 14.2 us; 98k: 47 vs 21 us
       k_finish_pull<T, 4><<<nblk(4 * top.na), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad,
                                                                    dQlocal, energies, ff);

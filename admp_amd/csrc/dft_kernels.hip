@@ -4,6 +4,7 @@
 // Every block stages a tile of lines in LDS as j <-> N-j pair sums, then one thread produces one output pair.
 // At 97^3 (f64) the whole chain is ~0.9 GFLOP of f64 FMAs; the lines come out of L2 / Infinity Cache (7 MB spectrum).
 #include "dft_lines.h"
+#include "env.h"
 
 namespace admp {
 
@@ -709,7 +710,7 @@ void launch_dft_x_mix(hipStream_t st, const int K[3], const T* tw, T* spec, cons
 // the two plane kernels in place of launch_dft_z + launch_dft_y (forward) / launch_dft_y + launch_dft_z (inverse)
 template <class T>
 bool dft_zy_fits(const int K[3]) {
-  static const bool off = [] { const char* e = getenv("ADMP_DFT_PLANES"); return e && atoi(e) == 0; }();
+  static const bool off = !env_flag("ADMP_DFT_PLANES", true);
   // two workgroups per plane must fit the chip in one round (one workgroup per CU): with more planes the separate passes win
   return !off && 2 * K[0] <= 256 && ZyLayout<T>(K[1], K[2]).total + 2048 <= 160 * 1024;      // (+ the kernels' static LDS)
 }
@@ -717,7 +718,7 @@ bool dft_zy_fits(const int K[3]) {
 // run at a twentieth of the f64 rate on this chip (tools/ubench/lds_atomics.hip)
 template <class T>
 bool dft_zy_spread_fits(const int K[3], int na) {
-  static const int mx = [] { const char* e = getenv("ADMP_FUSE_SPREAD_MAX"); return e ? atoi(e) : 8192; }();
+  static const int mx = env_int("ADMP_FUSE_SPREAD_MAX", 8192);
   return sizeof(T) == 8 && na > 0 && na <= mx && na <= kZySpreadMaxAtoms && dft_zy_fits<T>(K) && zy_spread_sub<T>(K[1], K[2]) >= 16;
 }
 template <class T>

@@ -29,6 +29,7 @@
 #include "dft_math.h"
 #include "launch.h"
 #include "rccl_comm.h"
+#include "scf_policy.h"
 
 using namespace admp;
 
@@ -352,7 +353,7 @@ struct EngineBase {
 
   // row order of the freshly built table (see launch_row_order); ADMP_PAIR_SORT=0 keeps the natural order
   void order_rows() {
-    static const bool off = [] { const char* e = getenv("ADMP_PAIR_SORT"); return e && atoi(e) == 0; }();
+    static const bool off = !env_flag("ADMP_PAIR_SORT", true);
     if (off) {
       if (nbr.order) { (void)hipFree(nbr.order); nbr.order = nullptr; }
       if (nbr.order_plain) { (void)hipFree(nbr.order_plain); nbr.order_plain = nullptr; }
@@ -459,7 +460,7 @@ struct EngineBase {
         } else if (i - r >= kMaxGroup) ok = false;
       }
       gp.push_back(na);
-      static const bool off = [] { const char* e = getenv("ADMP_FINISH_GROUPS"); return e && atoi(e) == 0; }();
+      static const bool off = !env_flag("ADMP_FINISH_GROUPS", true);
       if (ok && !off) {
         HIP_TRY(hipMalloc(&top.grp_ptr, sizeof(int) * gp.size()));
         HIP_TRY(hipMemcpy(top.grp_ptr, gp.data(), sizeof(int) * gp.size(), hipMemcpyHostToDevice));
@@ -594,17 +595,8 @@ struct Engine : EngineBase {
   // validity of the cached G table
   struct TabKey { double box[9] = {0}, kappa = -1; int K[3] = {0, 0, 0}, Y0 = 0, ref = 0; bool pfa = false; } tabkey[4];
   static int tab_slot(int which) { return which == 1 ? 0 : (which == 6 ? 1 : (which == 8 ? 2 : 3)); }
-  bool warm_regime = false;   // previous polarizable call converged at its first SCF check
-  // Residual history of consecutive polarizable calls (MD: every call starts from the previous call's dipoles): the residual
-  // of a call's first check is the previous call's last residual plus what one step of motion adds.  scf_growth = that
-  // increase as last observed after a call of the same kind, scf_last = the residual the previous call ended with (< 0: no history).  The first cycle is
-  // evaluated speculatively with the full kernels only when scf_last + scf_growth predicts that its check will pass.
-  double scf_last = -1.0;
-  double scf_growth[2][2] = {{0.0, 0.0}, {0.0, 0.0}};    // the last two observed increases after a call without / with a Jacobi
-  int scf_nobs[2] = {0, 0};                              // step (they differ: the residual is a maximum norm, not additive);
-  int scf_state = 0;                                     // a prediction needs two observations of the current kind
-  double scf_contract = -1.0;   // factor by which one Jacobi step shrank the residual in the last call that took steps
-                                // ((last / first residual)^(1 / steps); < 0: never observed)
+  static_assert(kScfChainSteps == E_CHAIN, "one residual word per chained Jacobi step");
+  ScfHistory scf;             // residual history of the polarizable calls of this handle: picks the form of the next one
   bool mono_ok = false;       // this evaluation may use the charge-only pair forms (no dE/dQ_local requested)
 
   ~Engine() override {
@@ -700,7 +692,7 @@ struct Engine : EngineBase {
     // Columns of the ordered compaction.  Only `rows` (the home rows in the table's order: a different sequence) takes a pass
     // of its own; home / polarizable home / the per-peer import, export and migrant columns are bins of ONE pass over the atoms
     // (slab_kernels.hip k_slab_bins; ADMP_SLAB_BINS=0: a pass per column as in round 3, for A/B and tests).
-    static const bool bins_on = [] { const char* e = getenv("ADMP_SLAB_BINS"); return !(e && atoi(e) == 0); }();
+    static const bool bins_on = env_flag("ADMP_SLAB_BINS", true);
     SlabCols cs;
     SlabBins sb;
     sb.N = bins_on ? N : 0; sb.me = me;
@@ -846,7 +838,7 @@ struct Engine : EngineBase {
     // fused-x path: the kz rows of the spectrum are padded to whole 128-byte lines.  With K2/2+1 = 129 complex numbers per row
     // every row of a tile straddles two lines; padded to 144, rocFFT's batched 2-D r2c / c2r of the 256^3 f32 mesh take
     // 61 / 64 us instead of 88 / 91 (tools/ubench/rocfft_yz_layouts.cpp).
-    static const bool fx_off = [] { const char* e = getenv("ADMP_FUSED_X"); return e && atoi(e) == 0; }();
+    static const bool fx_off = !env_flag("ADMP_FUSED_X", true);
     const bool want_fx = snranks == 1 && !fx_off && fftx_usable(K[0]);
     const size_t per_line = 128 / (2 * sizeof(T));
     // (a slab rank pads the rows of its batched 2-D transforms the same way; the transposes carry the unpadded rows)
@@ -955,8 +947,7 @@ struct Engine : EngineBase {
   void setup_dft() {
     use_dft = use_pfa = false;
     if (snranks != 1) return;
-    const char* e = getenv("ADMP_DFT");
-    const int mode = e ? atoi(e) : -1;
+    const int mode = env_int("ADMP_DFT", -1);      // (read at every set-up)
     if (mode == 0) return;
     bool small = true, hard = false;
     for (int d = 0; d < 3; ++d) {
@@ -981,7 +972,7 @@ struct Engine : EngineBase {
   // Two-level direct DFT (pfa_kernels.hip): every dimension either fits the plain lines (<= 160) or splits into a smooth
   // cofactor N1 <= 32 and a prime power N2 <= 160.  ADMP_DFT=2 forces it for any mesh it can split (tests); ADMP_PFA=0 off.
   bool setup_pfa() {
-    static const bool off = [] { const char* e = getenv("ADMP_PFA"); return e && atoi(e) == 0; }();
+    static const bool off = !env_flag("ADMP_PFA", true);
     if (off) return false;
     for (int d = 0; d < 3; ++d)
       if (!pfa_split(K[d], &pfa.ax[d])) return false;
@@ -1031,7 +1022,7 @@ struct Engine : EngineBase {
   }
   // rider: an SCF field kernel whose workgroups run inside the x pass (pair_kernels.hip k_xconv_pair; direct-DFT meshes only)
   bool rider_ok() const {
-    static const bool on = [] { const char* e = getenv("ADMP_FIELD_RIDER"); return !(e && atoi(e) == 0); }();
+    static const bool on = env_flag("ADMP_FIELD_RIDER", true);
     return on && use_dft && !use_pfa && snranks == 1 && !overlap_ok();
   }
   bool convolve(T* mesh_p, T* spec_p, const T* gtab, int slot, T* accum = nullptr, T* out = nullptr,
@@ -1312,7 +1303,7 @@ struct Engine : EngineBase {
     // base planes of all atoms first: a 28-byte-per-atom pass (k_atom_bases).  The first evaluation of a handle / topology /
     // buffer, and evaluations that recompile the table's site classes, take the all-atom pass below, so that every row of
     // `sites` has held valid data at least once (the class compilation reads all of them).  ADMP_SLAB_SUBSET=0: always all.
-    static const bool subset_on = [] { const char* e = getenv("ADMP_SLAB_SUBSET"); return !(e && atoi(e) == 0); }();
+    static const bool subset_on = env_flag("ADMP_SLAB_SUBSET", true);
     if (snranks > 1 && subset_on && slab_sites_na == na && slab_sites_ptr == sites.p && !cls_pending && have_pairs) {
       { TIMED("atom_bases"); launch_atom_bases<T>(stream, na, ev.pos, ev.g, bases_d.as<int4>()); }
       ev.bases = bases_d.as<int4>();
@@ -1457,8 +1448,8 @@ struct Engine : EngineBase {
   // step on one stream against 0.1929 with the side stream, and a third of the run-to-run spread), 30 us at 6144 atoms
   // (0.241 against 0.261 ms), more above.
   bool overlap_ok() const {
-    static const int mx = [] { const char* e = getenv("ADMP_OVERLAP_MAX"); return e ? atoi(e) : 200000; }();
-    static const int mn = [] { const char* e = getenv("ADMP_OVERLAP_MIN"); return e ? atoi(e) : 4096; }();
+    static const int mx = env_int("ADMP_OVERLAP_MAX", 200000);
+    static const int mn = env_int("ADMP_OVERLAP_MIN", 4096);
     return side_stream_on && snranks == 1 && top.na <= mx && top.na >= mn;
   }
   // An exception between on_side() and join_side() (a failed launch, a refused argument further down the call) would leave
@@ -1473,7 +1464,7 @@ struct Engine : EngineBase {
   // the main chain that follows (see recip_pass); larger ones first -- there the pair kernel is long and wants the early start.
   // ADMP_SIDE_FIRST = 0 / 1 forces one order (A/B).
   bool side_first() const {
-    static const int mode = [] { const char* e = getenv("ADMP_SIDE_FIRST"); return e ? atoi(e) : -1; }();
+    static const int mode = env_int("ADMP_SIDE_FIRST", -1);
     return mode >= 0 ? mode != 0 : top.na > 16384;
   }
   template <class F>
@@ -1518,8 +1509,7 @@ struct Engine : EngineBase {
   // k_gather_staged<.., FIN>); the launch_finish_only that follows is then a no-op.  ADMP_FUSE_FIN_MAX = 0 turns it off (A/B).
   bool fin_fused = false;
   bool fuse_fin_ok() const {
-    const char* e = getenv("ADMP_FUSE_FIN_MAX");       // (read per call: the parity tests run both forms in one process)
-    const int fin_max = e ? atoi(e) : 8192;
+    const int fin_max = env_int("ADMP_FUSE_FIN_MAX", 8192);       // (read per call: the parity tests run both forms in one process)
     return snranks == 1 && !ev.home && top.gath_blk && top.na <= fin_max;
   }
   FinishArgs<T> finish_args(bool want_grad, T* dQl) {
@@ -1637,10 +1627,9 @@ struct Engine : EngineBase {
   // Small systems are dispatch-bound: the SCF residual rides in the epilogue of the field gather that precedes a check
   // (field_epilogue(word) describes it; the check's own kernel is then skipped).  word: a zero word of the energy block.
   const unsigned long long* ff_done = nullptr;
-  bool fuse_ok() const {
-    static const int fuse_max = [] { const char* e = getenv("ADMP_FUSE_FF_MAX"); return e ? atoi(e) : 16384; }();
-    return top.na <= fuse_max && snranks == 1 && !ev.home;
-  }
+  // ADMP_FUSE_FF_MAX: atom count up to which a field finish rides in a gather
+  static int fuse_ff_max() { static const int v = env_int("ADMP_FUSE_FF_MAX", 16384); return v; }
+  bool fuse_ok() const { return top.na <= fuse_ff_max() && snranks == 1 && !ev.home; }
   FieldFin<T> field_epilogue(unsigned long long* word) {
     FieldFin<T> ff;
     if (!word || !fuse_ok()) return ff;
@@ -1797,9 +1786,27 @@ struct Engine : EngineBase {
     recip_pass(slot, [&] { on_side([&] { first_pair_field(); }); });
   }
 
-  void pme(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
-           const double* mS, const double* pS, void* U_, int max_cycle, double thresh, double* E, void* dpos_,
-           void* dQl_, int* ncyc, int* conv, int on_device) override {
+  // ---- Engine::pme: staging, the SCF in one of three forms (scf_policy.h picks it), the closing pass --------------------
+  // device views of the arrays of one call (the caller's own, or staging buffers of host arrays)
+  struct PmeIo {
+    const T *pos = nullptr, *Ql = nullptr, *pol = nullptr, *thole = nullptr;
+    T *U = nullptr, *dpos = nullptr, *dQl = nullptr;
+    T* gbuf = nullptr;           // the gradient rows of this call: dpos, or the internal buffer of an energy-only call
+    double* E = nullptr;         // the caller's four energy parts
+  };
+  // what the forms of the SCF hand to each other and to the closing pass
+  struct ScfRun {
+    // phi_valid: the mesh holds phi = c2r(G S) of the CURRENT dipoles (last SCF field evaluation, no update since):
+    // the closing gather can then reuse it instead of spreading and transforming again.
+    // phi_accum: that phi was assembled from increments, so no single k-space pass saw its energy -- the closing gather
+    // sums it over the atoms instead.
+    bool phi_valid = false, done = false, finished = false, phi_accum = false;
+    bool have_base = false;    // fld_pair / fld_recip / phi belong to the dipoles before the last Jacobi step
+    int cyc = 0, flag = 1, i = 0, n_act = 0;   // (i: the reference's loop variable, the cycle scf_loop starts from)
+    double f_first = -1.0, f_final = -1.0;     // residuals of the first and of the last check of this call
+  };
+  PmeIo stage_pme_io(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, void* U_, double* E, void* dpos_,
+                     void* dQl_, int on_device) {
     // (the one-shot dipole source is taken off the handle before anything can fail: a call that throws must not leave a
     // pointer behind for the next one)
     U_src_now = on_device ? U_src : nullptr;
@@ -1808,218 +1815,205 @@ struct Engine : EngineBase {
     ARG_CHECK(pos_ && box && Ql_ && E, "null argument");
     const int na = top.na;
     HIP_TRY(hipSetDevice(device));
-    const T* pos = stage_in(s_pos, pos_, 3 * (size_t)na, on_device);
-    const T* Ql = stage_in(s_Q, Ql_, 9 * (size_t)na, on_device);
-    const T* pol = lpol ? stage_in(s_pol, pol_, na, on_device) : nullptr;
-    const T* thole = lpol ? stage_in(s_thole, thole_, na, on_device) : nullptr;
-    T* U = nullptr;
+    PmeIo io;
+    io.E = E;
+    io.pos = stage_in(s_pos, pos_, 3 * (size_t)na, on_device);
+    io.Ql = stage_in(s_Q, Ql_, 9 * (size_t)na, on_device);
+    io.pol = lpol ? stage_in(s_pol, pol_, na, on_device) : nullptr;
+    io.thole = lpol ? stage_in(s_thole, thole_, na, on_device) : nullptr;
     if (lpol) {
       ARG_CHECK(U_, "polarizable handle needs U_inout");
-      if (on_device) U = reinterpret_cast<T*>(U_);
-      else { s_U.need(3 * (size_t)na * sizeof(T)); HIP_TRY(hipMemcpyAsync(s_U.p, U_, 3 * (size_t)na * sizeof(T), hipMemcpyHostToDevice, stream)); U = s_U.as<T>(); }
+      if (on_device) io.U = reinterpret_cast<T*>(U_);
+      else { s_U.need(3 * (size_t)na * sizeof(T)); HIP_TRY(hipMemcpyAsync(s_U.p, U_, 3 * (size_t)na * sizeof(T), hipMemcpyHostToDevice, stream)); io.U = s_U.as<T>(); }
     }
-    T* dpos = nullptr;
     if (dpos_) {
-      if (on_device) dpos = reinterpret_cast<T*>(dpos_);
-      else { s_out.need(3 * (size_t)na * sizeof(T)); dpos = s_out.as<T>(); }
+      if (on_device) io.dpos = reinterpret_cast<T*>(dpos_);
+      else { s_out.need(3 * (size_t)na * sizeof(T)); io.dpos = s_out.as<T>(); }
     }
-    T* dQl = nullptr;
     if (dQl_) {
       ARG_CHECK(dpos_, "dE_dQlocal requires dE_dpos");
-      if (on_device) dQl = reinterpret_cast<T*>(dQl_);
-      else { s_dQ.need(9 * (size_t)na * sizeof(T)); dQl = s_dQ.as<T>(); }
+      if (on_device) io.dQl = reinterpret_cast<T*>(dQl_);
+      else { s_dQ.need(9 * (size_t)na * sizeof(T)); io.dQl = s_dQ.as<T>(); }
     }
     grad.need(3 * (size_t)na * sizeof(T));   // the gradient buffer is needed internally even for energy-only calls
-    T* gbuf = dpos ? dpos : grad.as<T>();
-    mono_ok = (dQl == nullptr);
+    io.gbuf = io.dpos ? io.dpos : grad.as<T>();
+    mono_ok = (io.dQl == nullptr);
+    return io;
+  }
+  void unstage_pme_io(const PmeIo& io, void* U_, void* dpos_, void* dQl_, int on_device) {
+    if (on_device) return;
+    const int na = top.na;
+    if (dpos_) HIP_TRY(hipMemcpyAsync(dpos_, io.dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (dQl_) HIP_TRY(hipMemcpyAsync(dQl_, io.dQl, 9 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (lpol) HIP_TRY(hipMemcpyAsync(U_, io.U, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  // A closing pass that was enqueued ahead of its check and ran for nothing: undo its energy sums (self and penalty words;
+  // atom_parts: the reciprocal energy its gather summed over the atoms as well).  Gradient / dQ are rewritten by the regular
+  // closing pass.
+  void undo_closing_sums(bool atom_parts) {
+    HIP_TRY(hipMemsetAsync(Ed_cur() + E_SELF, 0, 2 * sizeof(double), stream));
+    if (atom_parts) HIP_TRY(hipMemsetAsync(Ed_cur() + E_SLOTS, 0, E_PARTS * sizeof(double), stream));
+  }
+  // Chained form (up to 200k atoms; at 3072 atoms a host synchronisation costs as much as three kernels): when the history says the
+  // first check will fail and n Jacobi steps will do, the whole call is enqueued at once -- first field evaluation and its
+  // check, then n times (Jacobi step GATED on the previous check's residual on the device: a zero step once a check has
+  // passed, after which every later residual repeats the passing one; increment; check), the closing pass -- and read back
+  // with one synchronisation.  The host then replays the reference's decisions on the n + 1 residuals: same dipoles,
+  // cycle count and flag as the plain loop; a wrong guess costs the kernels that ran for nothing (closing pass when more
+  // cycles are needed, increments after the check that passed).
+  void scf_chained(ScfRun& run, int nhat, const PmeIo& io, double thresh) {
+    const int n_act = run.n_act = nact_known();
+    recip_pass_first_field(E_SCF_RECIP);
+    auto word = [&](int k) {      // residual of check k: E_FMAX, then the (still zero) chain words of this evaluation
+      return k == 0 ? fmax_word() : reinterpret_cast<unsigned long long*>(Ed_cur() + E_FMAX1 + (k - 1));
+    };
+    next_check_word();
+    first_gather_field(field_epilogue(word(0)));
+    launch_field_check(word(0));
+    const bool early_full = overlap_ok();       // the closing pair kernel next to the last increment's mesh chain
+    // the last residual rides in the closing gather (it reads the accumulated phi anyway): the field gather of the last
+    // increment is not run (small single-rank systems; ADMP_CHAIN_LAST_FIELD=1 keeps it: A/B, tests)
+    static const bool keep_last = env_flag("ADMP_CHAIN_LAST_FIELD", false);
+    const bool last_in_gather = fuse_ok() && !keep_last && n_act > 0;
+    for (int c = 0; c < nhat; ++c) {
+      scf_jacobi(n_act, word(c), thresh);        // a zero step once a check has passed: later residuals repeat it
+      const bool last = c == nhat - 1;
+      if (early_full && last)      // (the dipoles are final now)
+        scf_increment(n_act, word(c + 1), [&] { stage_pair_full(io.gbuf); }, last_in_gather);
+      else
+        scf_increment(n_act, word(c + 1), nullptr, last && last_in_gather);
+      if (!(last && last_in_gather)) launch_field_check(word(c + 1));
+    }
+    if (!early_full) stage_pair_full(io.gbuf);
+    const FinishArgs<T> fin_c = finish_args(io.dpos != nullptr, io.dQl);
+    if (last_in_gather) {
+      const FieldFin<T> ffl = field_epilogue(word(nhat));
+      stage_gather(mesh.as<T>(), io.gbuf, fld_recip.as<T>(), false, Ed_cur() + E_SLOTS, &fin_c, &ffl);
+      launch_field_check(word(nhat));            // (done by the epilogue: clears the mark)
+    } else {
+      stage_gather(mesh.as<T>(), io.gbuf, nullptr, false, Ed_cur() + E_SLOTS, &fin_c);
+    }
+    launch_finish_only(io.dpos ? io.gbuf : nullptr, io.dQl);
+    read_energies(E_PARTS_SUM, io.E);
+    nact_seen();
+    run.f_first = Eh[E_FMAX];
+    run.have_base = true;
+    run.phi_accum = true;
+    int hit = -1;
+    for (int k = 0; k <= nhat && hit < 0; ++k)
+      if ((k == 0 ? Eh[E_FMAX] : Eh[E_FMAX1 + k - 1]) < thresh) hit = k;
+    if (hit >= 0) {
+      run.i = hit;
+      run.f_final = hit == 0 ? Eh[E_FMAX] : Eh[E_FMAX1 + hit - 1];
+      run.phi_valid = run.done = run.finished = true;
+      ev.active = false;
+      if (hit < nhat) { ++scf_stats[5]; scf_stats[6] += nhat - hit; }
+    } else {
+      ++scf_stats[4];   // more cycles are needed: undo the energy sums of the closing pass, go on like the plain loop
+      undo_closing_sums(true);
+      run.f_final = Eh[E_FMAX1 + nhat - 1];
+      scf_jacobi(n_act);
+      run.i = nhat + 1;
+    }
+  }
+  // Steady-state MD regime (the previous call converged at its first check): evaluate the FIRST SCF cycle
+  // with the full kernels -- they produce dE/dU alongside the gradient -- so that, when the check passes
+  // again, the step is already finished (no separate field kernels, no second pass).  Same arithmetic and
+  // same (U, flag, i) as the plain loop; a failed check only costs the difference between the kernels.
+  // The closing kernel is enqueued speculatively as well, so the step has ONE host synchronisation.
+  void scf_speculative(ScfRun& run, const PmeIo& io, double thresh) {
+    recip_pass(E_SCF_RECIP, [&] { on_side([&] { stage_pair_full(io.gbuf, fld_pair.as<T>()); }); });
+    // small systems are dispatch-bound: the field finish rides in the gather's epilogue; larger ones keep the two
+    // kernels (98k atoms: gather 26 -> 47 us fused against 9 us saved; 1M atoms: 0.40 vs 0.31 + 0.056 ms)
+    const bool fuse_ff = top.na <= fuse_ff_max();
+    const bool fuse_g = fuse_ff && snranks == 1;      // (not fuse_ok(): that one also asks for !ev.home)
+    const FinishArgs<T> fin_s = finish_args(io.dpos != nullptr, io.dQl);
+    stage_gather(mesh.as<T>(), io.gbuf, fld_recip.as<T>(), fuse_g, nullptr, fuse_g ? &fin_s : nullptr);
+    const bool pull = !ev.home && top.inv_ptr;          // the atomics-free closing kernel can carry the field finish
+    if (!fuse_g && !pull) launch_field_finish_only();
+    launch_finish_only(io.dpos ? io.gbuf : nullptr, io.dQl, !fuse_g && pull);
+    const double fmax = read_energies(E_SCF_RECIP, io.E);
+    run.f_first = run.f_final = fmax;
+    nact_seen();
+    run.n_act = nact_known();
+    if (fmax < thresh) {
+      run.phi_valid = run.done = run.finished = true;
+      ev.active = false;
+    } else {   // undo the speculative energy sums; gradient / dQ are rewritten by the regular closing pass
+      ++scf_stats[2];
+      undo_closing_sums(false);
+      scf_jacobi(run.n_act);
+      run.i = 1;
+      run.have_base = true;      // the full kernels left the field of the old dipoles behind: continue by increments
+    }
+  }
+  // the reference's loop (admp/pme.py:132-143), from cycle run.i on: the whole SCF of a plain call, what a failed guess of
+  // the other two forms left to do, nothing after a guess that held
+  void scf_loop(ScfRun& run, double thresh, int max_cycle) {
+    for (; !run.done && run.i < max_cycle; ++run.i) {     // admp/pme.py:132-138
+      if (!run.have_base) {        // first field evaluation of the call: everything, at the polarizable sites
+        recip_pass_first_field(E_SCF_RECIP);
+        unsigned long long* w = fuse_ok() ? next_check_word() : nullptr;
+        first_gather_field(field_epilogue(w));
+        run.have_base = true;
+      } else {
+        scf_increment(run.n_act, fuse_ok() ? next_check_word() : nullptr);
+        run.phi_accum = true;
+      }
+      const double fmax = scf_check(&run.n_act);
+      if (run.f_first < 0.0) run.f_first = fmax;
+      run.f_final = fmax;
+      if (fmax < thresh) { run.phi_valid = true; break; }
+      scf_jacobi(run.n_act);
+    }
+    if (run.i == max_cycle) run.i = max_cycle - 1;   // python's loop variable after exhaustion
+    run.cyc = run.i;
+    scf_stats[7] += run.cyc;
+    run.flag = (run.i != max_cycle - 1);             // admp/pme.py:139-143
+  }
+  // gradient, dE/dQ_local and the four energies at the final dipoles -- whatever of it the SCF has not produced already
+  void closing_pass(const ScfRun& run, const PmeIo& io) {
+    const bool atoms_energy = run.phi_valid && run.phi_accum;
+    if (!run.done) {
+      if (!run.phi_valid) recip_pass(E_RECIP, [&] { on_side([&] { stage_pair_full(io.gbuf); }); });
+      else stage_pair_full(io.gbuf);
+      // (the partial words are zero: nothing else of this evaluation writes them)
+      const FinishArgs<T> fin_t = finish_args(io.dpos != nullptr, io.dQl);
+      stage_gather(mesh.as<T>(), io.gbuf, nullptr, false, atoms_energy ? Ed_cur() + E_SLOTS : nullptr,
+                   run.finished ? nullptr : &fin_t);
+    }
+    if (!run.finished)
+      stage_finish(io.dpos ? io.gbuf : nullptr, io.dQl,
+                   atoms_energy ? (int)E_PARTS_SUM : (run.phi_valid ? (int)E_SCF_RECIP : (int)E_RECIP), io.E);
+    join_side();
+  }
 
-    stage_begin(pos, box, Ql, pol, thole, ns, mS, pS, U);
-
-    // phi_valid: the mesh holds phi = c2r(G S) of the CURRENT dipoles (last SCF field evaluation, no update since):
-    // the closing gather can then reuse it instead of spreading and transforming again.
-    // phi_accum: that phi was assembled from increments, so no single k-space pass saw its energy -- the closing gather
-    // sums it over the atoms instead.
-    bool phi_valid = false, done = false, finished = false, phi_accum = false;
-    int cyc = 0, flag = 1;
+  void pme(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
+           const double* mS, const double* pS, void* U_, int max_cycle, double thresh, double* E, void* dpos_,
+           void* dQl_, int* ncyc, int* conv, int on_device) override {
+    const PmeIo io = stage_pme_io(pos_, box, Ql_, pol_, thole_, U_, E, dpos_, dQl_, on_device);
+    stage_begin(io.pos, box, io.Ql, io.pol, io.thole, ns, mS, pS, io.U);
+    ScfRun run;
     if (lpol) {
       ARG_CHECK(max_cycle >= 1, "max_cycle must be >= 1");
-      int i = 0, n_act = 0;
-      bool have_base = false;    // fld_pair / fld_recip / phi belong to the dipoles before the last Jacobi step
       // which form of the first cycle: ADMP_SPECULATE=0 / 1 forces the plain / the speculative one (A/B, tests)
-      static const int spec_mode = [] { const char* e = getenv("ADMP_SPECULATE"); return e ? atoi(e) : -1; }();
-      // a failed speculation wastes the full pair kernel, the gather and the closing kernel; a successful one saves the field
-      // kernels and one synchronisation: at 3072 atoms that is 30 against 45 us, at 98k atoms about even, at 1M atoms 0.55
-      // against 0.18 ms -- very large systems speculate only on a clear prediction
-      const double spec_infl = top.na <= 200000 ? 1.0 : 1.5;    // weight of the observed growth (0 on a static geometry)
-      const bool have_pred = scf_last >= 0.0 && scf_nobs[scf_state] >= 2;
-      const double g_hi = std::max(scf_growth[scf_state][0], scf_growth[scf_state][1]);
-      const double g_lo = std::min(scf_growth[scf_state][0], scf_growth[scf_state][1]);
-      const bool speculate = spec_mode >= 0 ? spec_mode != 0
-                                            : (have_pred ? scf_last + spec_infl * g_hi < thresh : (scf_last < 0.0 && warm_regime));
-      double f_first = -1.0, f_final = -1.0;     // residuals of the first and of the last check of this call
-      // Chained form (up to 200k atoms; at 3072 atoms a host synchronisation costs as much as three kernels): when the history says the
-      // first check will fail and n Jacobi steps will do, the whole call is enqueued at once -- first field evaluation and its
-      // check, then n times (Jacobi step GATED on the previous check's residual on the device: a zero step once a check has
-      // passed, after which every later residual repeats the passing one; increment; check), the closing pass -- and read back
-      // with one synchronisation.  The host then replays the reference's decisions on the n + 1 residuals: same dipoles,
-      // cycle count and flag as the plain loop; a wrong guess costs the kernels that ran for nothing (closing pass when more
-      // cycles are needed, increments after the check that passed).
-      static const int chain_max = [] { const char* e = getenv("ADMP_SCF_CHAIN_MAX"); return e ? atoi(e) : 200000; }();
-      const double pred = have_pred ? scf_last + 0.5 * (g_hi + g_lo) : -1.0;
-      // number of Jacobi steps the history predicts: the residual contracts by scf_contract per step
-      int nhat = 0;
-      if (have_pred && scf_last + g_lo >= 1.1 * thresh && scf_contract > 0.0 && scf_contract < 0.95 && thresh > 0.0) {
-        double r = pred;
-        while (nhat <= E_CHAIN && r >= thresh) { r *= scf_contract; ++nhat; }
-      }
-      // (every input of these decisions is the same on every rank of a decomposed handle: the residuals are global maxima)
-      const bool chain = spec_mode < 0 && !speculate && top.na <= chain_max && nhat >= 1 && nhat <= E_CHAIN &&
-                         nhat + 2 <= max_cycle && (snranks > 1 || (!act_fresh && act_n > 0));
+      static const ScfSwitches sw = {env_int("ADMP_SPECULATE", -1), env_int("ADMP_SCF_CHAIN_MAX", 200000)};
+      const ScfPlan plan = scf.plan(thresh, top.na, max_cycle, snranks > 1 || (!act_fresh && act_n > 0), sw);
+      const bool chain = plan.form == ScfForm::chained, speculate = plan.form == ScfForm::speculative;
       static const bool scf_trace = getenv("ADMP_SCF_TRACE") != nullptr;     // one line per call: which form ran
       if (scf_trace) fprintf(stderr, "[admp scf] %s (predicted residual %.4g, threshold %.4g, %d steps)\n",
-                             chain ? "chained" : (speculate ? "speculative" : "plain"), pred, thresh, chain ? nhat : 0);
+                             chain ? "chained" : (speculate ? "speculative" : "plain"), plan.pred, thresh, chain ? plan.nhat : 0);
       ++scf_stats[chain ? 3 : (speculate ? 1 : 0)];
-      if (chain) {
-        n_act = nact_known();
-        recip_pass_first_field(E_SCF_RECIP);
-        auto word = [&](int k) {      // residual of check k: E_FMAX, then the (still zero) chain words of this evaluation
-          return k == 0 ? fmax_word() : reinterpret_cast<unsigned long long*>(Ed_cur() + E_FMAX1 + (k - 1));
-        };
-        next_check_word();
-        first_gather_field(field_epilogue(word(0)));
-        launch_field_check(word(0));
-        const bool early_full = overlap_ok();       // the closing pair kernel next to the last increment's mesh chain
-        // the last residual rides in the closing gather (it reads the accumulated phi anyway): the field gather of the last
-        // increment is not run (small single-rank systems; ADMP_CHAIN_LAST_FIELD=1 keeps it: A/B, tests)
-        static const bool keep_last = [] { const char* e = getenv("ADMP_CHAIN_LAST_FIELD"); return e && atoi(e) != 0; }();
-        const bool last_in_gather = fuse_ok() && !keep_last && n_act > 0;
-        for (int c = 0; c < nhat; ++c) {
-          scf_jacobi(n_act, word(c), thresh);        // a zero step once a check has passed: later residuals repeat it
-          const bool last = c == nhat - 1;
-          if (early_full && last)      // (the dipoles are final now)
-            scf_increment(n_act, word(c + 1), [&] { stage_pair_full(gbuf); }, last_in_gather);
-          else
-            scf_increment(n_act, word(c + 1), nullptr, last && last_in_gather);
-          if (!(last && last_in_gather)) launch_field_check(word(c + 1));
-        }
-        if (!early_full) stage_pair_full(gbuf);
-        const FinishArgs<T> fin_c = finish_args(dpos != nullptr, dQl);
-        if (last_in_gather) {
-          const FieldFin<T> ffl = field_epilogue(word(nhat));
-          stage_gather(mesh.as<T>(), gbuf, fld_recip.as<T>(), false, Ed_cur() + E_SLOTS, &fin_c, &ffl);
-          launch_field_check(word(nhat));            // (done by the epilogue: clears the mark)
-        } else {
-          stage_gather(mesh.as<T>(), gbuf, nullptr, false, Ed_cur() + E_SLOTS, &fin_c);
-        }
-        launch_finish_only(dpos ? gbuf : nullptr, dQl);
-        read_energies(E_PARTS_SUM, E);
-        nact_seen();
-        f_first = Eh[E_FMAX];
-        have_base = true;
-        phi_accum = true;
-        int hit = -1;
-        for (int k = 0; k <= nhat && hit < 0; ++k)
-          if ((k == 0 ? Eh[E_FMAX] : Eh[E_FMAX1 + k - 1]) < thresh) hit = k;
-        if (hit >= 0) {
-          i = hit;
-          f_final = hit == 0 ? Eh[E_FMAX] : Eh[E_FMAX1 + hit - 1];
-          phi_valid = done = finished = true;
-          ev.active = false;
-          if (hit < nhat) { ++scf_stats[5]; scf_stats[6] += nhat - hit; }
-        } else {
-          ++scf_stats[4];   // more cycles are needed: undo the energy sums of the closing pass, go on like the plain loop
-          HIP_TRY(hipMemsetAsync(Ed_cur() + E_SELF, 0, 2 * sizeof(double), stream));
-          HIP_TRY(hipMemsetAsync(Ed_cur() + E_SLOTS, 0, E_PARTS * sizeof(double), stream));
-          f_final = Eh[E_FMAX1 + nhat - 1];
-          scf_jacobi(n_act);
-          i = nhat + 1;
-        }
-      }
-      if (speculate) {
-        // Steady-state MD regime (the previous call converged at its first check): evaluate the FIRST SCF cycle
-        // with the full kernels -- they produce dE/dU alongside the gradient -- so that, when the check passes
-        // again, the step is already finished (no separate field kernels, no second pass).  Same arithmetic and
-        // same (U, flag, i) as the plain loop; a failed check only costs the difference between the kernels.
-        // The closing kernel is enqueued speculatively as well, so the step has ONE host synchronisation.
-        recip_pass(E_SCF_RECIP, [&] { on_side([&] { stage_pair_full(gbuf, fld_pair.as<T>()); }); });
-        // small systems are dispatch-bound: the field finish rides in the gather's epilogue; larger ones keep the two
-        // kernels (98k atoms: gather 26 -> 47 us fused against 9 us saved; 1M atoms: 0.40 vs 0.31 + 0.056 ms)
-        static const int fuse_max = [] { const char* e = getenv("ADMP_FUSE_FF_MAX"); return e ? atoi(e) : 16384; }();
-        const bool fuse_ff = top.na <= fuse_max;
-        const bool fuse_g = fuse_ff && snranks == 1;
-        const FinishArgs<T> fin_s = finish_args(dpos != nullptr, dQl);
-        stage_gather(mesh.as<T>(), gbuf, fld_recip.as<T>(), fuse_g, nullptr, fuse_g ? &fin_s : nullptr);
-        const bool pull = !ev.home && top.inv_ptr;          // the atomics-free closing kernel can carry the field finish
-        if (!fuse_g && !pull) launch_field_finish_only();
-        launch_finish_only(dpos ? gbuf : nullptr, dQl, !fuse_g && pull);
-        const double fmax = read_energies(E_SCF_RECIP, E);
-        f_first = f_final = fmax;
-        nact_seen();
-        n_act = nact_known();
-        if (fmax < thresh) {
-          phi_valid = done = finished = true;
-          ev.active = false;
-        } else {   // undo the speculative energy sums; gradient / dQ are rewritten by the regular closing pass
-          ++scf_stats[2];
-          HIP_TRY(hipMemsetAsync(Ed_cur() + E_SELF, 0, 2 * sizeof(double), stream));
-          scf_jacobi(n_act);
-          i = 1;
-          have_base = true;      // the full kernels left the field of the old dipoles behind: continue by increments
-        }
-      }
-      for (; !done && i < max_cycle; ++i) {     // admp/pme.py:132-138
-        if (!have_base) {        // first field evaluation of the call: everything, at the polarizable sites
-          recip_pass_first_field(E_SCF_RECIP);
-          unsigned long long* w = fuse_ok() ? next_check_word() : nullptr;
-          first_gather_field(field_epilogue(w));
-          have_base = true;
-        } else {
-          scf_increment(n_act, fuse_ok() ? next_check_word() : nullptr);
-          phi_accum = true;
-        }
-        const double fmax = scf_check(&n_act);
-        if (f_first < 0.0) f_first = fmax;
-        f_final = fmax;
-        if (fmax < thresh) { phi_valid = true; break; }
-        scf_jacobi(n_act);
-      }
-      if (i == max_cycle) i = max_cycle - 1;   // python's loop variable after exhaustion
-      cyc = i;
-      scf_stats[7] += cyc;
-      flag = (i != max_cycle - 1);             // admp/pme.py:139-143
-      warm_regime = (cyc == 0);
-      if (f_first >= 0.0) {
-        if (scf_last >= 0.0) {
-          scf_growth[scf_state][1] = scf_growth[scf_state][0];
-          scf_growth[scf_state][0] = f_first - scf_last;
-          ++scf_nobs[scf_state];
-        }
-        scf_last = f_final;
-        scf_state = cyc > 0 ? 1 : 0;
-        if (cyc >= 1 && f_first > 0.0 && f_final > 0.0 && f_final < f_first) scf_contract = std::pow(f_final / f_first, 1.0 / cyc);
-      }
+      if (chain) scf_chained(run, plan.nhat, io, thresh);
+      if (speculate) scf_speculative(run, io, thresh);
+      scf_loop(run, thresh, max_cycle);
+      scf.observe(run.f_first, run.f_final, run.cyc);
     }
-
-    const bool atoms_energy = phi_valid && phi_accum;
-    if (!done) {
-      if (!phi_valid) recip_pass(E_RECIP, [&] { on_side([&] { stage_pair_full(gbuf); }); });
-      else stage_pair_full(gbuf);
-      // (the partial words are zero: nothing else of this evaluation writes them)
-      const FinishArgs<T> fin_t = finish_args(dpos != nullptr, dQl);
-      stage_gather(mesh.as<T>(), gbuf, nullptr, false, atoms_energy ? Ed_cur() + E_SLOTS : nullptr, finished ? nullptr : &fin_t);
-    }
-    if (!finished)
-      stage_finish(dpos ? gbuf : nullptr, dQl, atoms_energy ? (int)E_PARTS_SUM : (phi_valid ? (int)E_SCF_RECIP : (int)E_RECIP), E);
-
-    join_side();
-    if (!on_device) {
-      if (dpos_) HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-      if (dQl_) HIP_TRY(hipMemcpyAsync(dQl_, dQl, 9 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-      if (lpol) HIP_TRY(hipMemcpyAsync(U_, U, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (ncyc) *ncyc = cyc;
-    if (conv) *conv = flag;
+    closing_pass(run, io);
+    unstage_pme_io(io, U_, dpos_, dQl_, on_device);
+    if (ncyc) *ncyc = run.cyc;
+    if (conv) *conv = run.flag;
   }
 
   // energy_fn / grad_U_fn / grad_pos_fn of the reference (admp/pme.py:69-78): energy and its derivatives at dipoles the
@@ -2048,9 +2042,7 @@ struct Engine : EngineBase {
       HIP_TRY(hipMemcpyAsync(dU_, field.p, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToDevice, stream));
     }
     stage_finish(dpos_ ? gbuf : nullptr, reinterpret_cast<T*>(dQl_), E_RECIP, E);
-    warm_regime = false;
-    scf_last = -1.0;
-    scf_nobs[0] = scf_nobs[1] = 0;
+    scf.forget();
   }
 
   void local_frames(const void* pos, const double* box, void* out) override {
@@ -2151,8 +2143,11 @@ struct Engine : EngineBase {
     fft_inverse(spec_p, mesh_p);
     { TIMED("comm_ghost"); c_shift(mesh_p, mesh_p + (size_t)nx * plane, (int64_t)(kGhost * plane), real_dtype(), 0, ADMP_TAG_GHOST); }
   }
-  void pme_box_grad_slab(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
-                         const double* mS, const double* pS, const void* U_, double* E, double* dbox) {
+  void pme_box_grad(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
+                    const double* mS, const double* pS, const void* U_, double* E, double* dbox) override {
+    ARG_CHECK(pos_ && box && Ql_ && E && dbox, "null argument");
+    if (lpol) ARG_CHECK(U_, "polarizable handle needs the induced dipoles");
+    const bool slab = snranks > 1;
     const int na = top.na;
     grad.need(3 * (size_t)na * sizeof(T));
     T* gbuf = grad.as<T>();
@@ -2163,60 +2158,27 @@ struct Engine : EngineBase {
     upload_binv(inv);
     double* acc = vir_begin();
     stage_pair_full(gbuf);
-    launch_pair_virial<T>(stream, na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW, pair_rows(), ev.n_home);
-    stage_spread(mesh.as<T>());
+    launch_pair_virial<T>(stream, na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW,
+                          slab ? pair_rows() : nullptr, ev.n_home);
+    if (slab) stage_spread(mesh.as<T>());
+    else { vs_n = na; vs_sites = sites.as<Site<T>>(); vs_g = ev.g; }
     if (!slot_clean[E_RECIP]) HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
     slot_clean[E_RECIP] = false;
-    convolve_slab_virial(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP, 1, vol, acc);
+    if (slab) convolve_slab_virial(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP, 1, vol, acc);
+    else recip_pass_virial(E_RECIP, 1, vol, acc);
+    // (one rank: ev.home is null and ev.n_home the atom count)
     stage_gather(mesh.as<T>(), gbuf);
     launch_gather_virial<T>(stream, ev.n_home, sites.as<Site<T>>(), lpol, ev.g, mesh.as<T>(), acc + V_XW, acc + V_Y, ev.home);
     if (lmax > 0)
       launch_frame_virial<T>(stream, top, ev.pos, ev.bx, sites.as<Site<T>>(), lpol, (T)kappa, pot.as<T>(), acc + V_XW, ev.home,
                              ev.n_home);
     // (the frame sums need the TOTAL potential of the home sites: pot holds pair + reciprocal space, the self term is added
-    // by the kernel itself, as on one rank)
-    stage_finish(nullptr, nullptr, E_RECIP, E);
-    { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
-    vir_assemble(inv, E[1], dbox);
-    warm_regime = false;
-    scf_last = -1.0;
-    scf_nobs[0] = scf_nobs[1] = 0;
-  }
-
-  void pme_box_grad(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
-                    const double* mS, const double* pS, const void* U_, double* E, double* dbox) override {
-    ARG_CHECK(pos_ && box && Ql_ && E && dbox, "null argument");
-    if (snranks > 1) {
-      if (lpol) ARG_CHECK(U_, "polarizable handle needs the induced dipoles");
-      pme_box_grad_slab(pos_, box, Ql_, pol_, thole_, ns, mS, pS, U_, E, dbox);
-      return;
-    }
-    if (lpol) ARG_CHECK(U_, "polarizable handle needs the induced dipoles");
-    const int na = top.na;
-    grad.need(3 * (size_t)na * sizeof(T));
-    T* gbuf = grad.as<T>();
-    mono_ok = true;
-    stage_begin(pos_, box, Ql_, pol_, thole_, ns, mS, pS, const_cast<void*>(U_));
-    double inv[9], vol;
-    make_box(box, inv, &vol);
-    upload_binv(inv);
-    double* acc = vir_begin();
-    stage_pair_full(gbuf);
-    launch_pair_virial<T>(stream, na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, acc + V_XW);
-    vs_n = na; vs_sites = sites.as<Site<T>>(); vs_g = ev.g;
-    if (!slot_clean[E_RECIP]) HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
-    slot_clean[E_RECIP] = false;
-    recip_pass_virial(E_RECIP, 1, vol, acc);
-    stage_gather(mesh.as<T>(), gbuf);
-    launch_gather_virial<T>(stream, na, sites.as<Site<T>>(), lpol, ev.g, mesh.as<T>(), acc + V_XW, acc + V_Y);
-    if (lmax > 0)
-      launch_frame_virial<T>(stream, top, ev.pos, ev.bx, sites.as<Site<T>>(), lpol, (T)kappa, pot.as<T>(), acc + V_XW);
+    // by the kernel itself)
     stage_finish(nullptr, nullptr, E_RECIP, E);
     vs_sites = nullptr;
+    if (slab) { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     vir_assemble(inv, E[1], dbox);
-    warm_regime = false;
-    scf_last = -1.0;
-    scf_nobs[0] = scf_nobs[1] = 0;
+    scf.forget();
   }
 
   // dispersion PME box gradient on a slab rank (round 4): the pair sums over its home rows, the channels spread / gathered on
@@ -2437,7 +2399,7 @@ struct Engine : EngineBase {
     // margin -- half the list cutoff (far more than half a skin) plus 4 planes for the pair potentials' slab rule -- are built:
     // the search then costs the rank its share of the box, not the box.  ADMP_SLAB_ROWS=0: every row on every rank.
     RowFilter rf;
-    static const bool rows_on = [] { const char* e = getenv("ADMP_SLAB_ROWS"); return !(e && atoi(e) == 0); }();
+    static const bool rows_on = env_flag("ADMP_SLAB_ROWS", true);
     if (rows_on && snranks > 1 && have_ewald && have_comm) {
       update_slab();
       const int mp = (int)std::ceil(0.5 * rc / (heights[0] / K[0])) + 4;
@@ -2533,6 +2495,9 @@ struct Engine : EngineBase {
     for (int t = 0; t < nt; ++t)
       for (int c = 0; c < 3; ++c) disp_ctab[t][c] = ctab[3 * t + c];
   }
+  // ADMP_DISP_TYPES=0 / ADMP_DISP_BATCH=0: no typed meshes / the per-channel loop (A/B, tests)
+  static bool disp_types_on() { static const bool on = env_flag("ADMP_DISP_TYPES", true); return on; }
+  static bool disp_batch_on() { static const bool on = env_flag("ADMP_DISP_BATCH", true); return on; }
   // dispersion PME (admp/disp_pme.py:80-123): real-space pairs + one scalar reciprocal pass per power
   void disp(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
             void* dpos_, int on_device) override {
@@ -2571,10 +2536,8 @@ struct Engine : EngineBase {
       const size_t nreal = nreal_local();
       mesh.need(nch * nreal * sizeof(T));
       ensure_bins(std::max(sr.n, 1));
-      static const bool typed_on = [] { const char* e = getenv("ADMP_DISP_TYPES"); return !(e && atoi(e) == 0); }();
-      static const bool batch_on_t = [] { const char* e = getenv("ADMP_DISP_BATCH"); return !(e && atoi(e) == 0); }();
       // (more types than powers would mean more transforms than the per-power form: pmax 6 with two types keeps its one mesh)
-      const bool typed = typed_on && batch_on_t && snranks == 1 && use_fx && sizeof(T) == 4 && disp_nt >= 1 && disp_nt <= nch &&
+      const bool typed = disp_types_on() && disp_batch_on() && snranks == 1 && use_fx && sizeof(T) == 4 && disp_nt >= 1 && disp_nt <= nch &&
                          disp_types;
       if (typed) {
         // Typed meshes (disp_kernels.hip): nt type meshes through the transforms, combined per k in the x pass
@@ -2623,8 +2586,7 @@ struct Engine : EngineBase {
       // and ONE batched c2r; then the channels of every mesh point are laid side by side (one streaming pass) and ONE gather
       // fetches them with a single load per stencil point -- the gather is bound by its load instructions (36 per lane and
       // mesh), not by the bytes they return.  ADMP_DISP_BATCH=0: the per-channel loop (A/B, tests).
-      static const bool batch_on = [] { const char* e = getenv("ADMP_DISP_BATCH"); return !(e && atoi(e) == 0); }();
-      if (batch_on && snranks == 1 && use_fx && nch >= 2) {
+      if (disp_batch_on() && snranks == 1 && use_fx && nch >= 2) {
         const size_t nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
         spec.need(nch * nspec * sizeof(T));
         mesh2.need(nch * nreal * sizeof(T));
@@ -2658,8 +2620,7 @@ struct Engine : EngineBase {
     for (int k = 0; k < 9; ++k) gj.Aop[k] = g.Jac[k];
     // Typed meshes on a direct-DFT mesh (small systems; see admp_disp_set_types): the types take the place of the powers in the
     // batch -- one-hot weights through the same site / spread / gather kernels, the x pass combines (dft_kernels.hip k_dft_x_mix)
-    static const bool typed_small_on = [] { const char* e = getenv("ADMP_DISP_TYPES"); return !(e && atoi(e) == 0); }();
-    if (typed_small_on && disp_nt >= 1 && disp_nt < nch && disp_types && use_dft && !use_pfa && snranks == 1 &&
+    if (disp_types_on() && disp_nt >= 1 && disp_nt < nch && disp_types && use_dft && !use_pfa && snranks == 1 &&
         !spread_uses_bricks(na, g)) {
       const int nt = disp_nt;
       MixTab mix;

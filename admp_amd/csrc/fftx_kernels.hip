@@ -332,7 +332,7 @@ void launch_fftx_mix(hipStream_t st, const int K[3], const T* tw, T* spec, const
   while ((1 << logN) < N) ++logN;
   const int ntp = mix.nt <= 1 ? 1 : (mix.nt == 2 ? 2 : 4);
   int NC = (int)(128 / (2 * sizeof(T)));                 // one 128-B line of columns per type ...
-  static const int lds_kb = [] { const char* e = getenv("ADMP_MIX_LDS_KB"); return e ? atoi(e) : 34; }();
+  static const int lds_kb = env_int("ADMP_MIX_LDS_KB", 34);
   while (NC > 1 && sizeof(Cx<T>) * ((size_t)N / 2 + (size_t)N * NC * ntp) > (size_t)lds_kb * 1024) NC >>= 1;     // ... while the tile fits
   const size_t sh = sizeof(Cx<T>) * ((size_t)N / 2 + (size_t)N * NC * ntp);
   const int ntile = (Kh + NC - 1) / NC;

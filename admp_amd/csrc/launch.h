@@ -6,6 +6,7 @@
 
 #include <initializer_list>
 
+#include "env.h"
 #include "frame_math.h"
 #include "pme_math.h"
 #include "spline_math.h"

@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void k_row_order(int na, const int* __restrict
 void launch_row_order(hipStream_t st, int na, const int* rowptr, int* order, const int* cls) {
   // window = the rows one workgroup of the pair kernel owns (256 lanes / lanes per row): measured at 1M atoms
   // 0.446 ms (window 128 = one workgroup) vs 0.458-0.474 (64, 256, 512, 1024) vs 0.495 unsorted
-  static const int Wenv = [] { const char* e = getenv("ADMP_ROW_WINDOW"); return e ? atoi(e) : 0; }();
+  static const int Wenv = env_int("ADMP_ROW_WINDOW", 0);
   int W = 256 / pair_lanes_per_row(na);
   if (W < 64) W = 64;
   if (Wenv >= 64 && Wenv <= kRowWindow) W = Wenv;

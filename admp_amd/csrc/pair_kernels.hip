@@ -704,13 +704,12 @@ void launch_scalar_pair_virial(hipStream_t st, int tt, int na, const NbrTable& n
 // folding; many lanes = enough wavefronts to fill the chip when there are few rows.  Measured (f32, polarizable):
 // 1M rows LPR 1/2/4/8 -> 0.749/0.493/0.502/0.534 ms; 98k rows 2/4/8 -> 0.068/0.064/0.065 ms; 3k rows 4/8/16/32 ->
 // 38/23/18/24 us.
+static int lpr_switch(const char* name) {      // a forced width: 1 .. 32 lanes, a power of two; anything else: -1 (not forced)
+  const int x = env_int(name, -1);
+  return (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32) ? x : -1;
+}
 int pair_lanes_per_row(int n_rows) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char* s = getenv("ADMP_PAIR_LPR");
-    int x = s ? atoi(s) : -1;
-    forced = (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32) ? x : -1;
-  }
+  static const int forced = lpr_switch("ADMP_PAIR_LPR");
   if (forced > 0) return forced;
   // round 2, rows parted by site class (water: a third of the rows and partners carry higher moments), pipelined loops:
   // 1M rows LPR 2/4/8 -> 0.325/0.303/0.422 ms, 98k rows 0.044/0.041/0.052 ms
@@ -718,11 +717,7 @@ int pair_lanes_per_row(int n_rows) {
 }
 // the field kernels (k_pair_field, k_pair_field_ind): env ADMP_FIELD_LPR overrides
 static int field_lanes_per_row(int n_rows, bool ind) {
-  static const int forced = [] {
-    const char* s = getenv("ADMP_FIELD_LPR");
-    const int x = s ? atoi(s) : -1;
-    return (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32) ? x : -1;
-  }();
+  static const int forced = lpr_switch("ADMP_FIELD_LPR");
   if (forced > 0) return forced;
   // light arithmetic per partner, bound by the partner fetches: more lanes per row = more fetches in flight.  350k rows (the
   // polarizable sites of 1M atoms) LPR 2/4/8/16 -> 0.110/0.093/0.083/0.091 ms (k_pair_field), 0.034/0.030/0.033/0.041 ms
@@ -732,11 +727,7 @@ static int field_lanes_per_row(int n_rows, bool ind) {
 
 // the scalar pair kernels (dispersion, Tang-Toennies; k_pair_scalar): env ADMP_SCALAR_LPR / ADMP_TT_LPR override
 static int scalar_lanes_per_row(int n_rows, bool tt, double avg_row) {
-  static const int forced[2] = {
-      [] { const char* s = getenv("ADMP_SCALAR_LPR"); const int x = s ? atoi(s) : -1;
-           return (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32) ? x : -1; }(),
-      [] { const char* s = getenv("ADMP_TT_LPR"); const int x = s ? atoi(s) : -1;
-           return (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32) ? x : -1; }()};
+  static const int forced[2] = {lpr_switch("ADMP_SCALAR_LPR"), lpr_switch("ADMP_TT_LPR")};
   if (forced[tt ? 1 : 0] > 0) return forced[tt ? 1 : 0];
   // round 4, packed 32-byte partner rows and the two-ahead prefetch: few lanes per row win as soon as the rows fill the chip
   // (a lane walks ~14 partners with its fetches in flight; more lanes only add row_reduce steps and idle tail lanes).
@@ -758,14 +749,12 @@ static int scalar_lanes_per_row(int n_rows, bool tt, double avg_row) {
 //   f64: 1 (the 256-register cap costs 184 B/lane of scratch: S1 30 us vs 20 us unconstrained)
 template <class T>
 static int pair_min_waves() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("ADMP_PAIR_MINW");
-    v = s ? atoi(s) : (sizeof(T) == 4 ? 2 : 1);
-  }
+  static const int v = env_int("ADMP_PAIR_MINW", sizeof(T) == 4 ? 2 : 1);
   return v;
 }
 
+// ADMP_PAIR_MONO=0: no charge-only pair forms
+static bool pair_mono_off() { static const bool off = !env_flag("ADMP_PAIR_MONO", true); return off; }
 static inline unsigned grid_for(int na, int lpr) { return (unsigned)(((long)na * lpr + kPairBlock - 1) / kPairBlock); }
 static inline unsigned grid_full(int na, int lpr) { return (unsigned)(((long)na * lpr + kFullBlock - 1) / kFullBlock); }
 
@@ -786,8 +775,7 @@ void launch_pair_full(hipStream_t st, int na, const NbrTable& nb, const Site<T>*
   if (na <= 0) return;
   const int lpr = pair_lanes_per_row(na);
   const int minw = pair_min_waves<T>();
-  static const bool mono_off = [] { const char* e = getenv("ADMP_PAIR_MONO"); return e && atoi(e) == 0; }();
-  if (mono_off || !cls_flags || !rq) use_mono = 0;
+  if (pair_mono_off() || !cls_flags || !rq) use_mono = 0;
 #define FULL(LP, L, MW, CUT)                                                                                           \
   k_pair_full<T, LP, L, MW, CUT><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                    \
       na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L),      \
@@ -806,8 +794,7 @@ template <class T>
 void launch_pair_field(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
                        const ScaleTab<T>& tab, T kappa, T* fld, const int* rows, const int* n_dev, const int* cls_flags,
                        const RQ4<T>* rq, const T* tholes) {
-  static const bool mono_off = [] { const char* e = getenv("ADMP_PAIR_MONO"); return e && atoi(e) == 0; }();
-  if (mono_off || !rq) cls_flags = nullptr;
+  if (pair_mono_off() || !rq) cls_flags = nullptr;
   if (na <= 0) return;
   const int lpr = field_lanes_per_row(na, false);
 #define FIELD(L, CUT)                                                                                                  \
@@ -825,8 +812,7 @@ template <class T>
 bool field_rider_full(FieldRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
                       const ScaleTab<T>& tab, T kappa, T* fld, const int* rows, const int* n_dev, const int* cls_flags,
                       const RQ4<T>* rq, const T* tholes) {
-  static const bool mono_off = [] { const char* e = getenv("ADMP_PAIR_MONO"); return e && atoi(e) == 0; }();
-  if (mono_off || !rq) cls_flags = nullptr;
+  if (pair_mono_off() || !rq) cls_flags = nullptr;
   if (na <= 0 || field_lanes_per_row(na, false) != kRiderLpr) return false;
   r.kind = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nb.rowend; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
   r.kappa = kappa; r.fld = fld; r.rows = rows; r.nblocks = grid_for(na, kRiderLpr); r.grid = xcd_grid(r.nblocks);

@@ -147,7 +147,7 @@ static size_t pfa_tile_bytes(const PfaAxis& a, int NC, size_t w) {
 }
 // columns per block: as many as fit the budget, at most 16 (64-B segments of f32 complex at 8)
 static size_t pfa_lds_budget() {
-  static const size_t b = [] { const char* e = getenv("ADMP_PFA_LDS_KB"); return (size_t)(e ? atoi(e) : 60) * 1024; }();
+  static const size_t b = (size_t)env_int("ADMP_PFA_LDS_KB", 60) * 1024;
   return b;
 }
 static int pfa_cols(const PfaAxis& a, size_t w) {
@@ -271,7 +271,7 @@ __device__ __forceinline__ void pfa_stage_a_mfma(const PfaAxis& a, const Cx<T>* 
   }
 }
 static bool pfa_use_mfma(const PfaAxis& a, int NC) {
-  static const bool off = [] { const char* e = getenv("ADMP_PFA_MFMA"); return e && atoi(e) == 0; }();
+  static const bool off = !env_flag("ADMP_PFA_MFMA", true);
   return !off && NC == 8 && (a.N2 & 1) && (a.N2 - 1) / 2 <= 128;
 }
 template <class T, int SIGN>
@@ -614,7 +614,7 @@ bool pfa_split(int N, PfaAxis* out) {
   while (m % p == 0) { N2 *= p; m /= p; }
   PfaAxis a;
   a.N = N;
-  static const int plain_max = [] { const char* e = getenv("ADMP_PFA_MIN"); return e ? atoi(e) : 160; }();   // tests: 0 splits whatever it can
+  static const int plain_max = env_int("ADMP_PFA_MIN", 160);   // tests: 0 splits whatever it can
   if (N <= plain_max || m == 1) { a.N1 = 1; a.N2 = N; }
   else { a.N1 = m; a.N2 = N2; }
   if (a.N2 > 160 || a.N1 > 32 || a.N2 < 2) return false;

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/admp_hip.h"
+#include "env.h"
 #include "rccl_comm.h"
 
 namespace {
@@ -204,8 +205,7 @@ int admp_rccl_create(admp_rccl** out, int device, const void* id128, int rank, i
   c->device = device; c->rank = rank; c->nranks = nranks;
   const ncclResult_t r = g_api.CommInitRank(&c->comm, nranks, id, rank);      // blocks until every rank has joined
   if (r != ncclSuccess) { fail("ncclCommInitRank", r); delete c; return ADMP_E_COMM; }
-  const char* e = getenv("ADMP_RCCL_SELF_SENDRECV");
-  c->self_sendrecv = e && atoi(e) != 0;
+  c->self_sendrecv = env_flag("ADMP_RCCL_SELF_SENDRECV", false);
   *out = c;
   return ADMP_OK;
 }

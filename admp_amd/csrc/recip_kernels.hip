@@ -1131,7 +1131,7 @@ int launch_spread(hipStream_t st, int na, const Site<T>* sites, int lpol, const 
   if (!spread_wants_bricks(na, bg.ncell) || one_brick_axis) {
     // measured (f32, reference K rule): 12 288 atoms scan 0.052 / bricks 0.066 / global atomics 0.130 ms; 18 000 atoms
     // 0.070 / 0.083 / 0.189; 30 000 atoms 0.144 / 0.109 -- the scan kernel serves everything below the brick threshold
-    static const int scan_max = [] { const char* e = getenv("ADMP_SPREAD_SCAN_MAX"); return e ? atoi(e) : 20000; }();
+    static const int scan_max = env_int("ADMP_SPREAD_SCAN_MAX", 20000);
     if (na <= scan_max || one_brick_axis) {
       k_spread_scan<T><<<dim3(bg.ncell, nb), 256, 0, st>>>(na, sites, lpol, g, bg, mesh, list, bases);
       return 0;
@@ -1193,13 +1193,8 @@ bool spread_wants_bricks(int na, int ncell) {
   return na >= m || (m > 0 && na >= 4096 && (long)na >= 24l * ncell);
 }
 int spread_brick_min_atoms() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ADMP_SPREAD_BRICK_MIN");
-    v = e ? atoi(e) : 20000;
-    if (v < 0) v = 0;
-  }
-  return v;
+  static const int v = env_int("ADMP_SPREAD_BRICK_MIN", 20000);
+  return v < 0 ? 0 : v;
 }
 
 // bytes of hipcub scan scratch for a mesh (used by the engine to size BinScratch)

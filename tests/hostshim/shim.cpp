@@ -11,6 +11,7 @@
 #include "../../admp_amd/csrc/spline_math.h"
 #include "../../admp_amd/csrc/disp_math.h"
 #include "../../admp_amd/csrc/dft_math.h"
+#include "../../admp_amd/csrc/scf_policy.h"
 
 using namespace admp;
 
@@ -354,4 +355,19 @@ void shim_dft_line(int prec, int kq, int kind, int N, int sign, const double* in
   }
 }
 int shim_largest_prime_factor(int n) { return largest_prime_factor(n); }
+// the SCF policy of Engine::pme (scf_policy.h): one history per handle; plan -> form_nhat = {form, nhat}, *pred
+void* shim_scf_create() { return new ScfHistory(); }
+void shim_scf_destroy(void* h) { delete static_cast<ScfHistory*>(h); }
+void shim_scf_plan(const void* h, double thresh, int na, int max_cycle, int can_chain, int spec_mode, int chain_max,
+                   int* form_nhat, double* pred) {
+  ScfSwitches sw;
+  sw.spec_mode = spec_mode;
+  sw.chain_max = chain_max;
+  const ScfPlan p = static_cast<const ScfHistory*>(h)->plan(thresh, na, max_cycle, can_chain != 0, sw);
+  form_nhat[0] = (int)p.form;
+  form_nhat[1] = p.nhat;
+  *pred = p.pred;
+}
+void shim_scf_observe(void* h, double f_first, double f_final, int cyc) { static_cast<ScfHistory*>(h)->observe(f_first, f_final, cyc); }
+void shim_scf_forget(void* h) { static_cast<ScfHistory*>(h)->forget(); }
 }

@@ -2,6 +2,7 @@
 (no compute calls without a GPU), and the host logic around it (covalent map -> CSR, Ewald
 parameters, pair-list builder, scale-table wrap, synthetic box generator)."""
 import ctypes
+import math
 import os
 import re
 import sys
@@ -292,3 +293,114 @@ def test_force_field_front_end_without_gpu(tmp_path):
     class Q:                                   # an OpenMM-style quantity
         _value, unit = 0.4, 'nanometer'
     assert abs(api._cutoff_angstrom(Q()) - 4.0) < 1e-12
+
+
+class _ScfRules:
+    """The rules by which Engine::pme picks the form of a call's SCF from the residual history of the calls before it,
+    written out independently of admp_amd/csrc/scf_policy.h (the same IEEE operations in the same order)."""
+    E_CHAIN = 6
+
+    def __init__(self):
+        self.warm, self.last, self.growth = False, -1.0, [[0.0, 0.0], [0.0, 0.0]]
+        self.nobs, self.state, self.contract = [0, 0], 0, -1.0
+
+    def plan(self, thresh, na, max_cycle, can_chain, spec_mode, chain_max):
+        s = self.state
+        have_pred = self.last >= 0.0 and self.nobs[s] >= 2
+        g_hi, g_lo = max(self.growth[s]), min(self.growth[s])
+        spec_infl = 1.0 if na <= 200000 else 1.5
+        if spec_mode >= 0:
+            speculate = spec_mode != 0
+        elif have_pred:
+            speculate = self.last + spec_infl * g_hi < thresh
+        else:
+            speculate = self.last < 0.0 and self.warm
+        pred = self.last + 0.5 * (g_hi + g_lo) if have_pred else -1.0
+        nhat = 0
+        if have_pred and self.last + g_lo >= 1.1 * thresh and 0.0 < self.contract < 0.95 and thresh > 0.0:
+            r = pred
+            while nhat <= self.E_CHAIN and r >= thresh:
+                r *= self.contract
+                nhat += 1
+        chain = (spec_mode < 0 and not speculate and na <= chain_max and 1 <= nhat <= self.E_CHAIN
+                 and nhat + 2 <= max_cycle and can_chain)
+        return (2 if chain else (1 if speculate else 0)), nhat, pred
+
+    def observe(self, f_first, f_final, cyc):
+        self.warm = cyc == 0
+        if f_first < 0.0:
+            return
+        s = self.state
+        if self.last >= 0.0:
+            self.growth[s][1] = self.growth[s][0]
+            self.growth[s][0] = f_first - self.last
+            self.nobs[s] += 1
+        self.last = f_final
+        self.state = 1 if cyc > 0 else 0
+        if cyc >= 1 and f_first > 0.0 and 0.0 < f_final < f_first:
+            # (C's pow: python's ** may round differently in the last bit)
+            self.contract = math.pow(f_final / f_first, 1.0 / cyc)
+
+    def forget(self):
+        self.warm, self.last, self.nobs = False, -1.0, [0, 0]
+
+
+def test_scf_policy_follows_the_written_rules():
+    """ScfHistory (the host-only header the engine's SCF driver asks) against the rules above, call by call, over 300
+    seeded random histories: same form, same predicted step count, same predicted residual (bit for bit)."""
+    from tests import hostshim_util as H
+    lib = H.lib()
+    lib.shim_scf_create.restype = ctypes.c_void_p
+    c_d, c_i, c_p = ctypes.c_double, ctypes.c_int, ctypes.c_void_p
+    forms, nhat_max, n_calls = set(), 0, 0
+    for seed in range(300):
+        rng = np.random.default_rng(seed)
+        thresh = (1e-2, 1e-4, 10.0)[seed % 3]
+        max_cycle = (1, 3, 20)[(seed // 3) % 3]
+        spec_mode = (-1, -1, -1, 0, 1)[seed % 5]           # mostly unset: the history decides
+        chain_max = (200000, 200000, 0)[(seed // 5) % 3]
+        na = (3072, 98304, 200000, 200001, 1000000)[(seed // 2) % 5]
+        # a sequence in the manner of an MD run: the first residual of a call is near the last one of the call before
+        # plus a drift, each Jacobi step contracts it; now and then something unrelated
+        drift = float(rng.choice([0.0, 0.3, 3.0, 30.0])) * thresh
+        rate = float(rng.uniform(0.05, 0.99))
+        ref = _ScfRules()
+        h = c_p(lib.shim_scf_create())
+        try:
+            f_prev = 0.5 * thresh
+            for call in range(40):
+                can_chain = bool(rng.random() < 0.85)
+                out, pred = (c_i * 2)(), c_d()
+                lib.shim_scf_plan(h, c_d(thresh), c_i(na), c_i(max_cycle), c_i(can_chain), c_i(spec_mode), c_i(chain_max),
+                                  out, ctypes.byref(pred))
+                want = ref.plan(thresh, na, max_cycle, can_chain, spec_mode, chain_max)
+                assert (out[0], out[1]) == want[:2], (seed, call, tuple(out), want)
+                assert pred.value == want[2], (seed, call, pred.value, want[2])
+                forms.add(out[0])
+                nhat_max = max(nhat_max, out[1])
+                n_calls += 1
+                u = rng.random()
+                if u < 0.05:
+                    lib.shim_scf_forget(h)
+                    ref.forget()
+                    continue
+                if u < 0.10:                       # a call that made no check at all
+                    f_first, f_final, cyc = -1.0, -1.0, 0
+                elif u < 0.15:                     # unrelated residuals, zero included
+                    f_first = float(rng.choice([0.0, 1.0, 100.0])) * thresh
+                    f_final, cyc = f_first * float(rng.uniform(0.0, 1.5)), int(rng.integers(0, 4))
+                else:
+                    f_first = f_prev + drift * float(rng.uniform(0.8, 1.2))
+                    f_final, cyc = f_first, 0
+                    while f_final >= thresh and cyc < max_cycle - 1:
+                        f_final *= rate
+                        cyc += 1
+                    f_prev = f_final
+                lib.shim_scf_observe(h, c_d(f_first), c_d(f_final), c_i(cyc))
+                ref.observe(f_first, f_final, cyc)
+        finally:
+            lib.shim_scf_destroy(h)
+    # every branch of the policy was exercised (a test that never plans a chain would hide a dead one)
+    assert forms == {0, 1, 2}, forms
+    assert nhat_max >= 2, nhat_max
+    assert n_calls > 10000
