@@ -158,6 +158,31 @@ __global__ __launch_bounds__(kDftBlock) void k_dft_x_conv(XConvArgs<T> xa) {
   dft_x_conv_body<T, KQ, JS>(xa, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
+// ---- x lines as one real circulant product (dft_lines.h dft_x_circ_body), for G tables that are even along x
+template <class T, int KQ>
+__global__ __launch_bounds__(kDftBlock) void k_dft_x_circ(XConvArgs<T> xa) {
+  dft_x_circ_body<T, KQ>(xa, blockIdx.x, blockIdx.y);
+}
+// its table: ctab[d][ky][kz], d = 0 .. N/2, the first column of the circulant of every x line of the G table
+// gtab[kx][ky][kz] (dft_math.h circ_table_entry, double arithmetic), one thread per entry.  The threads of d = 0 check the
+// premise on their column (circ_column_even) and raise *uneven where it fails: the table is then not used.
+// (the N cosines every entry draws from are computed once per workgroup: evaluated per term they made the kernel 49 us at 97^3)
+template <class T>
+__global__ __launch_bounds__(256) void k_ctab(int N, long ncol, const T* __restrict__ gtab, T* __restrict__ ctab, int* uneven) {
+  double* cw = reinterpret_cast<double*>(dft_smem);      // [N]
+  for (int m = threadIdx.x; m < N; m += 256) cw[m] = circ_cos(m, N);
+  __syncthreads();
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= ncol * (N / 2 + 1)) return;
+  const int d = (int)(t / ncol);
+  const T* __restrict__ G = gtab + (t - (long)d * ncol);
+  const double c = circ_table_entry(N, d, (double)G[0], [=](int k) { return (double)G[k * ncol] + (double)G[(N - k) * ncol]; },
+                                    (N & 1) ? 0.0 : (double)G[(N / 2) * ncol], [=](int m) { return cw[m]; });
+  ctab[t] = (T)c;
+  if (d == 0 && !circ_column_even(N, [=](int k) { return (double)G[k * ncol]; }, sizeof(T) == 4 ? 0x1p-24 : 0x1p-53))
+    atomicOr(uneven, 1);
+}
+
 // ---- x lines of the TYPED dispersion meshes (round 4; see disp_kernels.hip): the workgroup's NC "columns" are NC / NTP
 // physical columns of each of NTP (padded: 1, 2 or 4) type spectra, column t * NCt + c.  The transforms treat them as NC
 // independent columns; between them the types are combined per (frequency, physical column):
@@ -688,6 +713,23 @@ void launch_dft_x_conv(hipStream_t st, const int K[3], const T* tw, T* spec, con
                         reinterpret_cast<const Cx<T>*>(tw), energies, slot, spec_stride / 2};
   KQ_SWITCH((k_dft_x_conv<T, KQ, JS><<<grid, kDftBlock, sh, st>>>(xa)))
 }
+// the circulant form of the x pass of ONE mesh (ctab from launch_ctab) and its table
+template <class T>
+void launch_dft_x_circ(hipStream_t st, const int K[3], T* spec, const T* ctab, double* energies, int slot) {
+  const int N = K[0], Kh = K[2] / 2 + 1, TK = dft_tasks(N, dft_kq());
+  const int NC = dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0);
+  const size_t sh = dft_x_circ_col_bytes<T>(N) * (size_t)NC;
+  const dim3 grid((Kh + NC - 1) / NC, K[1], 1);
+  XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), DftTabs<T>(), nullptr,
+                  energies, slot, 0};
+  xa.ctab = ctab;
+  k_dft_x_circ<T, 2><<<grid, kDftBlock, sh, st>>>(xa);
+}
+template <class T>
+void launch_ctab(hipStream_t st, const int K[3], const T* gtab, T* ctab, int* uneven) {
+  const long ncol = (long)K[1] * (K[2] / 2 + 1), n = ncol * (K[0] / 2 + 1);
+  k_ctab<T><<<(unsigned)((n + 255) / 256), 256, sizeof(double) * (size_t)K[0], st>>>(K[0], ncol, gtab, ctab, uneven);
+}
 // x pass of the typed dispersion meshes: spec holds mix.nt type spectra, spec_stride (reals) apart
 template <class T>
 void launch_dft_x_mix(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, const MixTab& mix,
@@ -757,6 +799,8 @@ bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec
   template bool launch_dft_z<T>(hipStream_t, const int*, const T*, T*, T*, int, int, long, long, T*); \
   template void launch_dft_y<T>(hipStream_t, const int*, const T*, T*, int, int, long);           \
   template void launch_dft_x_conv<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int, int, long); \
+  template void launch_dft_x_circ<T>(hipStream_t, const int*, T*, const T*, double*, int);       \
+  template void launch_ctab<T>(hipStream_t, const int*, const T*, T*, int*);                      \
   template void launch_dft_x_mix<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, const MixTab&, long, double*, int);
 INST(float)
 INST(double)

@@ -110,6 +110,7 @@ struct XConvArgs {
   double* energies;
   int slot;
   long spec_stride;
+  const T* ctab = nullptr;      // circulant form (dft_x_circ_body): first columns [N/2+1][K2][K3/2+1] of the slot-0 G table
 };
 template <class T, int KQ, int JS>
 __device__ __forceinline__ void dft_x_conv_body(const XConvArgs<T>& xa, int bx, int by, int bz) {
@@ -222,6 +223,65 @@ __device__ __forceinline__ void dft_x_conv_body(const XConvArgs<T>& xa, int bx, 
   }
   e = block_reduce_sum<kDftBlock>(e);
   if (threadIdx.x == 0) atomicAdd(&energies[slot], e);
+}
+
+// ---- x lines as one real circulant product (dft_math.h circ_pair_outputs): same tile, same in-place store and the same
+// energy word as dft_x_conv_body, for G tables that are even along x (xa.ctab: built and checked by k_ctab, dft_kernels.hip).
+// One loop over the pair positions, one barrier; LDS: the pair sums and the tile's extended table [circ_ext_len][NC].
+// The energy sum is skipped for slot E_SCRATCH (convolutions whose energy nobody reads: the SCF increments).
+template <class T>
+inline size_t dft_x_circ_col_bytes(int N) {
+  return sizeof(PairCx<T>) * (size_t)((N - 1) / 2) + 2 * sizeof(Cx<T>) + sizeof(T) * (size_t)circ_ext_len(N);
+}
+template <class T, int KQ>
+__device__ __forceinline__ void dft_x_circ_body(const XConvArgs<T>& xa, int bx, int by) {
+  const bool ENERGY = xa.slot != E_SCRATCH;      // (workgroup-uniform)
+  const int N = xa.N, ncols = xa.ncols, NC = xa.NC, TK = xa.TK, K3 = xa.K3;
+  const long jstride = xa.jstride;
+  Cx<T>* __restrict__ spec = xa.spec;
+  const T* __restrict__ ctab = xa.ctab;
+  const int H = (N - 1) / 2, Kh = N / 2 + 1;
+  PairCx<T>* ab = reinterpret_cast<PairCx<T>*>(dft_smem);   // [H][NC]
+  Cx<T>* x0 = reinterpret_cast<Cx<T>*>(ab + H * NC);          // [NC]
+  Cx<T>* xn = x0 + NC;                                        // [NC]
+  T* cext = reinterpret_cast<T*>(xn + NC);                    // [circ_ext_len(N)][NC], row 0 = extended position -(N/2)
+  const int col0 = bx * NC;
+  const int nca = min(NC, ncols - col0);
+  const long base = (long)by * xa.fixstride + col0;
+  for (int t = threadIdx.x; t < Kh * NC; t += kDftBlock) {      // c[d] sits at the extended positions d, -d and N - d
+    const int d = t / NC, cc = t - d * NC;
+    const T v = cc < nca ? ctab[base + (long)d * jstride + cc] : T(0);
+    cext[(N / 2 + d) * NC + cc] = v;
+    cext[(N / 2 - d) * NC + cc] = v;
+    if (N - d <= N / 2 + H) cext[(N / 2 + N - d) * NC + cc] = v;
+  }
+  load_pairs<T>(N, NC, nca, spec, base, jstride, ab, x0, xn);
+  __syncthreads();
+  const int g = (int)threadIdx.x / NC, c = (int)threadIdx.x - g * NC;
+  double e = 0.0;
+  if (g < TK && c < nca) {
+    int i[KQ];
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) i[q] = (g + q * TK < Kh) ? g + q * TK : 0;
+    Cx<T> P[KQ], M[KQ];
+    circ_pair_outputs<T, KQ>(N, i, NC, cext + (N / 2) * NC + c, NC, ab + c, x0[c], xn[c], P, M);
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+      const int iq = g + q * TK;
+      if (iq < Kh) {
+        const bool single = iq == 0 || 2 * iq == N;
+        if (ENERGY) e += circ_pair_energy<T>(N, iq, P[q], M[q], ab[(single ? 0 : iq - 1) * NC + c], x0[c], xn[c]);
+        spec[base + (long)iq * jstride + c] = Cx<T>{T(0.5) * (P[q].re + M[q].re), T(0.5) * (P[q].im + M[q].im)};
+        if (!single) spec[base + (long)(N - iq) * jstride + c] = Cx<T>{T(0.5) * (P[q].re - M[q].re), T(0.5) * (P[q].im - M[q].im)};
+      }
+    }
+    const int kz = col0 + c;
+    if (ENERGY && (kz == 0 || ((K3 & 1) == 0 && kz == K3 / 2))) e *= 0.5;
+  }
+  if (ENERGY) {
+    e = block_reduce_sum<kDftBlock>(e);
+    if (threadIdx.x == 0) atomicAdd(&xa.energies[xa.slot], e);
+  }
 }
 
 }  // namespace admp

@@ -246,6 +246,117 @@ ADMP_HD void irdft_pair_outputs(int N, const int* j, int stride, const Cx<T>* p,
   }
 }
 
+// ---- the x pass of the convolution as ONE real circulant product ---------------------------------------------------------
+// For one column (ky, kz) the x pass is out = F^-1 diag(G) F in (both unnormalised).  Where G(k) = G(N - k) along the line --
+// every orthorhombic cell, both k-point orders -- that is the circulant matrix with the real, even first column
+//     c[d] = sum_k G(k) e^(2 pi i k d / N) = G(0) + sum_{k=1..H} (G(k) + G(N-k)) cos(2 pi k d / N)   (+ (-1)^d G(N/2), N even)
+// and with the pair sums a_j = x_j + x_{N-j}, b_j = x_j - x_{N-j} the kernels stage anyway
+//     P_i = out_i + out_{N-i} = 2 c[i] x_0 + sum_j (c[i-j] + c[i+j]) a_j    (+ 2 c[i - N/2] x_{N/2}, N even)
+//     M_i = out_i - out_{N-i} =              sum_j (c[i-j] - c[i+j]) b_j
+// one loop over the H pair positions instead of a forward and an inverse transform, no twiddles, no spectrum S.  The energy
+// the pass sums in k space follows from Parseval: sum_k G |S_k|^2 = sum_x Re(conj(in_x) out_x), and for a pair of outputs
+// conj(x_i) out_i + conj(x_{N-i}) out_{N-i} = (conj(a_i) P_i + conj(b_i) M_i) / 2.
+// The column's table is passed EXTENDED so that the loop has no index arithmetic: ce[e * cstride] = c[e mod N], e running
+// from -(N/2) to N/2 + H (circ_ext_len entries, ce pointing at e = 0).
+
+// entry d of the first column in double; gs(k) = G(k) + G(N-k), k = 1..H
+ADMP_HD double circ_cos(int m, int N) {          // cos(2 pi m / N), 0 <= m < N, argument reduced to [0, pi/2]
+  if (2 * m > N) m = N - m;
+  const double pi = 3.141592653589793;
+  return 4 * m > N ? -cos(pi * (double)(N - 2 * m) / (double)N) : cos(pi * (double)(2 * m) / (double)N);
+}
+// cosm(m) = cos(2 pi m / N), 0 <= m < N: circ_cos, or a table of it
+template <class LoadGs, class CosM>
+ADMP_HD double circ_table_entry(int N, int d, double G0, LoadGs gs, double Gn, CosM cosm) {
+  const int H = (N - 1) / 2;
+  double c = G0;
+  int m = 0;
+  for (int k = 1; k <= H; ++k) {
+    m += d;
+    if (m >= N) m -= N;
+    c += gs(k) * cosm(m);
+  }
+  if ((N & 1) == 0) c += (d & 1) ? -Gn : Gn;
+  return c;
+}
+// The premise, checked per column on the STORED table (type T, unit roundoff ulp): G(k) and G(N-k) come out of the same
+// formula at mirrored integer frequencies, so in a cell where they are equal they differ by the rounding of that evaluation
+// in double (a product chain of ~20 operations and one exp: a few ulp of double, nothing in f32) plus half an ulp of T each
+// from the store.  kCircEvenUlps = 8 ulp of T of the column's largest |G| covers that; a triclinic cell misses it by many
+// orders (its mixed terms change G by O(1) relative amounts).
+constexpr double kCircEvenUlps = 8.0;
+template <class LoadG>
+ADMP_HD bool circ_column_even(int N, LoadG G, double ulp) {
+  const int H = (N - 1) / 2;
+  double gmax = fabs(G(0));
+  for (int k = 1; k < N; ++k) { const double g = fabs(G(k)); gmax = g > gmax ? g : gmax; }
+  bool ok = true;
+  for (int k = 1; k <= H; ++k) ok = ok && fabs(G(k) - G(N - k)) <= kCircEvenUlps * ulp * gmax;
+  return ok;
+}
+ADMP_HD int circ_ext_len(int N) { return N / 2 + N / 2 + (N - 1) / 2 + 1; }
+// index into c[0 .. N/2] of extended position e (-(N/2) <= e <= N/2 + H)
+ADMP_HD int circ_fold(int e, int N) {
+  if (e < 0) e = -e;
+  return 2 * e > N ? N - e : e;
+}
+
+// KQ pairs (P_i, M_i) of one line, i = i[0..KQ) in 0 .. N/2 (entries outside may be passed as 0 and ignored):
+// pair sums ab[(j-1) * stride], j = 1..H; x0 = x_0; xn = x_{N/2} (N even)
+template <class T>
+ADMP_HD void circ_step(const PairCx<T>& p, T c1, T c2, Cx<T>& P, Cx<T>& M) {
+  const T s = c1 + c2, d = c1 - c2;
+  P.re += s * p.are;
+  P.im += s * p.aim;
+  M.re += d * p.bre;
+  M.im += d * p.bim;
+}
+// steps unrolled together (their LDS reads are in flight at once).  Measured at 97^3 f64: 2 -> +1.1 us on the plain kernel;
+// 8 -> -0.5 us there, but the rider kernel (pair_kernels.hip k_xconv_pair) then needs 191 registers instead of the field
+// workgroups' 165, drops to two waves per SIMD and loses 3 us.
+constexpr int kCircUnroll = 4;
+template <class T, int KQ>
+ADMP_HD void circ_pair_outputs(int N, const int* i, int cstride, const T* ce, int stride, const PairCx<T>* ab, Cx<T> x0,
+                               Cx<T> xn, Cx<T>* P, Cx<T>* M) {
+  const int H = (N - 1) / 2;
+  const T* cm[KQ];
+  const T* cp[KQ];
+#pragma unroll
+  for (int q = 0; q < KQ; ++q) {
+    const T c0 = T(2) * ce[i[q] * cstride];
+    P[q] = Cx<T>{c0 * x0.re, c0 * x0.im};
+    M[q] = Cx<T>{T(0), T(0)};
+    if ((N & 1) == 0) {
+      const T cn = T(2) * ce[(i[q] - N / 2) * cstride];
+      P[q].re += cn * xn.re;
+      P[q].im += cn * xn.im;
+    }
+    cm[q] = ce + (i[q] - 1) * cstride;      // c[i - j] at j = 1, walking down
+    cp[q] = ce + (i[q] + 1) * cstride;      // c[i + j] at j = 1, walking up
+  }
+  int j = 0;
+  for (; j + kCircUnroll <= H; j += kCircUnroll) {
+#pragma unroll
+    for (int jj = 0; jj < kCircUnroll; ++jj) {
+      const PairCx<T> p = ab[(j + jj) * stride];
+#pragma unroll
+      for (int q = 0; q < KQ; ++q) circ_step(p, cm[q][-(j + jj) * cstride], cp[q][(j + jj) * cstride], P[q], M[q]);
+    }
+  }
+  for (; j < H; ++j) {
+    const PairCx<T> p = ab[j * stride];
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) circ_step(p, cm[q][-j * cstride], cp[q][j * cstride], P[q], M[q]);
+  }
+}
+// sum over the outputs i and N - i of Re(conj(in) out), in double: ai = the pair sums of position i (unused for i = 0, N/2)
+template <class T>
+ADMP_HD double circ_pair_energy(int N, int i, Cx<T> P, Cx<T> M, const PairCx<T>& ai, Cx<T> x0, Cx<T> xn) {
+  if (i == 0) return 0.5 * ((double)x0.re * P.re + (double)x0.im * P.im);
+  if (2 * i == N) return 0.5 * ((double)xn.re * P.re + (double)xn.im * P.im);
+  return 0.5 * ((double)ai.are * P.re + (double)ai.aim * P.im + (double)ai.bre * M.re + (double)ai.bim * M.im);
+}
+
 // largest prime factor (host): rocFFT has radix kernels for 2, 3, 5, 7, 11, 13 and falls back to Bluestein above
 inline int largest_prime_factor(int n) {
   int best = 1;

@@ -188,6 +188,8 @@ struct EngineBase {
   // [4] ... that needed more steps than enqueued (closing pass wasted), [5] ... that enqueued more steps than needed,
   // [6] increments that ran for nothing in those, [7] Jacobi steps in total
   int64_t scf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // x passes of the direct-DFT convolution of one mesh (admp_xpass_stats): [0] circulant form, [1] forward * G * inverse
+  int64_t xpass_stats[2] = {0, 0};
   const void* U_src = nullptr;  // admp_set_dipole_source: read-only initial dipoles of the NEXT polarizable evaluation
   const void* U_src_now = nullptr;   // ... taken over by that evaluation (Engine::pme), consumed by its site pass
   double cutoff = 0.0;          // admp_set_cutoff: listed pairs beyond it are skipped (0: every listed pair, as the reference)
@@ -594,6 +596,11 @@ struct Engine : EngineBase {
   DevBuf pfa_tw, pfa_fmap, pfa_ptab, gtab_nat;
   // validity of the cached G table
   struct TabKey { double box[9] = {0}, kappa = -1; int K[3] = {0, 0, 0}, Y0 = 0, ref = 0; bool pfa = false; } tabkey[4];
+  // circulant form of the x pass (dft_math.h): first columns of the G table of slot 0, rebuilt with it; xctab_ok: the table
+  // is even along x in every column (k_ctab's check, read back when the table is built)
+  DevBuf xctab, xctab_flag;
+  bool xctab_ok = false;
+  static bool xcirc_on() { static const bool on = env_flag("ADMP_DFT_XCIRC", true); return on; }
   static int tab_slot(int which) { return which == 1 ? 0 : (which == 6 ? 1 : (which == 8 ? 2 : 3)); }
   static_assert(kScfChainSteps == E_CHAIN, "one residual word per chained Jacobi step");
   ScfHistory scf;             // residual history of the polarizable calls of this handle: picks the form of the next one
@@ -605,7 +612,7 @@ struct Engine : EngineBase {
                       &s_thole, &s_U, &s_out, &s_dQ, &s_par, &mesh, &spec, &gtabs[0], &gtabs[1], &gtabs[2], &gtabs[3], &fft_work, &binv_d, &scan_scratch, &bin_cells,
                       &bin_sorted, &bin_scan, &home_list, &dft_tw, &bases_d, &vir_d, &act_d, &isites, &mesh2, &act_tmp,
                       &rq_d, &pfa_tw, &pfa_fmap, &pfa_ptab, &gtab_nat, &fx_tw, &bin_cells_ind, &bin_sorted_ind, &srow_d, &onehot_d, &tcount_d, &prune_rowptr, &prune_cnt, &prune_col,
-                      &cut_end, &cut_col, &cut_iend, &cut_icol})
+                      &cut_end, &cut_col, &cut_iend, &cut_icol, &xctab, &xctab_flag})
       b->release();
     free_topology();
     if (ind.end) (void)hipFree(ind.end);
@@ -1084,7 +1091,11 @@ struct Engine : EngineBase {
       }
       DftTabs<T> tabs;
       tabs.p[0] = gtab;
-      if (rider && rider->kind) { TIMED("dft_x_kspace"); launch_dft_x_conv_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *rider); }
+      // G table of slot 0 even along x (every orthorhombic cell): one circulant product per line instead of two transforms
+      const T* ct = xctab_ok && gtab == gtabs[0].template as<T>() ? xctab.template as<T>() : nullptr;
+      ++xpass_stats[ct ? 0 : 1];
+      if (rider && rider->kind) { TIMED("dft_x_kspace"); launch_dft_x_conv_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *rider, ct); }
+      else if (ct) { TIMED("dft_x_kspace"); launch_dft_x_circ<T>(stream, K, spec_p, ct, Ed, slot); }
       else { TIMED("dft_x_kspace"); launch_dft_x_conv<T>(stream, K, tw, spec_p, tabs, Ed, slot); }
       bool added;
       if (planes) { TIMED("dft_yz_inv"); added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum); }
@@ -1203,6 +1214,19 @@ struct Engine : EngineBase {
     std::memcpy(key.box, box, sizeof(key.box));
     key.kappa = kappa; key.K[0] = K[0]; key.K[1] = K[1]; key.K[2] = K[2]; key.Y0 = snranks > 1 ? Y0 : 0; key.ref = ref_korder;
     key.pfa = use_pfa;
+    if (slot == 0) {
+      xctab_ok = false;
+      if (use_dft && !use_pfa && snranks == 1 && xcirc_on()) {
+        xctab.need((size_t)(K[0] / 2 + 1) * K[1] * (K[2] / 2 + 1) * sizeof(T));
+        xctab_flag.need(sizeof(int));
+        HIP_TRY(hipMemsetAsync(xctab_flag.p, 0, sizeof(int), stream));
+        { TIMED("xcirc_table"); launch_ctab<T>(stream, K, gtab_cur, xctab.as<T>(), xctab_flag.as<int>()); }
+        int uneven = 1;
+        HIP_TRY(hipMemcpyAsync(&uneven, xctab_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        xctab_ok = uneven == 0;
+      }
+    }
   }
 
   ScaleTab<T> make_tab(int ns, const double* mS, const double* pS) {
@@ -3276,6 +3300,12 @@ int admp_scf_stats(admp_handle* h, int64_t* out8, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out8, "null");
     for (int k = 0; k < 8; ++k) { out8[k] = e.scf_stats[k]; if (reset) e.scf_stats[k] = 0; }
+  });
+}
+int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(out2, "null");
+    for (int k = 0; k < 2; ++k) { out2[k] = e.xpass_stats[k]; if (reset) e.xpass_stats[k] = 0; }
   });
 }
 int admp_slab_home(admp_handle* h, int32_t* home_out, int* n_home, int* n_import) {

@@ -224,6 +224,13 @@ void launch_dft_y(hipStream_t st, const int K[3], const T* tw, T* spec, int inve
 template <class T>
 void launch_dft_x_conv(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
                        int slot, int nb = 1, long spec_stride = 0);
+// the x pass of one mesh as a real circulant product per column (dft_math.h), for a G table that is even along x:
+// launch_ctab builds ctab [K1/2+1][K2][K3/2+1] from gtab and sets *uneven (device word, cleared by the caller) where a
+// column of gtab is not even -- ctab must then not be used
+template <class T>
+void launch_dft_x_circ(hipStream_t st, const int K[3], T* spec, const T* ctab, double* energies, int slot);
+template <class T>
+void launch_ctab(hipStream_t st, const int K[3], const T* gtab, T* ctab, int* uneven);
 
 // ---- pfa_kernels.hip: two-level (Good-Thomas) direct DFT for mesh dimensions N = N1 * N2 > 160 with a hard prime power N2
 struct PfaAxis { int N, N1, N2; };            // N1 = 1: plain direct lines
@@ -318,7 +325,7 @@ bool field_rider_ind(FieldRider<T>& r, int n_rows, const IndTable& it, const Sit
                      const ScaleTab<T>& tab, T kappa, T* fld, const int* rows);
 template <class T>
 void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                             int slot, const FieldRider<T>& fr);
+                             int slot, const FieldRider<T>& fr, const T* ctab = nullptr /* circulant form of the x pass */);
 // (nbr_kernels.hip) inner table of an MD loop: the entries of `full` whose minimum-image distance is below rc, rows compacted
 // in the order of `full`.  hipError_t as int; one host synchronisation (the entry count).
 template <class T>

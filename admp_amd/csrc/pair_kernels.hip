@@ -279,11 +279,13 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_field_ind(int na, const int
 // Workgroups with blockIdx.x < nbx are x-pass tiles (dft_lines.h), the others field workgroups number
 // (blockIdx.x - nbx) * gridDim.y + blockIdx.y.
 // (CUT: kind 1 walks an inner table, see k_pair_full; kind 2 takes its row ends from the sub-table in either case)
-template <class T, int LPR, bool CUT>
+// (CIRC: the x-pass tiles run the circulant form, dft_x_circ_body)
+template <class T, int LPR, bool CUT, bool CIRC>
 __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, FieldRider<T> fr, int nbx) {
   static_assert(kPairBlock == kDftBlock, "the two kinds of workgroups share one launch");
   if ((int)blockIdx.x < nbx) {
-    dft_x_conv_body<T, 2, 1>(xa, blockIdx.x, blockIdx.y, 0);
+    if (CIRC) dft_x_circ_body<T, 2>(xa, blockIdx.x, blockIdx.y);
+    else dft_x_conv_body<T, 2, 1>(xa, blockIdx.x, blockIdx.y, 0);
     return;
   }
   const unsigned bid = (blockIdx.x - (unsigned)nbx) * gridDim.y + blockIdx.y;
@@ -829,19 +831,29 @@ bool field_rider_ind(FieldRider<T>& r, int n_rows, const IndTable& it, const Sit
   return true;
 }
 // x pass of a direct-DFT convolution (one mesh) with the rider's workgroups appended to its grid
+// ctab != nullptr: the circulant form of the x pass (dft_kernels.hip launch_ctab; tw and tabs are then unused)
 template <class T>
 void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                             int slot, const FieldRider<T>& fr) {
+                             int slot, const FieldRider<T>& fr, const T* ctab) {
   const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
-  const int NC = dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
-  const size_t sh = sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
+  const int NC = ctab ? dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0)
+                      : dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
+  const size_t sh = ctab ? dft_x_circ_col_bytes<T>(N) * (size_t)NC
+                         : sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
   const int nbx = (Kh + NC - 1) / NC;
   const unsigned extra = (fr.grid + (unsigned)K[1] - 1) / (unsigned)K[1];
-  const XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
-                        reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
+  XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
+                  reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
+  xa.ctab = ctab;
   const dim3 grid((unsigned)nbx + extra, (unsigned)K[1], 1);
-  if (fr.kind == 1 && fr.rowend) k_xconv_pair<T, kRiderLpr, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
-  else k_xconv_pair<T, kRiderLpr, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+  const bool cut = fr.kind == 1 && fr.rowend;
+  if (ctab) {
+    if (cut) k_xconv_pair<T, kRiderLpr, true, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+    else k_xconv_pair<T, kRiderLpr, false, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+  } else {
+    if (cut) k_xconv_pair<T, kRiderLpr, true, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+    else k_xconv_pair<T, kRiderLpr, false, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
+  }
 }
 
 template <class T>
@@ -905,7 +917,7 @@ void launch_tt_pair(hipStream_t st, int na, const NbrTable& nb, const SRow<T>* s
   template bool field_rider_ind<T>(FieldRider<T>&, int, const IndTable&, const Site<T>*, const Box<T>&,             \
                                    const ScaleTab<T>&, T, T*, const int*);                                          \
   template void launch_dft_x_conv_rider<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int,  \
-                                           const FieldRider<T>&);                                                   \
+                                           const FieldRider<T>&, const T*);                                         \
   template void launch_pack_scalar_rows<T>(hipStream_t, int, int, const T*, const T*, SRow<T>*);                    \
   template void launch_disp_pair<T>(hipStream_t, int, const NbrTable&, const SRow<T>*, const Box<T>&,               \
                                     const ScaleTab<T>&, T, int, T*, double*, const int*, int, double);              \

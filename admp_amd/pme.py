@@ -430,6 +430,12 @@ class ADMPPmeForce(HipForceBase):
                 'wasted_increments', 'jacobi_steps')
         return dict(zip(keys, (int(v) for v in out)))
 
+    def xpass_stats(self, reset=False):
+        """Forms of the x passes of the direct-DFT mesh convolution so far (admp_xpass_stats): dict of counters."""
+        out = (ctypes.c_int64 * 2)()
+        _lib.check(self._h, self._L.admp_xpass_stats(self._h, out, 1 if reset else 0), 'admp_xpass_stats')
+        return {'circulant': int(out[0]), 'transforms': int(out[1])}
+
     def optimize_Uind(self, positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=None,
                       maxiter=None, thresh=None):
         """Jacobi SCF of the induced dipoles; returns (U, converged, i) like admp/pme.py:111-143."""

@@ -358,6 +358,9 @@ int admp_slab_home(admp_handle* h, int32_t* home_out, int* n_home, int* n_import
  * that needed more steps than enqueued, chained calls that enqueued more than needed, field increments that ran for nothing
  * in those, Jacobi steps in total}; reset != 0 clears the counters.  The results never depend on the form. */
 int admp_scf_stats(admp_handle* h, int64_t* out8, int reset);
+/* Which form the x passes of the direct-DFT mesh convolution took: out2 = {one real circulant product per line (G table
+ * even along x: orthorhombic cells; ADMP_DFT_XCIRC=0 turns it off), forward transform * G * inverse transform}. */
+int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* When enabled every kernel launch is bracketed by HIP events on the handle's stream. */

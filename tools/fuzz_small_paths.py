@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Fuzz of the small-system paths of round 4 (spread inside the forward plane transform, closing work in the gather, last
-chained residual in the closing gather, field kernels riding in the x pass, one stream) against the same library with all of
+chained residual in the closing gather, field kernels riding in the x pass, one stream) and of the circulant x pass against the same library with all of
 them switched off: random water boxes of several sizes on direct-DFT meshes, a few warm-started steps each (so that the
 speculative / chained / plain SCF forms all occur), energies / gradient / dipoles / cycle counts compared.
     python tools/fuzz_small_paths.py            # runs both legs in child processes and compares"""
 import os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OFF = dict(ADMP_FUSE_SPREAD_MAX='0', ADMP_FUSE_FIN_MAX='0', ADMP_FIELD_RIDER='0', ADMP_CHAIN_LAST_FIELD='1', ADMP_OVERLAP_MIN='0')
+OFF = dict(ADMP_FUSE_SPREAD_MAX='0', ADMP_FUSE_FIN_MAX='0', ADMP_FIELD_RIDER='0', ADMP_CHAIN_LAST_FIELD='1', ADMP_OVERLAP_MIN='0',
+           ADMP_DFT_XCIRC='0')
 CASES = [(125, (97, 97, 97), 11), (343, (61, 97, 53), 12), (700, (97, 67, 101), 13), (1500, (31, 97, 97), 14), (2600, (97, 97, 97), 15),
          (1024, (113, 59, 71), 16)]
 
