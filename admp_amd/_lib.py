@@ -60,6 +60,7 @@ PROTOTYPES = {
     'admp_slab_info': (_i32, [_vp, _c.POINTER(_i64)]),
     'admp_scf_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_xpass_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
+    'admp_pair_rider_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_set_comm': (_i32, [_vp, _vp]),
     'admp_slab_home': (_i32, [_vp, _vp, _ip, _ip]),
     'admp_rccl_unique_id': (_i32, [_vp]),

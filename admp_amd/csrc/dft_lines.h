@@ -4,6 +4,7 @@
 #include "dft_math.h"
 #include "launch.h"
 #include "reduce.h"
+#include "rider_layout.h"
 
 namespace admp {
 

@@ -190,6 +190,8 @@ struct EngineBase {
   int64_t scf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // x passes of the direct-DFT convolution of one mesh (admp_xpass_stats): [0] circulant form, [1] forward * G * inverse
   int64_t xpass_stats[2] = {0, 0};
+  // closing pair kernels of polarizable calls (admp_pair_rider_stats): [0] rode in an x pass, [1] launched on their own
+  int64_t pair_rider_stats[2] = {0, 0};
   const void* U_src = nullptr;  // admp_set_dipole_source: read-only initial dipoles of the NEXT polarizable evaluation
   const void* U_src_now = nullptr;   // ... taken over by that evaluation (Engine::pme), consumed by its site pass
   double cutoff = 0.0;          // admp_set_cutoff: listed pairs beyond it are skipped (0: every listed pair, as the reference)
@@ -1032,12 +1034,20 @@ struct Engine : EngineBase {
     static const bool on = env_flag("ADMP_FIELD_RIDER", true);
     return on && use_dft && !use_pfa && snranks == 1 && !overlap_ok();
   }
+  // pair rider: the closing pair kernel in the x pass (k_xconv_pair_full: small polarizable f64 systems).  ADMP_PAIR_RIDER=0
+  // restores the launch of its own (read per call: the parity test runs both forms in one process); so does
+  // ADMP_OPT_SIDE_STREAM = 0, the mode for clean per-kernel times, which keeps the kernel under its pair_full label.
+  bool pair_rider_ok() const {
+    return lpol && side_stream_on && rider_ok() && env_flag("ADMP_PAIR_RIDER", true);
+  }
   bool convolve(T* mesh_p, T* spec_p, const T* gtab, int slot, T* accum = nullptr, T* out = nullptr,
-                const PlaneSpread<T>* sp = nullptr, const FieldRider<T>* rider = nullptr) {
+                const PlaneSpread<T>* sp = nullptr, const FieldRider<T>* rider = nullptr, const FullRider<T>* prider = nullptr) {
     double* Ed = Ed_cur();
     T* mesh_o = out ? out : mesh_p;
     ARG_CHECK(!sp || (use_dft && !use_pfa && snranks == 1), "internal: plane spread on a transform path without it");
     ARG_CHECK(!(rider && rider->kind) || (use_dft && !use_pfa && snranks == 1), "internal: field rider on a transform path without it");
+    ARG_CHECK(!(prider && prider->on) || (use_dft && !use_pfa && snranks == 1 && !(rider && rider->kind == 1)),
+              "internal: pair rider on a transform path without it");
     if (snranks > 1) {
       // x-slab ranks: the stencils of the home atoms overhang into kGhost planes of the next rank (added there before the
       // transform), the 3-D transform is batched 2-D r2c on the owned planes -> transpose (all-to-all over the ranks: every
@@ -1094,7 +1104,11 @@ struct Engine : EngineBase {
       // G table of slot 0 even along x (every orthorhombic cell): one circulant product per line instead of two transforms
       const T* ct = xctab_ok && gtab == gtabs[0].template as<T>() ? xctab.template as<T>() : nullptr;
       ++xpass_stats[ct ? 0 : 1];
-      if (rider && rider->kind) { TIMED("dft_x_kspace"); launch_dft_x_conv_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *rider, ct); }
+      if (prider && prider->on) {
+        TIMED("dft_x_kspace");
+        launch_dft_x_conv_full_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *prider, rider && rider->kind == 2 ? rider : nullptr, ct);
+      }
+      else if (rider && rider->kind) { TIMED("dft_x_kspace"); launch_dft_x_conv_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *rider, ct); }
       else if (ct) { TIMED("dft_x_kspace"); launch_dft_x_circ<T>(stream, K, spec_p, ct, Ed, slot); }
       else { TIMED("dft_x_kspace"); launch_dft_x_conv<T>(stream, K, tw, spec_p, tabs, Ed, slot); }
       bool added;
@@ -1524,9 +1538,27 @@ struct Engine : EngineBase {
     }
     slot_clean[E_REAL] = false;
     check_mono_inputs(mono_ok);
+    if (lpol) ++pair_rider_stats[1];
     TIMED("pair_full");
     launch_pair_full<T>(stream, ev.n_home, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(),
                         Ed_cur(), pair_rows(), fld_out, mono_ok ? 1 : 0, cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole);
+  }
+  // stage_pair_full as a rider of the next x pass: everything but the launch (the energy words are cleared here, ahead of
+  // the fused launch); false = it cannot ride, nothing was done and the caller takes stage_pair_full
+  bool pair_full_rider(FullRider<T>& pr, T* grad_p, T* fld_out = nullptr) {
+    if (!pair_rider_ok()) return false;
+    need_eval();
+    check_mono_inputs(mono_ok);
+    if (!full_rider<T>(pr, ev.n_home, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(), Ed_cur(),
+                       pair_rows(), fld_out, mono_ok ? 1 : 0, cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole))
+      return false;
+    if (!slot_clean[E_REAL]) {
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_REAL, 0, sizeof(double), stream));
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_RPARTS, 0, E_PARTS * sizeof(double), stream));
+    }
+    slot_clean[E_REAL] = false;
+    ++pair_rider_stats[0];
+    return true;
   }
   // with_field_finish: the gather also forms the total dE/dU and its maximum (launch_field_finish's work, fused)
   // Small single-rank systems with frame groups: the closing kernel's work rides in the gather's epilogue (recip_kernels.hip,
@@ -1685,11 +1717,14 @@ struct Engine : EngineBase {
   // extra_side: more work for the side stream of this increment (the closing pair kernel of a chained call, whose dipoles are final)
   // field_from_total_phi: do not gather the increment's field -- the caller's next kernel is a full gather of the accumulated
   // phi with a field epilogue, which yields the same reciprocal field (and the residual) for every atom
-  void scf_increment(int n_act, unsigned long long* check_word = nullptr,   // fld_pair / fld_recip / phi <- their values for the dipoles after scf_jacobi
-                     const std::function<void()>& extra_side = nullptr, bool field_from_total_phi = false) {
+  // full_grad: the closing pair kernel (gradient rows full_grad) may ride in this increment's x pass -- the dipoles are
+  // final; returns whether it did
+  bool scf_increment(int n_act, unsigned long long* check_word = nullptr,   // fld_pair / fld_recip / phi <- their values for the dipoles after scf_jacobi
+                     const std::function<void()>& extra_side = nullptr, bool field_from_total_phi = false,
+                     T* full_grad = nullptr) {
     if (n_act <= 0 && snranks == 1) {
       if (extra_side) on_side(extra_side);
-      return;
+      return false;
     }
     const bool first = side_first();
     FieldRider<T> fr;      // (filled below, once the sub-table is current: the field kernel then rides in the x pass)
@@ -1729,14 +1764,17 @@ struct Engine : EngineBase {
       if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)}; }
     if (!first && !fused) side_work();
     const PlaneSpread<T> sp = plane_spread(n_act, isites.as<Site<T>>(), 1, nullptr);
+    FullRider<T> pr;
+    const bool full_rides = full_grad && pair_full_rider(pr, full_grad);
     const bool added = convolve(mesh2.as<T>(), spec.as<T>(), gtab_cur, E_SCRATCH, mesh.as<T>(), nullptr, fused ? &sp : nullptr,
-                                ride ? &fr : nullptr);
+                                ride ? &fr : nullptr, full_rides ? &pr : nullptr);
     join_side();
     if (!field_from_total_phi) {
       TIMED("gather_field_ind");
       launch_gather_field<T>(stream, n_act, isites.as<Site<T>>(), ev.g, mesh2.as<T>(), fld_recip.as<T>(), nullptr, 1, nullptr,
                              act_list(), check_word ? field_epilogue(check_word) : FieldFin<T>()); }
     if (!added) { TIMED("mesh_add"); launch_mesh_add<T>(stream, (long)nreal, mesh.as<T>(), mesh2.as<T>()); }
+    return full_rides;
   }
 
   // one device->host copy + sync: energies (and the max|field| word, returned).  On a slab rank the four parts are first
@@ -1782,7 +1820,7 @@ struct Engine : EngineBase {
   // evaluation); behind the spread it is hidden by a running kernel and the side kernels still have the three transform
   // passes to hide behind (side_first()).
   template <class F>
-  void recip_pass(int slot, F&& side_work, const FieldRider<T>* rider = nullptr) {
+  void recip_pass(int slot, F&& side_work, const FieldRider<T>* rider = nullptr, const FullRider<T>* prider = nullptr) {
     need_eval();
     const bool fused = spread_fused(ev.n_home);      // the forward transform spreads (dft_kernels.hip, zy_plane_spread)
     const bool first = side_first() || fused;
@@ -1792,7 +1830,14 @@ struct Engine : EngineBase {
     if (!slot_clean[slot]) HIP_TRY(hipMemsetAsync(Ed_cur() + slot, 0, sizeof(double), stream));
     slot_clean[slot] = false;
     const PlaneSpread<T> sp = plane_spread(ev.n_home, sites.as<Site<T>>(), lpol, ev.bases);
-    convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, slot, nullptr, nullptr, fused ? &sp : nullptr, rider);
+    convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, slot, nullptr, nullptr, fused ? &sp : nullptr, rider, prider);
+  }
+  // reciprocal pass + closing pair kernel (gradient rows grad_p; fld_out: its dE/dU as well): in the x pass, or next to
+  // the mesh chain on the side stream / ahead of it on this one
+  void recip_pass_pair_full(int slot, T* grad_p, T* fld_out = nullptr) {
+    FullRider<T> pr;
+    if (pair_full_rider(pr, grad_p, fld_out)) recip_pass(slot, [] {}, nullptr, &pr);
+    else recip_pass(slot, [&] { on_side([&] { stage_pair_full(grad_p, fld_out); }); });
   }
   void recip_pass(int slot) { recip_pass(slot, [] {}); }
   // first field evaluation of a call: the mesh chain and the real-space field of all partners -- on the side stream, or (small
@@ -1896,6 +1941,7 @@ struct Engine : EngineBase {
     first_gather_field(field_epilogue(word(0)));
     launch_field_check(word(0));
     const bool early_full = overlap_ok();       // the closing pair kernel next to the last increment's mesh chain
+    bool full_rode = false;                     // ... or inside its x pass (pair_rider_ok(): never both)
     // the last residual rides in the closing gather (it reads the accumulated phi anyway): the field gather of the last
     // increment is not run (small single-rank systems; ADMP_CHAIN_LAST_FIELD=1 keeps it: A/B, tests)
     static const bool keep_last = env_flag("ADMP_CHAIN_LAST_FIELD", false);
@@ -1906,10 +1952,10 @@ struct Engine : EngineBase {
       if (early_full && last)      // (the dipoles are final now)
         scf_increment(n_act, word(c + 1), [&] { stage_pair_full(io.gbuf); }, last_in_gather);
       else
-        scf_increment(n_act, word(c + 1), nullptr, last && last_in_gather);
+        full_rode = scf_increment(n_act, word(c + 1), nullptr, last && last_in_gather, last ? io.gbuf : nullptr);
       if (!(last && last_in_gather)) launch_field_check(word(c + 1));
     }
-    if (!early_full) stage_pair_full(io.gbuf);
+    if (!early_full && !full_rode) stage_pair_full(io.gbuf);
     const FinishArgs<T> fin_c = finish_args(io.dpos != nullptr, io.dQl);
     if (last_in_gather) {
       const FieldFin<T> ffl = field_epilogue(word(nhat));
@@ -1947,7 +1993,7 @@ struct Engine : EngineBase {
   // same (U, flag, i) as the plain loop; a failed check only costs the difference between the kernels.
   // The closing kernel is enqueued speculatively as well, so the step has ONE host synchronisation.
   void scf_speculative(ScfRun& run, const PmeIo& io, double thresh) {
-    recip_pass(E_SCF_RECIP, [&] { on_side([&] { stage_pair_full(io.gbuf, fld_pair.as<T>()); }); });
+    recip_pass_pair_full(E_SCF_RECIP, io.gbuf, fld_pair.as<T>());
     // small systems are dispatch-bound: the field finish rides in the gather's epilogue; larger ones keep the two
     // kernels (98k atoms: gather 26 -> 47 us fused against 9 us saved; 1M atoms: 0.40 vs 0.31 + 0.056 ms)
     const bool fuse_ff = top.na <= fuse_ff_max();
@@ -2000,7 +2046,7 @@ struct Engine : EngineBase {
   void closing_pass(const ScfRun& run, const PmeIo& io) {
     const bool atoms_energy = run.phi_valid && run.phi_accum;
     if (!run.done) {
-      if (!run.phi_valid) recip_pass(E_RECIP, [&] { on_side([&] { stage_pair_full(io.gbuf); }); });
+      if (!run.phi_valid) recip_pass_pair_full(E_RECIP, io.gbuf);
       else stage_pair_full(io.gbuf);
       // (the partial words are zero: nothing else of this evaluation writes them)
       const FinishArgs<T> fin_t = finish_args(io.dpos != nullptr, io.dQl);
@@ -3306,6 +3352,12 @@ int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out2, "null");
     for (int k = 0; k < 2; ++k) { out2[k] = e.xpass_stats[k]; if (reset) e.xpass_stats[k] = 0; }
+  });
+}
+int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(out2, "null");
+    for (int k = 0; k < 2; ++k) { out2[k] = e.pair_rider_stats[k]; if (reset) e.pair_rider_stats[k] = 0; }
   });
 }
 int admp_slab_home(admp_handle* h, int32_t* home_out, int* n_home, int* n_import) {

@@ -326,6 +326,38 @@ bool field_rider_ind(FieldRider<T>& r, int n_rows, const IndTable& it, const Sit
 template <class T>
 void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
                              int slot, const FieldRider<T>& fr, const T* ctab = nullptr /* circulant form of the x pass */);
+// The closing pair kernel (k_pair_full, polarizable, double precision) riding in the x pass of a direct-DFT convolution
+// (pair_kernels.hip k_xconv_pair_full): launch_pair_full's arguments.  full_rider: false = this launch cannot ride (no rows,
+// another lane count or type than the rider kernel is compiled for) -- the caller then launches k_pair_full on its own.
+template <class T>
+struct FullRider {
+  int on = 0, na = 0;
+  const int* rowptr = nullptr;
+  const int* rowend = nullptr;
+  const int* col = nullptr;
+  const Site<T>* sites = nullptr;
+  Box<T> box;
+  ScaleTab<T> tab;
+  T kappa = 0;
+  T* grad = nullptr;
+  T* pot = nullptr;
+  double* energies = nullptr;
+  const int* rows = nullptr;
+  T* fld = nullptr;
+  unsigned nblocks = 0, grid = 0;
+  int use_mono = 0;
+  const int* cls_flags = nullptr;
+  const RQ4<T>* rq = nullptr;
+  const T* tholes = nullptr;
+};
+template <class T>
+bool full_rider(FullRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box, const ScaleTab<T>& tab,
+                T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows, T* fld, int use_mono,
+                const int* cls_flags, const RQ4<T>* rq, const T* tholes);
+// x pass + closing pair kernel (+ the field-increment kernel: fr of kind 2, or nullptr) in one launch
+template <class T>
+void launch_dft_x_conv_full_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
+                                  int slot, const FullRider<T>& pr, const FieldRider<T>* fr, const T* ctab);
 // (nbr_kernels.hip) inner table of an MD loop: the entries of `full` whose minimum-image distance is below rc, rows compacted
 // in the order of `full`.  hipError_t as int; one host synchronisation (the entry count).
 template <class T>

@@ -42,27 +42,51 @@ __device__ __forceinline__ void stage_tab(const ScaleTab<T>& tab, T* s) {
 // CUT (admp_set_cutoff on a multipolar handle): the kernel walks the evaluation's inner table (build_cut_table: the entries
 // below the cutoff at this call's sites, at the rows' own offsets) and a row ends at rowend[row]; without it at rowptr[row + 1],
 // exactly as before the option existed (rowend unused).
-template <class T, bool LPOL, int LPR, int MINW, bool CUT>
-__global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const int* __restrict__ rowptr,
-                                                          const int* __restrict__ rowend, const int* __restrict__ col,
-                                                          const Site<T>* __restrict__ sites, Box<T> box,
-                                                          ScaleTab<T> tab, T kappa, T* __restrict__ grad,
-                                                          T* __restrict__ pot, double* energies,
-                                                          const int* __restrict__ rows, T* __restrict__ fld,
-                                                          unsigned nblocks, int use_mono,
-                                                          const int* __restrict__ cls_flags,
-                                                          const RQ4<T>* __restrict__ rq, const T* __restrict__ tholes) {
+// The body is a device function of the workgroup's rank `bid`: blockIdx.x of k_pair_full, or the rank among the pair
+// workgroups that ride in an x pass of the mesh convolution (k_xconv_pair_full below).
+// ILDS (the rider, which has to fit 256 registers to run two waves per SIMD next to the x-pass tiles): the row atom's site
+// is staged once per row in LDS and read from there by the row's LPR lanes at every partner, instead of living in 40
+// registers across the loops.  Same values, same arithmetic in the same order.
+// The f64 rider kernel under its 256-register bound: 304 B of scratch per lane with the body as it is, 144 B with the row
+// site in LDS.  Tried on top of that: the lane's 15 accumulators in LDS as well (30 registers less: 48 B of scratch, what
+// the x-pass tiles use on their own, but 34 KB of LDS per workgroup): fused launch 22.1 against 22.0 us at 3072 atoms on
+// the 97^3 mesh -- no gain, not kept; the launch is as long as the two rounds of tiles next to the pair workgroups, not
+// as the pair workgroups' spills.
+template <class T, bool LPOL, int LPR, bool CUT, bool ILDS>
+__device__ __forceinline__ void pair_full_block(unsigned bid, int na, const int* __restrict__ rowptr,
+                                                const int* __restrict__ rowend, const int* __restrict__ col,
+                                                const Site<T>* __restrict__ sites, const Box<T>& box,
+                                                const ScaleTab<T>& tab, T kappa, T* __restrict__ grad,
+                                                T* __restrict__ pot, double* energies,
+                                                const int* __restrict__ rows, T* __restrict__ fld,
+                                                unsigned nblocks, int use_mono,
+                                                const int* __restrict__ cls_flags,
+                                                const RQ4<T>* __restrict__ rq, const T* __restrict__ tholes) {
   __shared__ T s_tab[48];
   stage_tab(tab, s_tab);
-  const long blk = xcd_block(blockIdx.x, nblocks);
+  const long blk = xcd_block(bid, nblocks);
   const long t = (blk < 0 ? (long)na * LPR : blk * kFullBlock) + threadIdx.x;
   const int slot = (int)(t / LPR), sub = (int)(t % LPR);
   // `na` counts the rows this launch owns; with a row list (multi-GPU: the rank's home atoms) slot -> atom
   const int row = slot < na ? (rows ? rows[slot] : slot) : na;
   T g[3] = {0, 0, 0}, P[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, F[3] = {0, 0, 0};
   double e = 0.0;
+  __shared__ Site<T> s_I[ILDS ? kFullBlock / LPR : 1];
+  if (ILDS) {
+    if (slot < na && sub == 0) s_I[threadIdx.x / LPR] = sites[row];
+    __syncthreads();
+  }
   if (slot < na) {
-    const Site<T> I = sites[row];
+    Site<T> Ir;
+    if (!ILDS) Ir = sites[row];
+    // ILDS: one read of the staged row per partner; the index passes through an empty asm statement, or the compiler
+    // hoists the (loop-invariant) reads out of the loops and the row is back in registers
+    auto row_site = [&]() -> const Site<T>& {
+      if (!ILDS) return Ir;
+      int ri = (int)threadIdx.x / LPR;
+      asm volatile("" : "+v"(ri));
+      return s_I[ri];
+    };
     const int beg = rowptr[row] + sub, end = CUT ? rowend[row] : rowptr[row + 1];
     T* Fp = (LPOL && fld) ? F : nullptr;
     // Charge-only sites (pme_math.h).  The neighbour table was compiled with the atoms' classes (NbrTable::cls): the entries
@@ -72,7 +96,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
     // when the table's classes are out of date (CLS_STALE: an atom it has as charge-only is not any more) the marks are
     // ignored and every partner takes the general form -- valid for any site.
     const bool use = use_mono && !(*cls_flags & CLS_STALE);
-    const bool imono = use_mono && site_is_mono(I);
+    const bool imono = use_mono && site_is_mono(row_site());
     // The loops are software-pipelined: an iteration's col entry (and, in the light loops, the partner's position / charge
     // words) are fetched one or two iterations ahead -- the dependent chain col -> site -> arithmetic otherwise leaves the
     // waves waiting (SQ_WAIT_ANY 71 % of the wave cycles at 4 waves per SIMD once the arithmetic per partner had shrunk).
@@ -88,7 +112,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
           const Site<T> J = sites[c & kColMask];
           const int nb = col_nb(c);
           const PairScales<T> sc = {s_tab[nb], s_tab[16 + nb], s_tab[32 + nb]};
-          e += (double)pair_energy_grad<T, LPOL, false>(box, I, J, sc, kappa, g, P, Fp, nullptr, nullptr);
+          e += (double)pair_energy_grad<T, LPOL, false>(box, row_site(), J, sc, kappa, g, P, Fp, nullptr, nullptr);
           c = cn;
         }
       }
@@ -103,7 +127,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
           const T t1 = tholes ? tholes[c1 & kColMask] : T(0);
           const int nb = col_nb(c0);
           const PairScales<T> sc = {s_tab[nb], s_tab[16 + nb], s_tab[32 + nb]};
-          e += (double)pair_full_mono<T, LPOL>(box, I, q0.v, q0.v[3], t0, sc, kappa, g, P, Fp);
+          e += (double)pair_full_mono<T, LPOL>(box, row_site(), q0.v, q0.v[3], t0, sc, kappa, g, P, Fp);
           c0 = c1; c1 = c2; q0 = q1; t0 = t1;
         }
       }
@@ -117,6 +141,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
           const Site<T> J = sites[c & kColMask];
           const int nb = col_nb(c);
           const PairScales<T> sc = {s_tab[nb], s_tab[16 + nb], s_tab[32 + nb]};
+          const Site<T>& I = row_site();
           e += (double)pair_mono_full<T, LPOL>(box, I.r, I.Q[0], I.thole, J, sc, kappa, g, P[0]);
           c = cn;
         }
@@ -128,6 +153,7 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
         for (; k < end; k += LPR) {
           const int c2 = k + 2 * LPR < end ? col[k + 2 * LPR] : 0;
           const RQ4<T> q1 = rq[c1 & kColMask];
+          const Site<T>& I = row_site();
           e += (double)pair_mono_mono<T>(box, I.r, I.Q[0], q0.v, q0.v[3], s_tab[col_nb(c0)], kappa, g, P[0]);
           c0 = c1; c1 = c2; q0 = q1;
         }
@@ -150,7 +176,20 @@ __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const in
     if (LPOL && fld) { fld[3 * row] = F[0]; fld[3 * row + 1] = F[1]; fld[3 * row + 2] = F[2]; }
   }
   e = block_reduce_sum<kFullBlock>(e);
-  if (threadIdx.x == 0) atomicAdd(&energies[E_RPARTS + (blockIdx.x & (E_PARTS - 1))], 0.5 * e);
+  if (threadIdx.x == 0) atomicAdd(&energies[E_RPARTS + (bid & (E_PARTS - 1))], 0.5 * e);
+}
+template <class T, bool LPOL, int LPR, int MINW, bool CUT>
+__global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const int* __restrict__ rowptr,
+                                                          const int* __restrict__ rowend, const int* __restrict__ col,
+                                                          const Site<T>* __restrict__ sites, Box<T> box,
+                                                          ScaleTab<T> tab, T kappa, T* __restrict__ grad,
+                                                          T* __restrict__ pot, double* energies,
+                                                          const int* __restrict__ rows, T* __restrict__ fld,
+                                                          unsigned nblocks, int use_mono,
+                                                          const int* __restrict__ cls_flags,
+                                                          const RQ4<T>* __restrict__ rq, const T* __restrict__ tholes) {
+  pair_full_block<T, LPOL, LPR, CUT, false>(blockIdx.x, na, rowptr, rowend, col, sites, box, tab, kappa, grad, pot, energies, rows, fld,
+                                            nblocks, use_mono, cls_flags, rq, tholes);
 }
 
 // (bid: the workgroup's index in a launch of its own -- blockIdx.x of k_pair_field, or its rank among the field workgroups
@@ -295,6 +334,30 @@ __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, Fiel
                              fr.n_dev, fr.cls_flags, fr.rq, fr.tholes);
   else
     pair_field_ind_block<T, LPR>(bid, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows);
+}
+
+// ---- the closing pair kernel riding in the x pass (small systems on one stream) ------------------------------------------------
+// Every polarizable call ends with one k_pair_full that depends on the site rows only; nothing of the mesh chain needs its
+// rows before the closing gather.  Its workgroups ride in an x pass like the field kernels above, but in a kernel of their
+// own: the f64 polarizable body wants 256 registers, and a fused kernel takes the register count of its largest body, so
+// this one is compiled for two waves per SIMD (two workgroups per CU: 512 slots for 192 pair workgroups and 485 tiles at
+// 3072 atoms on the 97^3 mesh) while k_xconv_pair keeps its three.  Block ids: rider_layout.h (pair workgroups first).
+// fr.kind == 2: the field-increment kernel of a chained SCF call rides as well (rg.nind workgroups).
+// Measured at 3072 atoms on the 97^3 mesh: 22.0 us against 19.1 (x pass) + 13.9 (k_pair_full) in a row.  A raised wave
+// priority for the tile workgroups (s_setprio 2) changed neither the launch (22.0 us) nor the step time: not kept.
+template <class T, int LPR, bool CUT, bool CIRC>
+__global__ __launch_bounds__(kPairBlock, 2) void k_xconv_pair_full(XConvArgs<T> xa, FullRider<T> pr, FieldRider<T> fr, RiderGrid rg) {
+  static_assert(kPairBlock == kDftBlock && kFullBlock == kDftBlock, "the kinds of workgroups share one launch");
+  const RiderBlock b = rider_block(rg, blockIdx.x, blockIdx.y, gridDim.x);      // (workgroup-uniform)
+  if (b.kind == RIDER_TILE) {
+    if (CIRC) dft_x_circ_body<T, 2>(xa, (int)b.bx, (int)b.by);
+    else dft_x_conv_body<T, 2, 1>(xa, (int)b.bx, (int)b.by, 0);
+  } else if (b.kind == RIDER_PAIR) {
+    pair_full_block<T, true, LPR, CUT, true>(b.rank, pr.na, pr.rowptr, pr.rowend, pr.col, pr.sites, pr.box, pr.tab, pr.kappa, pr.grad, pr.pot,
+                                             pr.energies, pr.rows, pr.fld, pr.nblocks, pr.use_mono, pr.cls_flags, pr.rq, pr.tholes);
+  } else if (b.kind == RIDER_IND) {
+    pair_field_ind_block<T, LPR>(b.rank, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows);
+  }
 }
 
 // dispersion / Tang-Toennies: scalar pair terms, same row layout.  Position and parameters of an atom are packed into ONE
@@ -856,6 +919,47 @@ void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spe
   }
 }
 
+// the closing pair kernel as a rider (k_xconv_pair_full).  Double precision, polarizable, kRiderLpr lanes per row; single
+// precision (127 registers under the same bound) has not been measured as a rider and keeps its own launch.
+template <class T>
+bool full_rider(FullRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box, const ScaleTab<T>& tab,
+                T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows, T* fld, int use_mono,
+                const int* cls_flags, const RQ4<T>* rq, const T* tholes) {
+  if (sizeof(T) != 8 || !lpol || na <= 0 || pair_lanes_per_row(na) != kRiderLpr) return false;
+  if (pair_mono_off() || !cls_flags || !rq) use_mono = 0;
+  r.on = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nb.rowend; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
+  r.kappa = kappa; r.grad = grad; r.pot = pot; r.energies = energies; r.rows = rows; r.fld = fld;
+  r.nblocks = grid_full(na, kRiderLpr); r.grid = xcd_grid(r.nblocks);
+  r.use_mono = use_mono; r.cls_flags = cls_flags; r.rq = rq; r.tholes = tholes;
+  return true;
+}
+template <class T>
+void launch_dft_x_conv_full_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
+                                  int slot, const FullRider<T>& pr, const FieldRider<T>* fr, const T* ctab) {
+  if constexpr (sizeof(T) == 8) {
+    const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
+    const int NC = ctab ? dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0)
+                        : dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
+    const size_t sh = ctab ? dft_x_circ_col_bytes<T>(N) * (size_t)NC
+                           : sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
+    XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
+                    reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
+    xa.ctab = ctab;
+    RiderGrid rg;
+    rg.npair = pr.grid; rg.nind = fr ? fr->grid : 0u; rg.nbx = (unsigned)((Kh + NC - 1) / NC); rg.ny = (unsigned)K[1];
+    const FieldRider<T> none{};
+    const FieldRider<T>& f2 = fr ? *fr : none;
+    const dim3 grid(rider_grid_blocks(rg), 1, 1);
+    if (ctab) {
+      if (pr.rowend) k_xconv_pair_full<T, kRiderLpr, true, true><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
+      else k_xconv_pair_full<T, kRiderLpr, false, true><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
+    } else {
+      if (pr.rowend) k_xconv_pair_full<T, kRiderLpr, true, false><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
+      else k_xconv_pair_full<T, kRiderLpr, false, false><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
+    }
+  }
+}
+
 template <class T>
 void launch_pair_field_ind(hipStream_t st, int n_rows, const IndTable& it, const Site<T>* sites, const Box<T>& box,
                            const ScaleTab<T>& tab, T kappa, T* fld, const int* rows) {
@@ -918,6 +1022,10 @@ void launch_tt_pair(hipStream_t st, int na, const NbrTable& nb, const SRow<T>* s
                                    const ScaleTab<T>&, T, T*, const int*);                                          \
   template void launch_dft_x_conv_rider<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int,  \
                                            const FieldRider<T>&, const T*);                                         \
+  template bool full_rider<T>(FullRider<T>&, int, const NbrTable&, const Site<T>*, const Box<T>&, const ScaleTab<T>&, T, int, T*, \
+                              T*, double*, const int*, T*, int, const int*, const RQ4<T>*, const T*);               \
+  template void launch_dft_x_conv_full_rider<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int, \
+                                                const FullRider<T>&, const FieldRider<T>*, const T*);               \
   template void launch_pack_scalar_rows<T>(hipStream_t, int, int, const T*, const T*, SRow<T>*);                    \
   template void launch_disp_pair<T>(hipStream_t, int, const NbrTable&, const SRow<T>*, const Box<T>&,               \
                                     const ScaleTab<T>&, T, int, T*, double*, const int*, int, double);              \

@@ -436,6 +436,12 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(self._h, self._L.admp_xpass_stats(self._h, out, 1 if reset else 0), 'admp_xpass_stats')
         return {'circulant': int(out[0]), 'transforms': int(out[1])}
 
+    def pair_rider_stats(self, reset=False):
+        """Where the closing pair kernels of the polarizable calls ran so far (admp_pair_rider_stats): dict of counters."""
+        out = (ctypes.c_int64 * 2)()
+        _lib.check(self._h, self._L.admp_pair_rider_stats(self._h, out, 1 if reset else 0), 'admp_pair_rider_stats')
+        return {'rode': int(out[0]), 'own_launch': int(out[1])}
+
     def optimize_Uind(self, positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=None,
                       maxiter=None, thresh=None):
         """Jacobi SCF of the induced dipoles; returns (U, converged, i) like admp/pme.py:111-143."""

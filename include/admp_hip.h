@@ -361,6 +361,9 @@ int admp_scf_stats(admp_handle* h, int64_t* out8, int reset);
 /* Which form the x passes of the direct-DFT mesh convolution took: out2 = {one real circulant product per line (G table
  * even along x: orthorhombic cells; ADMP_DFT_XCIRC=0 turns it off), forward transform * G * inverse transform}. */
 int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset);
+/* Where the closing pair kernel of the polarizable calls ran: out2 = {inside the x pass of a mesh convolution (small
+ * double-precision systems on the direct-DFT mesh, one stream; ADMP_PAIR_RIDER=0 turns it off), in a launch of its own}. */
+int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* When enabled every kernel launch is bracketed by HIP events on the handle's stream. */

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Fuzz of the small-system paths of round 4 (spread inside the forward plane transform, closing work in the gather, last
-chained residual in the closing gather, field kernels riding in the x pass, one stream) and of the circulant x pass against the same library with all of
+chained residual in the closing gather, field kernels and the closing pair kernel riding in the x pass, one stream) and of the
+circulant x pass against the same library with all of
 them switched off: random water boxes of several sizes on direct-DFT meshes, a few warm-started steps each (so that the
 speculative / chained / plain SCF forms all occur), energies / gradient / dipoles / cycle counts compared.
     python tools/fuzz_small_paths.py            # runs both legs in child processes and compares"""
@@ -8,7 +9,7 @@ import os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFF = dict(ADMP_FUSE_SPREAD_MAX='0', ADMP_FUSE_FIN_MAX='0', ADMP_FIELD_RIDER='0', ADMP_CHAIN_LAST_FIELD='1', ADMP_OVERLAP_MIN='0',
-           ADMP_DFT_XCIRC='0')
+           ADMP_DFT_XCIRC='0', ADMP_PAIR_RIDER='0')
 CASES = [(125, (97, 97, 97), 11), (343, (61, 97, 53), 12), (700, (97, 67, 101), 13), (1500, (31, 97, 97), 14), (2600, (97, 97, 97), 15),
          (1024, (113, 59, 71), 16)]
 
@@ -45,6 +46,7 @@ def leg(path):
             out[key + '_U'] = np.asarray(U)
             out[key + '_c'] = np.asarray([f.n_cycle, int(f.lconverg)])
         out['%d_forms' % n_mol] = np.asarray([f.scf_stats()[k] for k in ('plain', 'speculative', 'chained')])
+        out['%d_rides' % n_mol] = np.asarray([f.pair_rider_stats()[k] for k in ('rode', 'own_launch')])
     np.savez(path, **out)
 
 
@@ -64,8 +66,15 @@ if __name__ == '__main__':
     worst = 0.0
     for k, a in res['on'].items():
         b = res['off'][k]
-        if k.endswith('_forms'):
-            print(k, 'forms on', a, 'off', b)
+        if k.endswith('_forms') or k.endswith('_rides'):
+            print(k, 'on', a, 'off', b)
+            if k.endswith('_rides'):
+                # on: the closing pair kernel rode in every speculative and chained call of the one-stream sizes (below
+                # ADMP_OVERLAP_MIN = 4096 atoms; from there on it runs on the side stream); off: never
+                small = 3 * int(k.split('_')[0]) < 4096
+                forms = res['on'][k.replace('_rides', '_forms')]
+                assert b[0] == 0 and a.sum() == b.sum(), (k, a, b)
+                assert (a[0] >= forms[1] + forms[2] and a[0] > 0) if small else a[0] == 0, (k, a, forms)
             continue
         if k.endswith('_c'):
             assert (a == b).all(), (k, a, b)
