@@ -60,6 +60,7 @@ PROTOTYPES = {
     'admp_slab_info': (_i32, [_vp, _c.POINTER(_i64)]),
     'admp_scf_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_xpass_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
+    'admp_mesh_convolve': (_i32, [_vp, _dp, _i32, _vp, _i32, _dp, _ip]),
     'admp_pair_rider_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_set_comm': (_i32, [_vp, _vp]),
     'admp_slab_home': (_i32, [_vp, _vp, _ip, _ip]),
@@ -100,6 +101,9 @@ OPT_REFERENCE_KPOINTS = 1
 OPT_KEEP_POL_SITES = 2
 OPT_SIDE_STREAM = 3
 RCCL_ID_BYTES, RCCL_NTAGS = 128, 8
+# admp_mesh_convolve: words of its info array, values of info[0]
+MESH_INFO_WORDS = 16
+MESH_PATHS = ('rocfft', 'fused_x', 'direct_lines', 'direct_planes', 'two_level')
 
 _lib = None
 

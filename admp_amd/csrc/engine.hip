@@ -263,6 +263,7 @@ struct EngineBase {
   virtual void pme_at_U(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                         const double* mS, const double* pS, const void* U, double* E, void* dpos, void* dU, void* dQl) = 0;
   virtual void local_frames(const void* pos, const double* box, void* out) = 0;
+  virtual void mesh_convolve(const double* box, int which, void* data, int on_device, double* E_out, int32_t* info) = 0;
   virtual void pair_program_eval(int id, const void* pos, const double* box, const void* par, int ns, const double* mS,
                                  double* E, void* dpos, int on_device) = 0;
 
@@ -651,7 +652,7 @@ struct Engine : EngineBase {
 
   void set_ewald(double kappa_, int K1, int K2, int K3, int lmax_, int lpol_) override {
     ARG_CHECK(kappa_ > 0, "kappa must be positive");
-    ARG_CHECK(K1 >= 6 && K2 >= 6 && K3 >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
+    ARG_CHECK(K1 >= 2 && K2 >= 2 && K3 >= 2, "PME mesh must be at least 2 points per dimension");   // (spline users: make_geom)
     ARG_CHECK(lmax_ >= 0 && lmax_ <= 2, "l > 2 (beyond quadrupole) not supported");   // admp/recip.py:275
     kappa = kappa_; K[0] = K1; K[1] = K2; K[2] = K3; lmax = lmax_; lpol = lpol_ ? 1 : 0;
     have_ewald = true;
@@ -1194,6 +1195,8 @@ struct Engine : EngineBase {
   }
 
   RecipGeom<T> make_geom(const double* inv) {
+    // every spread and gather comes through here; only admp_mesh_convolve, which has no splines, takes shorter meshes
+    ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
     RecipGeom<T> g;
     for (int d = 0; d < 3; ++d) g.K[d] = K[d];
     for (int k = 0; k < 9; ++k) g.hinv[k] = (T)inv[k];
@@ -1240,6 +1243,43 @@ struct Engine : EngineBase {
         HIP_TRY(hipStreamSynchronize(stream));
         xctab_ok = uneven == 0;
       }
+    }
+  }
+
+  // admp_mesh_convolve: the k-space leg alone on a mesh of the caller's -- ensure_mesh, the handle's own G table, convolve():
+  // what an evaluation runs between its spread and its gather, without riders or plane spread (tests feed it meshes)
+  void mesh_convolve(const double* box, int which, void* data_, int on_device, double* E_out, int32_t* info) override {
+    ARG_CHECK(have_ewald, "admp_set_ewald first");
+    ARG_CHECK(snranks == 1, "admp_mesh_convolve works on a single rank only (slab-decomposed handle)");
+    ARG_CHECK(box && data_ && E_out && info, "null argument");
+    ARG_CHECK(which == 1 || which == 6 || which == 8 || which == 10, "which must be 1, 6, 8 or 10");
+    double inv[9], vol;
+    make_box(box, inv, &vol);
+    ensure_mesh();
+    ensure_gtab(box, inv, vol, which);
+    const size_t nreal = (size_t)K[0] * K[1] * K[2];
+    T* m = on_device ? reinterpret_cast<T*>(data_) : mesh.as<T>();
+    if (!on_device) HIP_TRY(hipMemcpyAsync(m, data_, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
+    energies_d.need(2 * E_WORDS * sizeof(double));
+    ehalf = 0; other_clean = false;
+    HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
+    const int64_t circ0 = xpass_stats[0];
+    convolve(m, spec.as<T>(), gtab_cur, E_RECIP);
+    if (!on_device) HIP_TRY(hipMemcpyAsync(data_, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(E_out, Ed_cur() + E_RECIP, sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < ADMP_MESH_INFO_WORDS; ++k) info[k] = 0;
+    if (use_pfa) {
+      info[0] = ADMP_MESH_PATH_TWO_LEVEL;
+      int forms[9];
+      pfa_forms(pfa, sizeof(T), forms);
+      for (int d = 0; d < 3; ++d) { info[2 + d] = pfa.ax[d].N1; info[5 + d] = pfa.ax[d].N2; info[12 + d] = forms[3 * d + 1]; }
+      info[8] = forms[0]; info[9] = forms[3]; info[10] = forms[6]; info[11] = forms[8];
+    } else if (use_dft) {
+      info[0] = dft_zy_fits<T>(K) ? ADMP_MESH_PATH_DIRECT_PLANES : ADMP_MESH_PATH_DIRECT_LINES;
+      info[1] = xpass_stats[0] > circ0 ? 1 : 2;
+    } else {
+      info[0] = use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT;
     }
   }
 
@@ -3353,6 +3393,10 @@ int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset) {
     ARG_CHECK(out2, "null");
     for (int k = 0; k < 2; ++k) { out2[k] = e.xpass_stats[k]; if (reset) e.xpass_stats[k] = 0; }
   });
+}
+int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
+                       int32_t* info16) {
+  return guarded(h, [&](EngineBase& e) { e.mesh_convolve(box, which, mesh_inout, on_device, E_out, info16); });
 }
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {

@@ -8,6 +8,7 @@
 
 #include "env.h"
 #include "frame_math.h"
+#include "pfa_maps.h"
 #include "pme_math.h"
 #include "spline_math.h"
 
@@ -233,17 +234,17 @@ template <class T>
 void launch_ctab(hipStream_t st, const int K[3], const T* gtab, T* ctab, int* uneven);
 
 // ---- pfa_kernels.hip: two-level (Good-Thomas) direct DFT for mesh dimensions N = N1 * N2 > 160 with a hard prime power N2
-struct PfaAxis { int N, N1, N2; };            // N1 = 1: plain direct lines
+// (PfaAxis, the split and the index maps: pfa_maps.h)
 struct PfaPlan {
   PfaAxis ax[3];
   int Khp;                                    // stored z columns: ax[2].N1 * (ax[2].N2 / 2 + 1)
   int tw_off[3];                              // twiddles of axis d at tw + tw_off[d] (complex entries): N2 entries, then N1
   const int* ptab[3];                         // device: index table of axis d (pfa_index_table)
 };
-bool pfa_split(int N, PfaAxis* out);          // false: no usable split
-void pfa_index_table(const PfaAxis& a, int* t);       // t[n1 * N2 + n2] = position | n1 << 16
-void pfa_freq_of_slot(const PfaAxis& a, int* f);      // f[slot] = frequency stored at that position of the axis
-void pfa_freq_of_zcolumn(const PfaAxis& a, int* f);   // the same for the Khp stored z columns
+bool pfa_split(int N, PfaAxis* out);          // pfa_split_at with ADMP_PFA_MIN (default 160) as plain_max; false: no usable split
+// which form each pass of the plan takes for words of w bytes: out[3 * d + 0 .. 2] = columns (x, y: NC) or lines (z: NL of the
+// forward pass) per workgroup, MFMA stage A or not, NL of the inverse z pass (0 on x and y) -- the launchers' own choices
+void pfa_forms(const PfaPlan& p, size_t w, int out[9]);
 template <class T>
 void launch_pfa_z(hipStream_t st, const PfaPlan& p, const T* tw, T* mesh, T* spec, int inverse, int nb = 1, long mesh_stride = 0,
                   long spec_stride = 0);

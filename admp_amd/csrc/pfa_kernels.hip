@@ -29,8 +29,6 @@ namespace admp {
 constexpr int kPfaBlock = 256;
 extern __shared__ __align__(32) unsigned char pfa_smem[];
 
-__host__ __device__ inline int pfa_pos(const PfaAxis& a, int n1, int n2) { return (a.N2 * n1 + a.N1 * n2) % a.N; }
-
 // sum_n1 y[n1 * stride] w1^(sign n1 k1), k1 fixed: the short stage (N1 <= 32)
 template <class T>
 __device__ __forceinline__ Cx<T> short_dft(int N1, int k1, int sign, const Cx<T>* y, int stride, const Cx<T>* tw1) {
@@ -608,39 +606,29 @@ __global__ __launch_bounds__(kPfaBlock) void k_pfa_z_c2r(PfaAxis a, int nlines, 
 }
 
 // ---- host side
-// split of one axis; false: this length neither fits the plain lines nor has a usable coprime split
+// split of one axis (pfa_maps.h); ADMP_PFA_MIN: the longest axis left to the plain lines (tests: 0 splits whatever it can)
 bool pfa_split(int N, PfaAxis* out) {
-  int p = largest_prime_factor(N), N2 = 1, m = N;
-  while (m % p == 0) { N2 *= p; m /= p; }
-  PfaAxis a;
-  a.N = N;
-  static const int plain_max = env_int("ADMP_PFA_MIN", 160);   // tests: 0 splits whatever it can
-  if (N <= plain_max || m == 1) { a.N1 = 1; a.N2 = N; }
-  else { a.N1 = m; a.N2 = N2; }
-  if (a.N2 > 160 || a.N1 > 32 || a.N2 < 2) return false;
-  *out = a;
-  return true;
+  static const int plain_max = env_int("ADMP_PFA_MIN", 160);
+  return pfa_split_at(N, plain_max, out);
 }
-void pfa_index_table(const PfaAxis& a, int* t) {      // t[n1 * N2 + n2] = position (low 16 bits) | n1 << 16
-  for (int n1 = 0; n1 < a.N1; ++n1)
-    for (int n2 = 0; n2 < a.N2; ++n2) t[n1 * a.N2 + n2] = pfa_pos(a, n1, n2) | (n1 << 16);
+// lines per block of the z passes: LDS = tw + Khp * NL complex + max(N reals, Khp complex) * NL
+static size_t pfa_z_bytes(const PfaAxis& a, int Khp, size_t w, int inverse, int NL) {
+  const size_t per_line = 2 * w * (size_t)Khp + (inverse ? 2 * w * (size_t)(Khp | 1) : w * (size_t)a.N);
+  return 2 * w * (size_t)(a.N1 + a.N2) + per_line * NL + sizeof(int) * (size_t)a.N;
 }
-void pfa_freq_of_slot(const PfaAxis& a, int* f) {      // f[slot] = the frequency stored there
-  for (int k1 = 0; k1 < a.N1; ++k1)
-    for (int k2 = 0; k2 < a.N2; ++k2) {
-      int k = k2;
-      while (k % a.N1 != k1) k += a.N2;               // CRT by search (N1 <= 32 steps)
-      f[pfa_pos(a, k1, k2)] = k;
-    }
+static int pfa_z_lines(const PfaAxis& a, int Khp, size_t w, int inverse) {
+  int NL = 16;        // 16 lines = the 16 data columns of an MFMA tile (one sub-line n1)
+  while (NL > 1 && pfa_z_bytes(a, Khp, w, inverse, NL) > pfa_lds_budget()) NL >>= 1;
+  return NL;
 }
-void pfa_freq_of_zcolumn(const PfaAxis& a, int* f) {   // f[cz] for the stored z half, cz = k2 * N1 + k1
-  const int Kh2 = a.N2 / 2 + 1;
-  for (int k2 = 0; k2 < Kh2; ++k2)
-    for (int k1 = 0; k1 < a.N1; ++k1) {
-      int k = k2;
-      while (k % a.N1 != k1) k += a.N2;
-      f[k2 * a.N1 + k1] = k;
-    }
+static bool pfa_z_mfma(const PfaAxis& a, int NL) { return NL == 16 && pfa_use_mfma(a, 8); }
+void pfa_forms(const PfaPlan& p, size_t w, int out[9]) {
+  for (int d = 0; d < 2; ++d) {
+    const int NC = pfa_cols(p.ax[d], w);
+    out[3 * d] = NC; out[3 * d + 1] = pfa_use_mfma(p.ax[d], NC) ? 1 : 0; out[3 * d + 2] = 0;
+  }
+  const int NLf = pfa_z_lines(p.ax[2], p.Khp, w, 0), NLi = pfa_z_lines(p.ax[2], p.Khp, w, 1);
+  out[6] = NLf; out[7] = (pfa_z_mfma(p.ax[2], NLf) ? 1 : 0) | (pfa_z_mfma(p.ax[2], NLi) ? 2 : 0); out[8] = NLi;
 }
 
 template <class T>
@@ -650,12 +638,9 @@ void launch_pfa_z(hipStream_t st, const PfaPlan& p, const T* tw, T* mesh, T* spe
   const int nlines = p.ax[0].N * p.ax[1].N, Khp = p.Khp;
   const Cx<T>* tw2 = reinterpret_cast<const Cx<T>*>(tw) + p.tw_off[2];
   const Cx<T>* tw1 = tw2 + a.N2;
-  // lines per block: LDS = tw + Khp * NL complex + max(N reals, Khp complex) * NL
-  const size_t per_line = sizeof(Cx<T>) * (size_t)Khp + (inverse ? sizeof(Cx<T>) * (size_t)(Khp | 1) : sizeof(T) * (size_t)a.N);
-  int NL = 16;        // 16 lines = the 16 data columns of an MFMA tile (one sub-line n1)
-  while (NL > 1 && sizeof(Cx<T>) * (size_t)(a.N1 + a.N2) + per_line * NL + sizeof(int) * (size_t)a.N > pfa_lds_budget()) NL >>= 1;
-  const int mf = (NL == 16 && pfa_use_mfma(a, 8)) ? 1 : 0;
-  const size_t sh = sizeof(Cx<T>) * (size_t)(a.N1 + a.N2) + per_line * NL + sizeof(int) * (size_t)a.N;
+  const int NL = pfa_z_lines(a, Khp, sizeof(T), inverse);
+  const int mf = pfa_z_mfma(a, NL) ? 1 : 0;
+  const size_t sh = pfa_z_bytes(a, Khp, sizeof(T), inverse, NL);
   const dim3 grid((nlines + NL - 1) / NL, nb);
   if (inverse)
     k_pfa_z_c2r<T><<<grid, kPfaBlock, sh, st>>>(a, nlines, NL, mf, reinterpret_cast<const Cx<T>*>(spec), mesh, tw2, tw1, p.ptab[2], mesh_stride, spec_stride / 2);

@@ -644,6 +644,10 @@ __global__ __launch_bounds__(256) void k_spread_planes(int na, const Site<T>* __
 // (0,1,2)"; for unequal meshes it also scrambles (j,k).  The resulting factor is not symmetric under k -> -k, which
 // the half spectrum needs; since |S(-k)| = |S(k)| for a real mesh, the energy and all its derivatives only see the
 // symmetrised factor (G(t) + G(-t)) / 2, which is what is stored.
+__device__ inline bool nyquist_index(int i0, int i1, int i2, int K0, int K1, int K2) {
+  return 2 * i0 == K0 || 2 * i1 == K1 || 2 * i2 == K2;
+}
+
 __device__ inline double gfactor_at(int i0, int i1, int i2, int K0, int K1, int K2, const double* __restrict__ binv,
                                     double volume, double kappa, int which, int ref_order) {
   int m0, m1, m2;
@@ -677,8 +681,12 @@ __global__ void k_gtab(int K0, int K1, int K2, int y0, int ny, const double* __r
     int i0 = (int)(t / ((long)nh * ny));
     if (fmap) { i0 = fmap[i0]; i1 = fmap[K0 + i1]; i2 = fmap[K0 + K1 + i2]; }   // slot -> frequency (pfa_kernels.hip)
     double G = gfactor_at(i0, i1, i2, K0, K1, K2, binv, volume, kappa, which, ref_order);
-    if (ref_order)
-      G = 0.5 * (G + gfactor_at((K0 - i0) % K0, (K1 - i1) % K1, (K2 - i2) % K2, K0, K1, K2, binv, volume, kappa, which, 1));
+    // An index at its Nyquist value has one signed frequency, -K/2, for itself and for its mirror point, so in a triclinic
+    // cell G(k) != G(-k) there.  The reference's full-spectrum sum sees the mean of the two; a half spectrum gives both
+    // the stored one's, and which of the two is stored differs between the layouts (kz <= K3/2, two-level z columns).
+    // Store the mean: every layout then computes the reference's sum.  (Orthorhombic cells: both are equal, bit for bit.)
+    if (ref_order || nyquist_index(i0, i1, i2, K0, K1, K2))
+      G = 0.5 * (G + gfactor_at((K0 - i0) % K0, (K1 - i1) % K1, (K2 - i2) % K2, K0, K1, K2, binv, volume, kappa, which, ref_order));
     gtab[t] = (T)G;
   }
 }
@@ -728,11 +736,12 @@ __global__ __launch_bounds__(256) void k_kspace_virial(int K0, int K1, int K2, c
     const double w = ((i2 == 0 || ((K2 & 1) == 0 && i2 == K2 / 2)) ? 0.5 : 1.0) * (re * re + im * im);
     double kv[3];
     double gp = gprime_at(i0, i1, i2, K0, K1, K2, binv, volume, kappa, which, ref_order, kv);
-    double f = ref_order ? 0.5 * w * gp : w * gp;
+    const bool mean = ref_order || nyquist_index(i0, i1, i2, K0, K1, K2);
+    double f = mean ? 0.5 * w * gp : w * gp;
     acc[0] += f * kv[0] * kv[0]; acc[1] += f * kv[1] * kv[1]; acc[2] += f * kv[2] * kv[2];
     acc[3] += f * kv[0] * kv[1]; acc[4] += f * kv[0] * kv[2]; acc[5] += f * kv[1] * kv[2];
-    if (ref_order) {   // the stored factor is the average over t and its mirror point (k_gtab)
-      gp = gprime_at((K0 - i0) % K0, (K1 - i1) % K1, (K2 - i2) % K2, K0, K1, K2, binv, volume, kappa, which, 1, kv);
+    if (mean) {   // the stored factor is the average over t and its mirror point (k_gtab)
+      gp = gprime_at((K0 - i0) % K0, (K1 - i1) % K1, (K2 - i2) % K2, K0, K1, K2, binv, volume, kappa, which, ref_order, kv);
       f = 0.5 * w * gp;
       acc[0] += f * kv[0] * kv[0]; acc[1] += f * kv[1] * kv[1]; acc[2] += f * kv[2] * kv[2];
       acc[3] += f * kv[0] * kv[1]; acc[4] += f * kv[0] * kv[2]; acc[5] += f * kv[1] * kv[2];

@@ -60,7 +60,8 @@ int admp_synchronize(admp_handle* h);
 int admp_set_topology(admp_handle* h, int n_atoms, const int32_t* axis_type, const int32_t* axis_idx,
                       const int32_t* excl_rowptr, const int32_t* excl_col, const int32_t* excl_nbonds);
 
-/* replaces: the kappa / K1..K3 / lmax / lpol environment (admp/pme.py:42-50, update_env :89-94) */
+/* replaces: the kappa / K1..K3 / lmax / lpol environment (admp/pme.py:42-50, update_env :89-94).  Meshes below 6 points per
+ * dimension are accepted here for admp_mesh_convolve alone: every call that spreads or gathers (order-6 splines) refuses them. */
 int admp_set_ewald(admp_handle* h, double kappa, int K1, int K2, int K3, int lmax, int lpol);
 
 /* behaviour switches that are not part of the reference's argument lists */
@@ -361,6 +362,26 @@ int admp_scf_stats(admp_handle* h, int64_t* out8, int reset);
 /* Which form the x passes of the direct-DFT mesh convolution took: out2 = {one real circulant product per line (G table
  * even along x: orthorhombic cells; ADMP_DFT_XCIRC=0 turns it off), forward transform * G * inverse transform}. */
 int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset);
+/* The k-space leg of a reciprocal pass alone, on a mesh of the caller's (admp/recip.py:400-426):
+ *     mesh <- IFFT( G * FFT(mesh) ) (unnormalised: N times numpy's ifftn),   *E_out = 1/2 sum_k G(k) |FFT(mesh)(k)|^2
+ * with G the handle's own table for `box`: which = 1: 2 DIELECTRIC Ck_1 / theta_k^2, gamma point zero; which = 6, 8, 10:
+ * 2 Ck_n / theta_k^2 with the gamma point.  It runs what an evaluation runs between its spread and its gather -- the same
+ * transform path (rocFFT, fused x, direct-DFT lines or planes, two-level), the same G table, the same kernels -- in place on
+ * K1 K2 K3 words of the handle's type, on the device (on_device != 0) or on the host.  Needs admp_set_ewald only (no
+ * topology, no pairs; meshes down to 2 points per dimension); single rank: a slab-decomposed handle returns ADMP_E_ARG.
+ * info16 says which form ran:
+ *   [0] path (ADMP_MESH_PATH_*)       [1] direct paths: x pass as 1 = one circulant product, 2 = two transforms (else 0)
+ *   two-level path, per axis d = x, y, z:  [2+d] N1   [5+d] N2   [12+d] MFMA stage A (z: bit 0 forward, bit 1 inverse pass)
+ *   [8] [9] columns per workgroup (NC) of the x and y passes   [10] [11] lines per workgroup (NL) of the forward / inverse z pass
+ *   [15] 0 */
+#define ADMP_MESH_INFO_WORDS 16
+#define ADMP_MESH_PATH_ROCFFT 0        /* rocFFT 3-D r2c, G kernel, c2r */
+#define ADMP_MESH_PATH_FUSED_X 1       /* rocFFT y-z planes around the fused x pass (fftx_kernels.hip) */
+#define ADMP_MESH_PATH_DIRECT_LINES 2  /* direct DFT, z, y and x lines as separate passes (dft_kernels.hip) */
+#define ADMP_MESH_PATH_DIRECT_PLANES 3 /* direct DFT, plane kernels for z and y */
+#define ADMP_MESH_PATH_TWO_LEVEL 4     /* Good-Thomas split (pfa_kernels.hip) */
+int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
+                       int32_t* info16);
 /* Where the closing pair kernel of the polarizable calls ran: out2 = {inside the x pass of a mesh convolution (small
  * double-precision systems on the direct-DFT mesh, one stream; ADMP_PAIR_RIDER=0 turns it off), in a launch of its own}. */
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset);
