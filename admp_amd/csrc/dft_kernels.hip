@@ -705,25 +705,16 @@ void launch_dft_y(hipStream_t st, const int K[3], const T* tw, T* spec, int inve
 template <class T>
 void launch_dft_x_conv(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
                        int slot, int nb, long spec_stride) {
-  const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
-  const int NC = dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
-  const size_t sh = sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
-  const dim3 grid((Kh + NC - 1) / NC, K[1], nb);
-  const XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
-                        reinterpret_cast<const Cx<T>*>(tw), energies, slot, spec_stride / 2};
-  KQ_SWITCH((k_dft_x_conv<T, KQ, JS><<<grid, kDftBlock, sh, st>>>(xa)))
+  const XPassPlan p = dft_x_plan(K, sizeof(T), false);
+  const XConvArgs<T> xa = dft_x_args<T>(p, K, tw, spec, tabs, energies, slot, nullptr, spec_stride);
+  KQ_SWITCH((k_dft_x_conv<T, KQ, JS><<<dim3(p.nbx, K[1], nb), kDftBlock, p.lds, st>>>(xa)))
 }
 // the circulant form of the x pass of ONE mesh (ctab from launch_ctab) and its table
 template <class T>
 void launch_dft_x_circ(hipStream_t st, const int K[3], T* spec, const T* ctab, double* energies, int slot) {
-  const int N = K[0], Kh = K[2] / 2 + 1, TK = dft_tasks(N, dft_kq());
-  const int NC = dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0);
-  const size_t sh = dft_x_circ_col_bytes<T>(N) * (size_t)NC;
-  const dim3 grid((Kh + NC - 1) / NC, K[1], 1);
-  XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), DftTabs<T>(), nullptr,
-                  energies, slot, 0};
-  xa.ctab = ctab;
-  k_dft_x_circ<T, 2><<<grid, kDftBlock, sh, st>>>(xa);
+  const XPassPlan p = dft_x_plan(K, sizeof(T), true);
+  const XConvArgs<T> xa = dft_x_args<T>(p, K, nullptr, spec, DftTabs<T>(), energies, slot, ctab);
+  k_dft_x_circ<T, 2><<<dim3(p.nbx, K[1], 1), kDftBlock, p.lds, st>>>(xa);
 }
 template <class T>
 void launch_ctab(hipStream_t st, const int K[3], const T* gtab, T* ctab, int* uneven) {
@@ -734,13 +725,14 @@ void launch_ctab(hipStream_t st, const int K[3], const T* gtab, T* ctab, int* un
 template <class T>
 void launch_dft_x_mix(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, const MixTab& mix,
                       long spec_stride, double* energies, int slot) {
-  const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
+  const XPassPlan p = dft_x_plan(K, sizeof(T), false);      // (the transform form's bytes per column; NC a multiple of the types)
+  const int N = p.N, Kh = p.Kh, TK = p.TK;
   const int ntp = mix.nt <= 1 ? 1 : (mix.nt == 2 ? 2 : 4);
-  int NC = dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
+  int NC = p.NC;
   NC -= NC % ntp;
   if (NC < ntp) NC = ntp;
   const int NCt = NC / ntp;
-  const size_t sh = sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
+  const size_t sh = dft_x_fixed_bytes(N, sizeof(T), false) + dft_x_col_bytes(N, sizeof(T), false) * (size_t)NC;
   const dim3 grid((Kh + NCt - 1) / NCt, K[1], 1);
 #define XMIX(NTP)                                                                                                          \
   k_dft_x_mix<T, 2, 1, NTP><<<grid, kDftBlock, sh, st>>>(N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2],                    \

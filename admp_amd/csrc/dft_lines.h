@@ -1,33 +1,14 @@
 // Pieces of the direct-DFT line kernels shared between dft_kernels.hip and the kernels that run an x pass next to other
-// work (pair_kernels.hip k_xconv_pair): block size, task helpers, the pair-sum loader and the body of the x pass.
+// work (pair_kernels.hip k_xconv_pair): task helpers, the pair-sum loader and the body of the x pass (block size and launch
+// shape: dft_plan.h).
 #pragma once
 #include "dft_math.h"
+#include "dft_plan.h"
 #include "launch.h"
 #include "reduce.h"
 #include "rider_layout.h"
 
 namespace admp {
-
-#ifndef ADMP_DFT_BLOCK
-#define ADMP_DFT_BLOCK 256
-#endif
-constexpr int kDftBlock = ADMP_DFT_BLOCK;
-constexpr size_t kDftLdsBudget = 60 * 1024;
-
-// Two output pairs per thread (they share one read of the pair sums), one thread per output set.  Round 2 measured the
-// alternatives on the 97^3 f64 mesh and dropped them (variants in the history): 1 or 4 output pairs per thread, and two
-// lanes per output set (each summing half of the pair positions: x pass 36.8 -> 44.4 us) -- more, thinner threads do not
-// help these latency-bound passes.  The kernels keep the two template parameters; one instantiation is compiled.
-static inline int dft_kq() { return 2; }
-static inline int dft_js() { return 1; }
-// thread-tasks per line and lines (columns) per block
-static inline int dft_tasks(int N, int KQ) { return (N / 2 + 1 + KQ - 1) / KQ; }
-static inline int dft_cols(int N, int KQ, size_t bytes_per_col, size_t fixed_bytes) {
-  int nc = (kDftBlock / dft_js()) / dft_tasks(N, KQ);
-  if (nc < 1) nc = 1;
-  while (nc > 1 && fixed_bytes + bytes_per_col * nc > kDftLdsBudget) --nc;
-  return nc;
-}
 
 extern __shared__ __align__(32) unsigned char dft_smem[];
 
@@ -113,6 +94,17 @@ struct XConvArgs {
   long spec_stride;
   const T* ctab = nullptr;      // circulant form (dft_x_circ_body): first columns [N/2+1][K2][K3/2+1] of the slot-0 G table
 };
+// the arguments of an x pass of shape p (dft_plan.h: dft_x_plan(K, sizeof(T), ctab != nullptr)) over the spectrum of mesh K;
+// spec_stride: reals between the spectra of a batch (the transform form only)
+template <class T>
+inline XConvArgs<T> dft_x_args(const XPassPlan& p, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
+                               int slot, const T* ctab = nullptr, long spec_stride = 0) {
+  static_assert(sizeof(Cx<T>) == 2 * sizeof(T) && sizeof(PairCx<T>) == 4 * sizeof(T), "dft_plan.h counts LDS in words");
+  XConvArgs<T> xa{p.N, p.Kh, p.NC, p.TK, (long)K[1] * p.Kh, (long)p.Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
+                  reinterpret_cast<const Cx<T>*>(tw), energies, slot, spec_stride / 2};
+  xa.ctab = ctab;
+  return xa;
+}
 template <class T, int KQ, int JS>
 __device__ __forceinline__ void dft_x_conv_body(const XConvArgs<T>& xa, int bx, int by, int bz) {
   const int N = xa.N, ncols = xa.ncols, NC = xa.NC, TK = xa.TK, K3 = xa.K3, slot = xa.slot;
@@ -230,10 +222,6 @@ __device__ __forceinline__ void dft_x_conv_body(const XConvArgs<T>& xa, int bx, 
 // energy word as dft_x_conv_body, for G tables that are even along x (xa.ctab: built and checked by k_ctab, dft_kernels.hip).
 // One loop over the pair positions, one barrier; LDS: the pair sums and the tile's extended table [circ_ext_len][NC].
 // The energy sum is skipped for slot E_SCRATCH (convolutions whose energy nobody reads: the SCF increments).
-template <class T>
-inline size_t dft_x_circ_col_bytes(int N) {
-  return sizeof(PairCx<T>) * (size_t)((N - 1) / 2) + 2 * sizeof(Cx<T>) + sizeof(T) * (size_t)circ_ext_len(N);
-}
 template <class T, int KQ>
 __device__ __forceinline__ void dft_x_circ_body(const XConvArgs<T>& xa, int bx, int by) {
   const bool ENERGY = xa.slot != E_SCRATCH;      // (workgroup-uniform)

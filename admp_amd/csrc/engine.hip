@@ -1042,7 +1042,7 @@ struct Engine : EngineBase {
     return lpol && side_stream_on && rider_ok() && env_flag("ADMP_PAIR_RIDER", true);
   }
   bool convolve(T* mesh_p, T* spec_p, const T* gtab, int slot, T* accum = nullptr, T* out = nullptr,
-                const PlaneSpread<T>* sp = nullptr, const FieldRider<T>* rider = nullptr, const FullRider<T>* prider = nullptr) {
+                const PlaneSpread<T>* sp = nullptr, const PairFieldArgs<T>* rider = nullptr, const PairFullArgs<T>* prider = nullptr) {
     double* Ed = Ed_cur();
     T* mesh_o = out ? out : mesh_p;
     ARG_CHECK(!sp || (use_dft && !use_pfa && snranks == 1), "internal: plane spread on a transform path without it");
@@ -1105,13 +1105,7 @@ struct Engine : EngineBase {
       // G table of slot 0 even along x (every orthorhombic cell): one circulant product per line instead of two transforms
       const T* ct = xctab_ok && gtab == gtabs[0].template as<T>() ? xctab.template as<T>() : nullptr;
       ++xpass_stats[ct ? 0 : 1];
-      if (prider && prider->on) {
-        TIMED("dft_x_kspace");
-        launch_dft_x_conv_full_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *prider, rider && rider->kind == 2 ? rider : nullptr, ct);
-      }
-      else if (rider && rider->kind) { TIMED("dft_x_kspace"); launch_dft_x_conv_rider<T>(stream, K, tw, spec_p, tabs, Ed, slot, *rider, ct); }
-      else if (ct) { TIMED("dft_x_kspace"); launch_dft_x_circ<T>(stream, K, spec_p, ct, Ed, slot); }
-      else { TIMED("dft_x_kspace"); launch_dft_x_conv<T>(stream, K, tw, spec_p, tabs, Ed, slot); }
+      { TIMED("dft_x_kspace"); launch_dft_x_pass<T>(stream, K, tw, spec_p, tabs, Ed, slot, ct, rider, prider); }
       bool added;
       if (planes) { TIMED("dft_yz_inv"); added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum); }
       else {
@@ -1568,35 +1562,41 @@ struct Engine : EngineBase {
     side_busy = false;
   }
 
+  // the closing pair kernel of this evaluation: its argument record, and what precedes its launch in either form
+  PairFullArgs<T> pair_full_args(T* grad_p, T* fld_out) {
+    const NbrTable& nb = wnbr();
+    PairFullArgs<T> a;
+    a.on = 1; a.na = ev.n_home; a.rowptr = nb.rowptr; a.rowend = nb.rowend; a.col = nb.col; a.sites = sites.as<Site<T>>();
+    a.box = ev.bx; a.tab = ev.tab; a.kappa = (T)kappa; a.grad = grad_p; a.pot = pot.as<T>(); a.energies = Ed_cur();
+    a.rows = pair_rows(); a.fld = fld_out; a.use_mono = mono_ok ? 1 : 0; a.cls_flags = cls_flags_dev();
+    a.rq = rq_d.as<RQ4<T>>(); a.tholes = ev.thole;
+    return a;
+  }
+  void pair_full_prologue() {
+    check_mono_inputs(mono_ok);
+    if (!slot_clean[E_REAL]) {
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_REAL, 0, sizeof(double), stream));
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_RPARTS, 0, E_PARTS * sizeof(double), stream));
+    }
+    slot_clean[E_REAL] = false;
+  }
   void stage_pair_full(T* grad_p, T* fld_out = nullptr) {
     need_eval();
     if (snranks > 1)   // the closing kernel ADDS frame-adjoint contributions to atoms of other ranks: those rows start at zero
       launch_rows_scatter<T>(stream, 2, sl.n_imp, 3, sl.imp.as<int>(), nullptr, grad_p);
-    if (!slot_clean[E_REAL]) {
-      HIP_TRY(hipMemsetAsync(Ed_cur() + E_REAL, 0, sizeof(double), stream));
-      HIP_TRY(hipMemsetAsync(Ed_cur() + E_RPARTS, 0, E_PARTS * sizeof(double), stream));
-    }
-    slot_clean[E_REAL] = false;
-    check_mono_inputs(mono_ok);
+    pair_full_prologue();
     if (lpol) ++pair_rider_stats[1];
     TIMED("pair_full");
-    launch_pair_full<T>(stream, ev.n_home, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(),
-                        Ed_cur(), pair_rows(), fld_out, mono_ok ? 1 : 0, cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole);
+    launch_pair_full<T>(stream, pair_full_args(grad_p, fld_out), lpol);
   }
   // stage_pair_full as a rider of the next x pass: everything but the launch (the energy words are cleared here, ahead of
-  // the fused launch); false = it cannot ride, nothing was done and the caller takes stage_pair_full
-  bool pair_full_rider(FullRider<T>& pr, T* grad_p, T* fld_out = nullptr) {
+  // the fused launch); false = it cannot ride, nothing was done and the caller takes stage_pair_full.  Riders are single-rank.
+  bool pair_full_rider(PairFullArgs<T>& pr, T* grad_p, T* fld_out = nullptr) {
     if (!pair_rider_ok()) return false;
     need_eval();
-    check_mono_inputs(mono_ok);
-    if (!full_rider<T>(pr, ev.n_home, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, lpol, grad_p, pot.as<T>(), Ed_cur(),
-                       pair_rows(), fld_out, mono_ok ? 1 : 0, cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole))
-      return false;
-    if (!slot_clean[E_REAL]) {
-      HIP_TRY(hipMemsetAsync(Ed_cur() + E_REAL, 0, sizeof(double), stream));
-      HIP_TRY(hipMemsetAsync(Ed_cur() + E_RPARTS, 0, E_PARTS * sizeof(double), stream));
-    }
-    slot_clean[E_REAL] = false;
+    pr = pair_full_args(grad_p, fld_out);
+    if (!full_rider<T>(pr, lpol)) return false;
+    pair_full_prologue();
     ++pair_rider_stats[0];
     return true;
   }
@@ -1690,11 +1690,32 @@ struct Engine : EngineBase {
     int rc = sort_ints(stream, act_d.as<int>(), act_tmp.as<int>(), n, &scan_scratch.p, &scan_bytes);
     if (rc != 0) throw Err{ADMP_E_HIP, std::string("sort_ints: ") + hipGetErrorString((hipError_t)rc)};
   }
-  void first_pair_field() {          // real-space dE/dU of the polarizable rows, all partners
-    check_mono_inputs(true);         // (the flag word handed over below switches the charge-only form on)
+  // the SCF field kernels over the polarizable rows: real-space dE/dU from all partners (k_pair_field), and its increment
+  // from the last Jacobi step of the polarizable partners (k_pair_field_ind, over the current sub-table)
+  PairFieldArgs<T> pair_field_common(int kind, int n_rows) {
+    PairFieldArgs<T> a;
+    a.kind = kind; a.na = n_rows; a.sites = sites.as<Site<T>>(); a.box = ev.bx; a.tab = ev.tab; a.kappa = (T)kappa;
+    a.fld = fld_pair.as<T>(); a.rows = act_list();
+    return a;
+  }
+  PairFieldArgs<T> pair_field_args() {      // (hands the flag word over: the charge-only form is on, see check_mono_inputs)
+    const NbrTable& nb = wnbr();
+    PairFieldArgs<T> a = pair_field_common(1, nact_rows());
+    a.rowptr = nb.rowptr; a.rowend = nb.rowend; a.col = nb.col;
+    a.n_dev = nact_arg(); a.cls_flags = cls_flags_dev(); a.rq = rq_d.as<RQ4<T>>(); a.tholes = ev.thole;
+    return a;
+  }
+  PairFieldArgs<T> pair_field_ind_args(int n_act) {
+    const IndTable& it = wind();
+    PairFieldArgs<T> a = pair_field_common(2, n_act);
+    a.rowptr = it.beg; a.rowend = it.end; a.col = it.col;
+    return a;
+  }
+  void first_pair_field() {
+    check_mono_inputs(true);
+    const PairFieldArgs<T> a = pair_field_args();
     TIMED("pair_field");
-    launch_pair_field<T>(stream, nact_rows(), wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
-                         act_list(), nact_arg(), cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole);
+    launch_pair_field<T>(stream, a);
   }
   void first_gather_field(const FieldFin<T>& ff) {   // reciprocal dE/dU of the polarizable rows from phi
     join_side();                     // (its epilogue reads the pair field)
@@ -1767,14 +1788,13 @@ struct Engine : EngineBase {
       return false;
     }
     const bool first = side_first();
-    FieldRider<T> fr;      // (filled below, once the sub-table is current: the field kernel then rides in the x pass)
+    PairFieldArgs<T> fr;   // (filled below, once the sub-table is current; it may ride in the x pass)
     bool ride = false;
     auto side_work = [&] {
       if (!ride)
         on_side([&] {
           TIMED("pair_field_ind");
-          launch_pair_field_ind<T>(stream, n_act, wind(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
-                                   act_list());
+          launch_pair_field_ind<T>(stream, fr);
         });
       if (extra_side) on_side(extra_side);
     };
@@ -1785,8 +1805,8 @@ struct Engine : EngineBase {
       if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
       ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
     }
-    ride = rider_ok() && field_rider_ind<T>(fr, n_act, wind(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(),
-                                            act_list());
+    fr = pair_field_ind_args(n_act);
+    ride = rider_ok() && field_rider<T>(fr);
     if (first) side_work();
     const size_t nreal = nreal_local();
     mesh2.need(nreal * sizeof(T));
@@ -1804,7 +1824,7 @@ struct Engine : EngineBase {
       if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)}; }
     if (!first && !fused) side_work();
     const PlaneSpread<T> sp = plane_spread(n_act, isites.as<Site<T>>(), 1, nullptr);
-    FullRider<T> pr;
+    PairFullArgs<T> pr;
     const bool full_rides = full_grad && pair_full_rider(pr, full_grad);
     const bool added = convolve(mesh2.as<T>(), spec.as<T>(), gtab_cur, E_SCRATCH, mesh.as<T>(), nullptr, fused ? &sp : nullptr,
                                 ride ? &fr : nullptr, full_rides ? &pr : nullptr);
@@ -1860,7 +1880,7 @@ struct Engine : EngineBase {
   // evaluation); behind the spread it is hidden by a running kernel and the side kernels still have the three transform
   // passes to hide behind (side_first()).
   template <class F>
-  void recip_pass(int slot, F&& side_work, const FieldRider<T>* rider = nullptr, const FullRider<T>* prider = nullptr) {
+  void recip_pass(int slot, F&& side_work, const PairFieldArgs<T>* rider = nullptr, const PairFullArgs<T>* prider = nullptr) {
     need_eval();
     const bool fused = spread_fused(ev.n_home);      // the forward transform spreads (dft_kernels.hip, zy_plane_spread)
     const bool first = side_first() || fused;
@@ -1875,7 +1895,7 @@ struct Engine : EngineBase {
   // reciprocal pass + closing pair kernel (gradient rows grad_p; fld_out: its dE/dU as well): in the x pass, or next to
   // the mesh chain on the side stream / ahead of it on this one
   void recip_pass_pair_full(int slot, T* grad_p, T* fld_out = nullptr) {
-    FullRider<T> pr;
+    PairFullArgs<T> pr;
     if (pair_full_rider(pr, grad_p, fld_out)) recip_pass(slot, [] {}, nullptr, &pr);
     else recip_pass(slot, [&] { on_side([&] { stage_pair_full(grad_p, fld_out); }); });
   }
@@ -1883,11 +1903,10 @@ struct Engine : EngineBase {
   // first field evaluation of a call: the mesh chain and the real-space field of all partners -- on the side stream, or (small
   // systems, one stream, direct-DFT mesh) with the field kernel's workgroups inside the x pass
   void recip_pass_first_field(int slot) {
-    FieldRider<T> fr;
     if (rider_ok()) {
       check_mono_inputs(true);
-      if (field_rider_full<T>(fr, nact_rows(), wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, (T)kappa, fld_pair.as<T>(), act_list(),
-                              nact_arg(), cls_flags_dev(), rq_d.as<RQ4<T>>(), ev.thole)) {
+      const PairFieldArgs<T> fr = pair_field_args();
+      if (field_rider<T>(fr)) {
         recip_pass(slot, [] {}, &fr);
         return;
       }

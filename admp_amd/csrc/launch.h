@@ -266,23 +266,7 @@ void launch_fftx_conv_batch(hipStream_t st, const int K[3], const T* tw, T* spec
                             int khp = 0, int ny = 0);
 
 // ---- pair_kernels.hip
-template <class T>
-void launch_pair_full(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                      const ScaleTab<T>& tab, T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows,
-                      T* fld /* optional: also write the real-space dE/dU (speculative SCF pass) */,
-                      int use_mono = 0 /* 1: charge-only sites take the reduced pair forms (pme_math.h); pot of such a
-                                          ROW then holds only its monopole component: not for dE/dQ_local requests */,
-                      const int* cls_flags = nullptr /* the flag word launch_prepare_sites wrote for THIS evaluation */,
-                      const RQ4<T>* rq = nullptr /* compact position/charge rows of launch_prepare_sites */,
-                      const T* tholes = nullptr /* the caller's per-atom thole array, or nullptr */);
-// n_dev (optional): the row count lives on the device (na is then the upper bound the grid is sized for)
-template <class T>
-void launch_pair_field(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                       const ScaleTab<T>& tab, T kappa, T* fld_pair, const int* rows, const int* n_dev = nullptr,
-                       const int* cls_flags = nullptr /* as launch_pair_full: charge-only partners take the short form */,
-                       const RQ4<T>* rq = nullptr, const T* tholes = nullptr);
-// incremental SCF: fld_pair[row] += sum_j T_ij dU_j over the polarizable partners, dU_j in the pad words of sites[j];
-// `it` = the polarizable-polarizable sub-table (rows keyed by atom), `rows` = the n_rows polarizable sites
+// incremental SCF: the polarizable-polarizable sub-table (rows keyed by atom) that k_pair_field_ind walks.
 // Row i holds its kept entries at col[beg[i] .. end[i]) with beg = the neighbour table's own row offsets (borrowed pointer):
 // the sub-table is written in ONE pass over the neighbour table -- no count pass, no prefix sum, no host read of the total
 // (round 4; the two-pass build cost 0.57 ms per list rebuild at 1M atoms plus a hipMalloc / hipFree pair).  col is as long
@@ -294,13 +278,36 @@ struct IndTable {
   int64_t cap = 0;            // entries col can hold
   int na_cap = 0;             // rows `end` can hold
 };
+// The argument record of the closing pair kernel, in a launch of its own (launch_pair_full) or as a rider of the x pass of a
+// direct-DFT convolution (k_xconv_pair_full, through launch_dft_x_pass).  The caller fills everything but nblocks / grid,
+// which the launcher sets for the lane count it picks; on == 0: absent.
 template <class T>
-void launch_pair_field_ind(hipStream_t st, int n_rows, const IndTable& it, const Site<T>* sites, const Box<T>& box,
-                           const ScaleTab<T>& tab, T kappa, T* fld_pair, const int* rows);
-// An SCF field kernel riding in the x pass of a direct-DFT convolution (pair_kernels.hip k_xconv_pair): kind 1 = k_pair_field
-// (rowptr / col of the neighbour table), 2 = k_pair_field_ind (rowptr / rowend / col of the polarizable sub-table)
+struct PairFullArgs {
+  int on = 0, na = 0;           // na: the rows of this launch
+  const int* rowptr = nullptr;  // the neighbour table; rowend != nullptr: an evaluation's inner table (NbrTable::rowend)
+  const int* rowend = nullptr;
+  const int* col = nullptr;
+  const Site<T>* sites = nullptr;
+  Box<T> box;
+  ScaleTab<T> tab;
+  T kappa = 0;
+  T* grad = nullptr;
+  T* pot = nullptr;
+  double* energies = nullptr;
+  const int* rows = nullptr;
+  T* fld = nullptr;             // optional: also write the real-space dE/dU (speculative SCF pass)
+  unsigned nblocks = 0, grid = 0;
+  int use_mono = 0;             // 1: charge-only sites take the reduced forms (pme_math.h): not for dE/dQ_local requests
+  const int* cls_flags = nullptr;   // the flag word launch_prepare_sites wrote for THIS evaluation
+  const RQ4<T>* rq = nullptr;       // compact position/charge rows of launch_prepare_sites
+  const T* tholes = nullptr;        // the caller's per-atom thole array, or nullptr
+};
+// The argument record of the SCF field kernels, on their own or as riders of an x pass (k_xconv_pair, k_xconv_pair_full).
+// kind 1 = k_pair_field: the neighbour table, cls_flags / rq / tholes as in PairFullArgs, n_dev (optional): the row count
+// lives on the device and na is the bound the grid is sized for.  kind 2 = k_pair_field_ind: fld[row] += sum_j T_ij dU_j,
+// dU_j in the pad words of sites[j]; rowptr / rowend / col = the IndTable's beg / end / col.  kind 0: absent.
 template <class T>
-struct FieldRider {
+struct PairFieldArgs {
   int kind = 0, na = 0;
   const int* rowptr = nullptr;
   const int* rowend = nullptr;
@@ -318,47 +325,23 @@ struct FieldRider {
   const T* tholes = nullptr;
 };
 template <class T>
-bool field_rider_full(FieldRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                      const ScaleTab<T>& tab, T kappa, T* fld, const int* rows, const int* n_dev, const int* cls_flags,
-                      const RQ4<T>* rq, const T* tholes);
+void launch_pair_full(hipStream_t st, PairFullArgs<T> a, int lpol);
 template <class T>
-bool field_rider_ind(FieldRider<T>& r, int n_rows, const IndTable& it, const Site<T>* sites, const Box<T>& box,
-                     const ScaleTab<T>& tab, T kappa, T* fld, const int* rows);
+void launch_pair_field(hipStream_t st, PairFieldArgs<T> a);       // kind 1
 template <class T>
-void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                             int slot, const FieldRider<T>& fr, const T* ctab = nullptr /* circulant form of the x pass */);
-// The closing pair kernel (k_pair_full, polarizable, double precision) riding in the x pass of a direct-DFT convolution
-// (pair_kernels.hip k_xconv_pair_full): launch_pair_full's arguments.  full_rider: false = this launch cannot ride (no rows,
-// another lane count or type than the rider kernel is compiled for) -- the caller then launches k_pair_full on its own.
+void launch_pair_field_ind(hipStream_t st, PairFieldArgs<T> a);   // kind 2
+// Can the kernel of this record ride in an x pass?  false: no rows, or another lane count (the closing kernel: another
+// type, or not polarizable) than the rider kernels are compiled for -- the caller then launches it on its own.
 template <class T>
-struct FullRider {
-  int on = 0, na = 0;
-  const int* rowptr = nullptr;
-  const int* rowend = nullptr;
-  const int* col = nullptr;
-  const Site<T>* sites = nullptr;
-  Box<T> box;
-  ScaleTab<T> tab;
-  T kappa = 0;
-  T* grad = nullptr;
-  T* pot = nullptr;
-  double* energies = nullptr;
-  const int* rows = nullptr;
-  T* fld = nullptr;
-  unsigned nblocks = 0, grid = 0;
-  int use_mono = 0;
-  const int* cls_flags = nullptr;
-  const RQ4<T>* rq = nullptr;
-  const T* tholes = nullptr;
-};
+bool full_rider(const PairFullArgs<T>& a, int lpol);
 template <class T>
-bool full_rider(FullRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box, const ScaleTab<T>& tab,
-                T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows, T* fld, int use_mono,
-                const int* cls_flags, const RQ4<T>* rq, const T* tholes);
-// x pass + closing pair kernel (+ the field-increment kernel: fr of kind 2, or nullptr) in one launch
+bool field_rider(const PairFieldArgs<T>& a);
+// The x pass of the direct-DFT convolution of one mesh, with or without riders: k_dft_x_circ (ctab != nullptr: the circulant
+// form, launch_ctab; tw and tabs are then unused) or k_dft_x_conv on their own; with a field rider k_xconv_pair; with the
+// closing pair kernel k_xconv_pair_full, which takes a field rider of kind 2 along.  Absent riders: nullptr or on / kind 0.
 template <class T>
-void launch_dft_x_conv_full_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                                  int slot, const FullRider<T>& pr, const FieldRider<T>* fr, const T* ctab);
+void launch_dft_x_pass(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies, int slot,
+                       const T* ctab, const PairFieldArgs<T>* field, const PairFullArgs<T>* full);
 // (nbr_kernels.hip) inner table of an MD loop: the entries of `full` whose minimum-image distance is below rc, rows compacted
 // in the order of `full`.  hipError_t as int; one host synchronisation (the entry count).
 template <class T>

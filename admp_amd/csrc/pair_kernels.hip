@@ -178,6 +178,8 @@ __device__ __forceinline__ void pair_full_block(unsigned bid, int na, const int*
   e = block_reduce_sum<kFullBlock>(e);
   if (threadIdx.x == 0) atomicAdd(&energies[E_RPARTS + (bid & (E_PARTS - 1))], 0.5 * e);
 }
+// (the three kernels keep their parameter lists, which their launchers fill from the records of launch.h: the machine code is
+// then the same as before the records; by value, the SGPR spills of the one-lane-per-row f64 instances of this one grow)
 template <class T, bool LPOL, int LPR, int MINW, bool CUT>
 __global__ __launch_bounds__(kFullBlock, MINW) void k_pair_full(int na, const int* __restrict__ rowptr,
                                                           const int* __restrict__ rowend, const int* __restrict__ col,
@@ -302,6 +304,10 @@ __device__ __forceinline__ void pair_field_ind_block(unsigned bid, int na, const
   if (row >= 0 && sub == 0) { fld[3 * row] += F[0]; fld[3 * row + 1] += F[1]; fld[3 * row + 2] += F[2]; }
 }
 template <class T, int LPR>
+__device__ __forceinline__ void pair_field_ind_block(unsigned bid, const PairFieldArgs<T>& a) {
+  pair_field_ind_block<T, LPR>(bid, a.na, a.rowptr, a.rowend, a.col, a.sites, a.box, a.tab, a.kappa, a.fld, a.rows);
+}
+template <class T, int LPR>
 __global__ __launch_bounds__(kPairBlock) void k_pair_field_ind(int na, const int* __restrict__ irow,
                                                                const int* __restrict__ iend,
                                                                const int* __restrict__ icol,
@@ -320,7 +326,7 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_field_ind(int na, const int
 // (CUT: kind 1 walks an inner table, see k_pair_full; kind 2 takes its row ends from the sub-table in either case)
 // (CIRC: the x-pass tiles run the circulant form, dft_x_circ_body)
 template <class T, int LPR, bool CUT, bool CIRC>
-__global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, FieldRider<T> fr, int nbx) {
+__global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, PairFieldArgs<T> fr, int nbx) {
   static_assert(kPairBlock == kDftBlock, "the two kinds of workgroups share one launch");
   if ((int)blockIdx.x < nbx) {
     if (CIRC) dft_x_circ_body<T, 2>(xa, blockIdx.x, blockIdx.y);
@@ -331,9 +337,8 @@ __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, Fiel
   if (bid >= fr.grid) return;                          // workgroup-uniform
   if (fr.kind == 1)
     pair_field_block<T, LPR, CUT>(bid, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows, fr.nblocks,
-                             fr.n_dev, fr.cls_flags, fr.rq, fr.tholes);
-  else
-    pair_field_ind_block<T, LPR>(bid, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows);
+                                  fr.n_dev, fr.cls_flags, fr.rq, fr.tholes);
+  else pair_field_ind_block<T, LPR>(bid, fr);
 }
 
 // ---- the closing pair kernel riding in the x pass (small systems on one stream) ------------------------------------------------
@@ -346,7 +351,7 @@ __global__ __launch_bounds__(kPairBlock) void k_xconv_pair(XConvArgs<T> xa, Fiel
 // Measured at 3072 atoms on the 97^3 mesh: 22.0 us against 19.1 (x pass) + 13.9 (k_pair_full) in a row.  A raised wave
 // priority for the tile workgroups (s_setprio 2) changed neither the launch (22.0 us) nor the step time: not kept.
 template <class T, int LPR, bool CUT, bool CIRC>
-__global__ __launch_bounds__(kPairBlock, 2) void k_xconv_pair_full(XConvArgs<T> xa, FullRider<T> pr, FieldRider<T> fr, RiderGrid rg) {
+__global__ __launch_bounds__(kPairBlock, 2) void k_xconv_pair_full(XConvArgs<T> xa, PairFullArgs<T> pr, PairFieldArgs<T> fr, RiderGrid rg) {
   static_assert(kPairBlock == kDftBlock && kFullBlock == kDftBlock, "the kinds of workgroups share one launch");
   const RiderBlock b = rider_block(rg, blockIdx.x, blockIdx.y, gridDim.x);      // (workgroup-uniform)
   if (b.kind == RIDER_TILE) {
@@ -356,7 +361,7 @@ __global__ __launch_bounds__(kPairBlock, 2) void k_xconv_pair_full(XConvArgs<T> 
     pair_full_block<T, true, LPR, CUT, true>(b.rank, pr.na, pr.rowptr, pr.rowend, pr.col, pr.sites, pr.box, pr.tab, pr.kappa, pr.grad, pr.pot,
                                              pr.energies, pr.rows, pr.fld, pr.nblocks, pr.use_mono, pr.cls_flags, pr.rq, pr.tholes);
   } else if (b.kind == RIDER_IND) {
-    pair_field_ind_block<T, LPR>(b.rank, fr.na, fr.rowptr, fr.rowend, fr.col, fr.sites, fr.box, fr.tab, fr.kappa, fr.fld, fr.rows);
+    pair_field_ind_block<T, LPR>(b.rank, fr);
   }
 }
 
@@ -833,22 +838,32 @@ static inline unsigned grid_full(int na, int lpr) { return (unsigned)(((long)na 
     default: CALL(8); break;       \
   }
 
+// A filled record is finished for the lane count: grid words, charge-only forms off without their inputs (either form).
 template <class T>
-void launch_pair_full(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                      const ScaleTab<T>& tab, T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows,
-                      T* fld, int use_mono, const int* cls_flags, const RQ4<T>* rq, const T* tholes) {
-  if (na <= 0) return;
-  const int lpr = pair_lanes_per_row(na);
+static void finish_args(PairFullArgs<T>& a, int lpr) {
+  if (pair_mono_off() || !a.cls_flags || !a.rq) a.use_mono = 0;
+  a.nblocks = grid_full(a.na, lpr); a.grid = xcd_grid(a.nblocks);
+}
+template <class T>
+static void finish_args(PairFieldArgs<T>& a, int lpr) {
+  if (pair_mono_off() || !a.rq) a.cls_flags = nullptr;
+  a.nblocks = grid_for(a.na, lpr); a.grid = xcd_grid(a.nblocks);
+}
+
+template <class T>
+void launch_pair_full(hipStream_t st, PairFullArgs<T> a, int lpol) {
+  if (a.na <= 0) return;
+  const int lpr = pair_lanes_per_row(a.na);
   const int minw = pair_min_waves<T>();
-  if (pair_mono_off() || !cls_flags || !rq) use_mono = 0;
+  finish_args(a, lpr);
 #define FULL(LP, L, MW, CUT)                                                                                           \
-  k_pair_full<T, LP, L, MW, CUT><<<xcd_grid(grid_full(na, L)), kFullBlock, 0, st>>>(                                    \
-      na, nb.rowptr, nb.rowend, nb.col, sites, box, tab, kappa, grad, pot, energies, rows, fld, grid_full(na, L),      \
-      use_mono, cls_flags, rq, tholes)
+  k_pair_full<T, LP, L, MW, CUT><<<a.grid, kFullBlock, 0, st>>>(a.na, a.rowptr, a.rowend, a.col, a.sites, a.box, a.tab, a.kappa, a.grad, \
+                                                                a.pot, a.energies, a.rows, a.fld, a.nblocks, a.use_mono,    \
+                                                                a.cls_flags, a.rq, a.tholes)
 #define CALL(L)                                                                                                        \
-  if (lpol && minw >= 2) { if (nb.rowend) FULL(true, L, 2, true); else FULL(true, L, 2, false); }                      \
-  else if (lpol) { if (nb.rowend) FULL(true, L, 1, true); else FULL(true, L, 1, false); }                              \
-  else if (nb.rowend) FULL(false, L, 2, true);                                                                         \
+  if (lpol && minw >= 2) { if (a.rowend) FULL(true, L, 2, true); else FULL(true, L, 2, false); }                       \
+  else if (lpol) { if (a.rowend) FULL(true, L, 1, true); else FULL(true, L, 1, false); }                               \
+  else if (a.rowend) FULL(false, L, 2, true);                                                                          \
   else FULL(false, L, 2, false)
   ADMP_LPR_SWITCH(lpr, CALL)
 #undef CALL
@@ -856,121 +871,78 @@ void launch_pair_full(hipStream_t st, int na, const NbrTable& nb, const Site<T>*
 }
 
 template <class T>
-void launch_pair_field(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                       const ScaleTab<T>& tab, T kappa, T* fld, const int* rows, const int* n_dev, const int* cls_flags,
-                       const RQ4<T>* rq, const T* tholes) {
-  if (pair_mono_off() || !rq) cls_flags = nullptr;
-  if (na <= 0) return;
-  const int lpr = field_lanes_per_row(na, false);
-#define FIELD(L, CUT)                                                                                                  \
-  k_pair_field<T, L, CUT><<<xcd_grid(grid_for(na, L)), kPairBlock, 0, st>>>(na, nb.rowptr, nb.rowend, nb.col, sites, box, \
-                                                                            tab, kappa, fld, rows, grid_for(na, L), n_dev, \
-                                                                            cls_flags, rq, tholes)
-#define CALL(L) if (nb.rowend) FIELD(L, true); else FIELD(L, false)
+void launch_pair_field(hipStream_t st, PairFieldArgs<T> a) {
+  if (a.na <= 0) return;
+  const int lpr = field_lanes_per_row(a.na, false);
+  finish_args(a, lpr);
+#define FIELD(L, CUT)                                                                                                     \
+  k_pair_field<T, L, CUT><<<a.grid, kPairBlock, 0, st>>>(a.na, a.rowptr, a.rowend, a.col, a.sites, a.box, a.tab, a.kappa, a.fld, a.rows, \
+                                                         a.nblocks, a.n_dev, a.cls_flags, a.rq, a.tholes)
+#define CALL(L) if (a.rowend) FIELD(L, true); else FIELD(L, false)
   ADMP_LPR_SWITCH(lpr, CALL)
 #undef CALL
 #undef FIELD
 }
-// the field kernels as riders of an x pass (k_xconv_pair): false = this launch cannot ride (no rows, another lane count)
-constexpr int kRiderLpr = 16;
 template <class T>
-bool field_rider_full(FieldRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,
-                      const ScaleTab<T>& tab, T kappa, T* fld, const int* rows, const int* n_dev, const int* cls_flags,
-                      const RQ4<T>* rq, const T* tholes) {
-  if (pair_mono_off() || !rq) cls_flags = nullptr;
-  if (na <= 0 || field_lanes_per_row(na, false) != kRiderLpr) return false;
-  r.kind = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nb.rowend; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
-  r.kappa = kappa; r.fld = fld; r.rows = rows; r.nblocks = grid_for(na, kRiderLpr); r.grid = xcd_grid(r.nblocks);
-  r.n_dev = n_dev; r.cls_flags = cls_flags; r.rq = rq; r.tholes = tholes;
-  return true;
-}
-template <class T>
-bool field_rider_ind(FieldRider<T>& r, int n_rows, const IndTable& it, const Site<T>* sites, const Box<T>& box,
-                     const ScaleTab<T>& tab, T kappa, T* fld, const int* rows) {
-  if (n_rows <= 0 || field_lanes_per_row(n_rows, true) != kRiderLpr) return false;
-  r.kind = 2; r.na = n_rows; r.rowptr = it.beg; r.rowend = it.end; r.col = it.col; r.sites = sites; r.box = box; r.tab = tab;
-  r.kappa = kappa; r.fld = fld; r.rows = rows; r.nblocks = grid_for(n_rows, kRiderLpr); r.grid = xcd_grid(r.nblocks);
-  r.n_dev = nullptr; r.cls_flags = nullptr; r.rq = nullptr; r.tholes = nullptr;
-  return true;
-}
-// x pass of a direct-DFT convolution (one mesh) with the rider's workgroups appended to its grid
-// ctab != nullptr: the circulant form of the x pass (dft_kernels.hip launch_ctab; tw and tabs are then unused)
-template <class T>
-void launch_dft_x_conv_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                             int slot, const FieldRider<T>& fr, const T* ctab) {
-  const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
-  const int NC = ctab ? dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0)
-                      : dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
-  const size_t sh = ctab ? dft_x_circ_col_bytes<T>(N) * (size_t)NC
-                         : sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
-  const int nbx = (Kh + NC - 1) / NC;
-  const unsigned extra = (fr.grid + (unsigned)K[1] - 1) / (unsigned)K[1];
-  XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
-                  reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
-  xa.ctab = ctab;
-  const dim3 grid((unsigned)nbx + extra, (unsigned)K[1], 1);
-  const bool cut = fr.kind == 1 && fr.rowend;
-  if (ctab) {
-    if (cut) k_xconv_pair<T, kRiderLpr, true, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
-    else k_xconv_pair<T, kRiderLpr, false, true><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
-  } else {
-    if (cut) k_xconv_pair<T, kRiderLpr, true, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
-    else k_xconv_pair<T, kRiderLpr, false, false><<<grid, kPairBlock, sh, st>>>(xa, fr, nbx);
-  }
-}
-
-// the closing pair kernel as a rider (k_xconv_pair_full).  Double precision, polarizable, kRiderLpr lanes per row; single
-// precision (127 registers under the same bound) has not been measured as a rider and keeps its own launch.
-template <class T>
-bool full_rider(FullRider<T>& r, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box, const ScaleTab<T>& tab,
-                T kappa, int lpol, T* grad, T* pot, double* energies, const int* rows, T* fld, int use_mono,
-                const int* cls_flags, const RQ4<T>* rq, const T* tholes) {
-  if (sizeof(T) != 8 || !lpol || na <= 0 || pair_lanes_per_row(na) != kRiderLpr) return false;
-  if (pair_mono_off() || !cls_flags || !rq) use_mono = 0;
-  r.on = 1; r.na = na; r.rowptr = nb.rowptr; r.rowend = nb.rowend; r.col = nb.col; r.sites = sites; r.box = box; r.tab = tab;
-  r.kappa = kappa; r.grad = grad; r.pot = pot; r.energies = energies; r.rows = rows; r.fld = fld;
-  r.nblocks = grid_full(na, kRiderLpr); r.grid = xcd_grid(r.nblocks);
-  r.use_mono = use_mono; r.cls_flags = cls_flags; r.rq = rq; r.tholes = tholes;
-  return true;
-}
-template <class T>
-void launch_dft_x_conv_full_rider(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies,
-                                  int slot, const FullRider<T>& pr, const FieldRider<T>* fr, const T* ctab) {
-  if constexpr (sizeof(T) == 8) {
-    const int N = K[0], Kh = K[2] / 2 + 1, H = (N - 1) / 2, TK = dft_tasks(N, dft_kq());
-    const int NC = ctab ? dft_cols(N, dft_kq(), dft_x_circ_col_bytes<T>(N), 0)
-                        : dft_cols(N, dft_kq(), sizeof(PairCx<T>) * (size_t)H + sizeof(Cx<T>) * (size_t)(2 + N), sizeof(Cx<T>) * (size_t)N);
-    const size_t sh = ctab ? dft_x_circ_col_bytes<T>(N) * (size_t)NC
-                           : sizeof(PairCx<T>) * (size_t)(H * NC) + sizeof(Cx<T>) * (size_t)(N + 2 * NC + N * NC);
-    XConvArgs<T> xa{N, Kh, NC, TK, (long)K[1] * Kh, (long)Kh, K[2], reinterpret_cast<Cx<T>*>(spec), tabs,
-                    reinterpret_cast<const Cx<T>*>(tw), energies, slot, 0};
-    xa.ctab = ctab;
-    RiderGrid rg;
-    rg.npair = pr.grid; rg.nind = fr ? fr->grid : 0u; rg.nbx = (unsigned)((Kh + NC - 1) / NC); rg.ny = (unsigned)K[1];
-    const FieldRider<T> none{};
-    const FieldRider<T>& f2 = fr ? *fr : none;
-    const dim3 grid(rider_grid_blocks(rg), 1, 1);
-    if (ctab) {
-      if (pr.rowend) k_xconv_pair_full<T, kRiderLpr, true, true><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
-      else k_xconv_pair_full<T, kRiderLpr, false, true><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
-    } else {
-      if (pr.rowend) k_xconv_pair_full<T, kRiderLpr, true, false><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
-      else k_xconv_pair_full<T, kRiderLpr, false, false><<<grid, kPairBlock, sh, st>>>(xa, pr, f2, rg);
-    }
-  }
-}
-
-template <class T>
-void launch_pair_field_ind(hipStream_t st, int n_rows, const IndTable& it, const Site<T>* sites, const Box<T>& box,
-                           const ScaleTab<T>& tab, T kappa, T* fld, const int* rows) {
-  if (n_rows <= 0) return;
-  const int lpr = field_lanes_per_row(n_rows, true);
-#define CALL(L)                                                                                                          \
-  k_pair_field_ind<T, L><<<xcd_grid(grid_for(n_rows, L)), kPairBlock, 0, st>>>(n_rows, it.beg, it.end, it.col, sites, box, tab, \
-                                                                               kappa, fld, rows)
+void launch_pair_field_ind(hipStream_t st, PairFieldArgs<T> a) {
+  if (a.na <= 0) return;
+  const int lpr = field_lanes_per_row(a.na, true);
+  finish_args(a, lpr);
+#define CALL(L) \
+  k_pair_field_ind<T, L><<<a.grid, kPairBlock, 0, st>>>(a.na, a.rowptr, a.rowend, a.col, a.sites, a.box, a.tab, a.kappa, a.fld, a.rows)
   ADMP_LPR_SWITCH(lpr, CALL)
 #undef CALL
 }
+
+// The kernels as riders of an x pass.  The rider kernels are compiled for kRiderLpr lanes per row; the closing kernel rides
+// in double precision and polarizable only: single precision (127 registers under the same bound) has not been measured as a
+// rider and keeps its own launch.
+constexpr int kRiderLpr = 16;
+template <class T>
+bool full_rider(const PairFullArgs<T>& a, int lpol) {
+  return sizeof(T) == 8 && lpol && a.na > 0 && pair_lanes_per_row(a.na) == kRiderLpr;
+}
+template <class T>
+bool field_rider(const PairFieldArgs<T>& a) {
+  return a.na > 0 && field_lanes_per_row(a.na, a.kind == 2) == kRiderLpr;
+}
+// One mesh, one launch (the choices: launch.h): the tiles' shape is the plan's, the riders' workgroups come on top.
+template <class T>
+void launch_dft_x_pass(hipStream_t st, const int K[3], const T* tw, T* spec, const DftTabs<T>& tabs, double* energies, int slot,
+                       const T* ctab, const PairFieldArgs<T>* field, const PairFullArgs<T>* full) {
+  const bool has_full = full && full->on, has_field = field && field->kind;
+  if (!has_full && !has_field) {
+    if (ctab) launch_dft_x_circ<T>(st, K, spec, ctab, energies, slot);
+    else launch_dft_x_conv<T>(st, K, tw, spec, tabs, energies, slot);
+    return;
+  }
+  const XPassPlan p = dft_x_plan(K, sizeof(T), ctab != nullptr);
+  const XConvArgs<T> xa = dft_x_args<T>(p, K, tw, spec, tabs, energies, slot, ctab);
+  PairFieldArgs<T> fr;
+  if (has_field && (!has_full || field->kind == 2)) { fr = *field; finish_args(fr, kRiderLpr); }
+#define XPAIR(KERNEL, CUT, GRID, ...)                                                                        \
+  if (ctab) {                                                                                            \
+    if (CUT) KERNEL<T, kRiderLpr, true, true><<<GRID, kPairBlock, p.lds, st>>>(xa, __VA_ARGS__);         \
+    else KERNEL<T, kRiderLpr, false, true><<<GRID, kPairBlock, p.lds, st>>>(xa, __VA_ARGS__);            \
+  } else {                                                                                               \
+    if (CUT) KERNEL<T, kRiderLpr, true, false><<<GRID, kPairBlock, p.lds, st>>>(xa, __VA_ARGS__);        \
+    else KERNEL<T, kRiderLpr, false, false><<<GRID, kPairBlock, p.lds, st>>>(xa, __VA_ARGS__);           \
+  }
+  if (has_full) {
+    if constexpr (sizeof(T) == 8) {      // (full_rider admits double precision only: there is no single-precision rider kernel)
+      PairFullArgs<T> pr = *full;
+      finish_args(pr, kRiderLpr);
+      RiderGrid rg;
+      rg.npair = pr.grid; rg.nind = fr.grid; rg.nbx = (unsigned)p.nbx; rg.ny = (unsigned)K[1];
+      XPAIR(k_xconv_pair_full, pr.rowend, dim3(rider_grid_blocks(rg), 1, 1), pr, fr, rg)
+    }
+  } else {
+    const dim3 grid((unsigned)p.nbx + (fr.grid + (unsigned)K[1] - 1) / (unsigned)K[1], (unsigned)K[1], 1);
+    XPAIR(k_xconv_pair, fr.kind == 1 && fr.rowend, grid, fr, p.nbx)
+  }
+#undef XPAIR
+}
+
 template <class T>
 void launch_disp_pair(hipStream_t st, int na, const NbrTable& nb, const SRow<T>* srows, const Box<T>& box,
                       const ScaleTab<T>& tab, T kappa, int pmax, T* grad, double* energies, const int* rows, int n_rows,
@@ -1008,24 +980,13 @@ void launch_tt_pair(hipStream_t st, int na, const NbrTable& nb, const SRow<T>* s
 }
 
 #define INST(T)                                                                                                     \
-  template void launch_pair_full<T>(hipStream_t, int, const NbrTable&, const Site<T>*, const Box<T>&,               \
-                                    const ScaleTab<T>&, T, int, T*, T*, double*, const int*, T*, int, const int*,   \
-                                    const RQ4<T>*, const T*);                                                       \
-  template void launch_pair_field<T>(hipStream_t, int, const NbrTable&, const Site<T>*, const Box<T>&,              \
-                                     const ScaleTab<T>&, T, T*, const int*, const int*, const int*,                 \
-                                     const RQ4<T>*, const T*);                                                      \
-  template void launch_pair_field_ind<T>(hipStream_t, int, const IndTable&, const Site<T>*, const Box<T>&,          \
-                                         const ScaleTab<T>&, T, T*, const int*);                                    \
-  template bool field_rider_full<T>(FieldRider<T>&, int, const NbrTable&, const Site<T>*, const Box<T>&, const ScaleTab<T>&, \
-                                    T, T*, const int*, const int*, const int*, const RQ4<T>*, const T*);            \
-  template bool field_rider_ind<T>(FieldRider<T>&, int, const IndTable&, const Site<T>*, const Box<T>&,             \
-                                   const ScaleTab<T>&, T, T*, const int*);                                          \
-  template void launch_dft_x_conv_rider<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int,  \
-                                           const FieldRider<T>&, const T*);                                         \
-  template bool full_rider<T>(FullRider<T>&, int, const NbrTable&, const Site<T>*, const Box<T>&, const ScaleTab<T>&, T, int, T*, \
-                              T*, double*, const int*, T*, int, const int*, const RQ4<T>*, const T*);               \
-  template void launch_dft_x_conv_full_rider<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int, \
-                                                const FullRider<T>&, const FieldRider<T>*, const T*);               \
+  template void launch_pair_full<T>(hipStream_t, PairFullArgs<T>, int);                                             \
+  template void launch_pair_field<T>(hipStream_t, PairFieldArgs<T>);                                                \
+  template void launch_pair_field_ind<T>(hipStream_t, PairFieldArgs<T>);                                            \
+  template bool full_rider<T>(const PairFullArgs<T>&, int);                                                         \
+  template bool field_rider<T>(const PairFieldArgs<T>&);                                                            \
+  template void launch_dft_x_pass<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int, const T*, \
+                                     const PairFieldArgs<T>*, const PairFullArgs<T>*);                              \
   template void launch_pack_scalar_rows<T>(hipStream_t, int, int, const T*, const T*, SRow<T>*);                    \
   template void launch_disp_pair<T>(hipStream_t, int, const NbrTable&, const SRow<T>*, const Box<T>&,               \
                                     const ScaleTab<T>&, T, int, T*, double*, const int*, int, double);              \

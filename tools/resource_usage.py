@@ -26,6 +26,7 @@ for c in rows:
     name = re.sub(r'\(.*', '', name).replace('void admp::', '')
     if flt and flt not in name:
         continue
-    print('%-48s VGPR %4s AGPR %3s SGPR %3s occ %2s scratch %5s LDS %6s' % (
+    print('%-48s VGPR %4s AGPR %3s SGPR %3s occ %2s scratch %5s LDS %6s vspill %3s' % (
         name[:48], c.get('VGPRs', '?'), c.get('AGPRs', '?'), c.get('TotalSGPRs', c.get('SGPRs', '?')),
-        c.get('Occupancy [waves/SIMD]', '?'), c.get('ScratchSize [bytes/lane]', '?'), c.get('LDS Size [bytes/block]', '?')))
+        c.get('Occupancy [waves/SIMD]', '?'), c.get('ScratchSize [bytes/lane]', '?'), c.get('LDS Size [bytes/block]', '?'),
+        c.get('VGPRs Spill', '?')))
