@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('ADMP_HIP_LIB') or os.path.join(_HERE, 'lib', 'libadmp
 
 _c = ctypes
 _vp, _i32, _i64, _dbl = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_double
+_u32, _u64 = _c.c_uint32, _c.c_uint64
 _dp = _c.POINTER(_c.c_double)
 _ip = _c.POINTER(_c.c_int)
 
@@ -53,6 +54,8 @@ PROTOTYPES = {
     'admp_mscale_grad': (_i32, [_vp, _i32, _vp, _dp, _vp, _i32, _i32, _dp, _i32]),
     'admp_md_bonded': (_i32, [_vp, _vp, _dp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     'admp_md_kick_drift': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp]),
+    'admp_md_langevin': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _u64, _u64, _vp]),
+    'admp_md_random': (_i32, [_vp, _i32, _i64, _u64, _u64, _u32, _vp]),
     'admp_neighbor_count': (_i32, [_vp, _i32, _vp, _dp, _dbl, _c.POINTER(_i64)]),
     'admp_neighbor_fill': (_i32, [_vp, _vp]),
     'admp_set_pairs_from_positions': (_i32, [_vp, _vp, _dp, _dbl]),

@@ -326,6 +326,9 @@ struct EngineBase {
                          const int32_t* aidx, const void* apar, double* E_dev, void* grad) = 0;
   virtual void md_kick_drift(int n, void* pos, void* vel, const void* grad, const void* inv_mass, double half_dt_acc, double dt,
                              double* ekin_dev) = 0;
+  virtual void md_langevin(int n, void* pos, void* vel, const void* grad, const void* inv_mass, double half_dt_acc, double dt,
+                           double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin_dev) = 0;
+  virtual void md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -2455,6 +2458,26 @@ struct Engine : EngineBase {
     launch_md_kick_drift<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), reinterpret_cast<const T*>(grad_),
                             reinterpret_cast<const T*>(inv_mass), half_dt_acc, dt, ekin_dev);
   }
+  void md_langevin(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, double half_dt_acc, double dt, double c1,
+                   double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin_dev) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && pos && vel && grad_ && inv_mass, "bad argument");
+    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
+    TIMED("md_langevin");
+    launch_md_langevin<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), reinterpret_cast<const T*>(grad_),
+                          reinterpret_cast<const T*>(inv_mass), half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, ekin_dev);
+    HIP_TRY(hipGetLastError());
+  }
+  void md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream_id, void* out) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(kind == 0 || kind == 1, "kind must be 0 (words) or 1 (normals)");
+    ARG_CHECK(n >= 0 && n <= (int64_t)1 << 32 && (n == 0 || out), "bad argument (the atom index is a 32-bit counter word)");
+    TIMED("md_random");
+    launch_md_random<T>(stream, kind, n, seed, step, stream_id, out);
+    HIP_TRY(hipGetLastError());
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3352,6 +3375,16 @@ int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int
 int admp_md_kick_drift(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
                        double half_dt_acc, double dt, double* ekin_dev) {
   return guarded(h, [&](EngineBase& e) { e.md_kick_drift(n_atoms, positions, velocities, grad, inv_mass, half_dt_acc, dt, ekin_dev); });
+}
+int admp_md_langevin(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
+                     double* ekin_dev) {
+  return guarded(h, [&](EngineBase& e) {
+    e.md_langevin(n_atoms, positions, velocities, grad, inv_mass, half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, ekin_dev);
+  });
+}
+int admp_md_random(admp_handle* h, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) {
+  return guarded(h, [&](EngineBase& e) { e.md_random(kind, n, seed, step, stream, out); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

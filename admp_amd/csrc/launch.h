@@ -664,5 +664,12 @@ void launch_md_bonded(hipStream_t st, int nb, const int* bidx, const T* bpar, in
 template <class T>
 void launch_md_kick_drift(hipStream_t st, int n, T* pos, T* vel, const T* grad, const T* inv_mass, double half_dt_acc, double dt,
                           double* ekin);
+// first half of a BAOAB Langevin step (B, A, O, A; noise of md_math.h, stream 0) and the generator written to memory
+// (kind 0: (n,4) uint32 words, kind 1: (n,3) T normals)
+template <class T>
+void launch_md_langevin(hipStream_t st, int n, T* pos, T* vel, const T* grad, const T* inv_mass, double half_dt_acc, double dt,
+                        double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin);
+template <class T>
+void launch_md_random(hipStream_t st, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out);
 
 }  // namespace admp

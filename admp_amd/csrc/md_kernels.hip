@@ -2,9 +2,13 @@
 // field (examples/*/mpidwater.xml:16-21, OpenMM's HarmonicBondForce / HarmonicAngleForce: E = k/2 (r - r0)^2, k/2 (theta -
 // theta0)^2) as ONE kernel over explicit bond / angle lists, and the two half steps of velocity Verlet as one elementwise
 // kernel each.  Round 3's driver did this with ~60 torch launches per step (autograd through acos / norm, elementwise updates).
+// The Langevin thermostat is one more elementwise kernel: the first half of a BAOAB step with its noise drawn in registers
+// from the counter-based generator of md_math.h (k_md_random writes the same words / normals to memory for the callers that
+// want them: the tests and the Maxwell-Boltzmann start of admp_amd/md.py).
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "md_math.h"
 #include "reduce.h"
 
 namespace admp {
@@ -80,6 +84,56 @@ __global__ __launch_bounds__(256) void k_md_kick_drift(int n, T* __restrict__ po
   }
 }
 
+// First half of a BAOAB Langevin step (Leimkuhler, Matthews 2013), one pass: B v -= half_dt_acc grad / m; A r += half_dt v;
+// O v = c1 v + sqrt(c2sq_kT_acc / m) xi; A r += half_dt v.  xi: three normals of (seed, step, stream 0, atom), computed in
+// double and rounded to T.  ekin (optional) += sum m v^2 / 2 after O.  The second half is k_md_kick_drift with dt = 0.
+template <class T>
+__global__ __launch_bounds__(256) void k_md_langevin(int n, T* __restrict__ pos, T* __restrict__ vel, const T* __restrict__ grad,
+                                                     const T* __restrict__ inv_mass, T half_dt_acc, T half_dt, T c1, T c2sq_kT_acc,
+                                                     uint64_t seed, uint64_t step, double* ekin) {
+  double ek = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const T im = inv_mass[i], sig = m_sqrt(c2sq_kT_acc * im);
+    double xi[3];
+    md_random_normals(seed, step, kStreamLangevin, (uint32_t)i, xi);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      T v = vel[3 * i + c] - half_dt_acc * grad[3 * i + c] * im;
+      T r = pos[3 * i + c] + half_dt * v;
+      v = c1 * v + sig * (T)xi[c];
+      r += half_dt * v;
+      vel[3 * i + c] = v;
+      pos[3 * i + c] = r;
+      ek += 0.5 * (double)v * (double)v / (double)im;
+    }
+  }
+  if (ekin) {
+    ek = block_reduce_sum<256>(ek);
+    if (threadIdx.x == 0) atomicAdd(ekin, ek);
+  }
+}
+
+// kind 0: out (n,4) uint32 = the words of (seed, step, stream, atom); kind 1: out (n,3) T = the normals
+template <class T>
+__global__ __launch_bounds__(256) void k_md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream,
+                                                   void* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    if (kind == 0) {
+      uint32_t w[4];
+      md_random_words(seed, step, stream, (uint32_t)i, w);
+      uint32_t* o = reinterpret_cast<uint32_t*>(out) + 4 * i;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = w[c];
+    } else {
+      double xi[3];
+      md_random_normals(seed, step, stream, (uint32_t)i, xi);
+      T* o = reinterpret_cast<T*>(out) + 3 * i;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c] = (T)xi[c];
+    }
+  }
+}
+
 template <class T>
 void launch_md_bonded(hipStream_t st, int nb, const int* bidx, const T* bpar, int na, const int* aidx, const T* apar, const T* pos,
                       const Box<T>& box, T* grad, double* E) {
@@ -94,10 +148,29 @@ void launch_md_kick_drift(hipStream_t st, int n, T* pos, T* vel, const T* grad, 
   if (blocks > 1024) blocks = 1024;      // (<= 1024 atomics on the kinetic-energy word)
   k_md_kick_drift<T><<<blocks, 256, 0, st>>>(n, pos, vel, grad, inv_mass, (T)half_dt_acc, (T)dt, ekin);
 }
+template <class T>
+void launch_md_langevin(hipStream_t st, int n, T* pos, T* vel, const T* grad, const T* inv_mass, double half_dt_acc, double dt,
+                        double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin) {
+  if (n <= 0) return;
+  int blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  k_md_langevin<T><<<blocks, 256, 0, st>>>(n, pos, vel, grad, inv_mass, (T)half_dt_acc, (T)(0.5 * dt), (T)c1, (T)c2sq_kT_acc, seed,
+                                           step, ekin);
+}
+template <class T>
+void launch_md_random(hipStream_t st, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) {
+  if (n <= 0) return;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  k_md_random<T><<<(int)blocks, 256, 0, st>>>(kind, n, seed, step, stream, out);
+}
 #define INST(T)                                                                                                              \
   template void launch_md_bonded<T>(hipStream_t, int, const int*, const T*, int, const int*, const T*, const T*, const Box<T>&, \
                                     T*, double*);                                                                            \
-  template void launch_md_kick_drift<T>(hipStream_t, int, T*, T*, const T*, const T*, double, double, double*);
+  template void launch_md_kick_drift<T>(hipStream_t, int, T*, T*, const T*, const T*, double, double, double*);             \
+  template void launch_md_langevin<T>(hipStream_t, int, T*, T*, const T*, const T*, double, double, double, double, uint64_t,  \
+                                      uint64_t, double*);                                                                      \
+  template void launch_md_random<T>(hipStream_t, int, int64_t, uint64_t, uint64_t, uint32_t, void*);
 INST(float)
 INST(double)
 #undef INST

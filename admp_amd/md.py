@@ -4,6 +4,11 @@
 and H-O-H angles) with one HIP kernel over explicit lists (include/admp_hip.h admp_md_bonded); `VelocityVerlet` does the two
 half steps with one kernel each (admp_md_kick_drift).  Energies accumulate in device words and are read only when the caller
 logs, so an MD step adds no host synchronisation of its own to those of the calculators.  Used by examples/md/nve_water.py.
+
+`Langevin` is the thermostat: BAOAB (Leimkuhler and Matthews 2013) with the same two-call shape, its first half one kernel
+(admp_md_langevin) that draws its noise in registers from a counter-based generator (csrc/md_math.h: Philox-4x32-10, a
+function of (seed, step, stream, atom) alone, so a restart at any step repeats the noise); `maxwell_boltzmann` draws the
+initial velocities from the same generator (admp_md_random).  Used by examples/md/nvt_water.py.
 """
 import ctypes
 
@@ -12,6 +17,9 @@ import torch
 
 from . import _lib
 from ._device import HipForceBase
+
+KB = 0.0083144626          # kJ/mol/K
+STREAM_LANGEVIN, STREAM_MAXWELL = 0, 1      # csrc/md_math.h: the two users of the generator never share a counter
 
 
 class HarmonicBonded(HipForceBase):
@@ -95,3 +103,110 @@ class VelocityVerlet:
     def kinetic_energy(self):
         """(host read) sum m v^2 / 2 of the last kick(want_ekin=True), in kJ/mol"""
         return float(self.ekin_word[0]) / self.ACC
+
+
+def random_fill(handle_owner, kind, n, seed, step, stream):
+    """The generator of csrc/md_math.h written to a new device tensor (admp_md_random): kind 0: (n,4) words as int32 bit
+    patterns (torch has no arithmetic on uint32; view them with numpy), kind 1: (n,3) standard normals of the handle's
+    precision.  Row i is a function of (seed, step, stream, i) alone."""
+    o = handle_owner
+    o._use_current_stream()
+    n = int(n)
+    if n < 0:
+        raise ValueError('n must not be negative')
+    out = torch.empty((n, 4), dtype=torch.int32, device=o._device) if kind == 0 else \
+        torch.empty((n, 3), dtype=o._dtype, device=o._device)
+    _lib.check(o._h, o._L.admp_md_random(o._h, int(kind), n, int(seed), int(step), int(stream), o._ptr(out)), 'admp_md_random')
+    return out
+
+
+def maxwell_boltzmann(handle_owner, masses, temperature, seed, remove_com=True):
+    """(n,3) device velocities in A/fs at `temperature` (K) for `masses` (amu): the normals of (seed, step 0, stream 1) times
+    sqrt(1e-4 kB T / m); remove_com: minus the mass-weighted mean velocity (the temperature is then the one over 3n - 3
+    degrees of freedom)."""
+    o = handle_owner
+    m = np.asarray(masses, dtype=np.float64).reshape(-1)
+    if temperature < 0 or not np.all(m > 0):
+        raise ValueError('temperature must not be negative and masses must be positive')
+    xi = random_fill(o, 1, len(m), seed, 0, STREAM_MAXWELL)
+    vel = xi * o._real(np.sqrt(VelocityVerlet.ACC * KB * float(temperature) / m))[:, None]
+    if remove_com:
+        m64 = torch.as_tensor(m, device=o._device)
+        vel -= ((m64[:, None] * vel.double()).sum(0) / m64.sum()).to(vel.dtype)
+    return vel.contiguous()
+
+
+class Langevin:
+    """BAOAB Langevin dynamics at `temperature` (K) with friction `friction_per_fs` (1/fs); units as in VelocityVerlet.
+    kick_drift is B, A, O, A in one kernel (v -= (dt/2) 1e-4 grad / m; r += (dt/2) v; v = c1 v + sqrt((1 - c1^2) 1e-4 kB T / m)
+    xi, c1 = exp(-friction dt); r += (dt/2) v) with xi drawn from (seed, step, stream 0, atom); kick is the closing B
+    (admp_md_kick_drift).  `step` counts the kick_drift calls and may be set (a restart draws the same noise again).
+    friction 0 is velocity Verlet."""
+    ACC = VelocityVerlet.ACC
+
+    def __init__(self, handle_owner, masses, dt_fs, temperature, friction_per_fs, seed):
+        self._o = handle_owner
+        self.dt = float(dt_fs)
+        self.T = float(temperature)
+        self.friction = float(friction_per_fs)
+        self.seed = int(seed)
+        self.step = 0
+        if self.T < 0 or self.friction < 0 or self.dt < 0 or not 0 <= self.seed < 2 ** 64:
+            raise ValueError('temperature, friction and dt must not be negative; the seed is an unsigned 64-bit number')
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if not np.all(m > 0):
+            raise ValueError('masses must be positive')
+        self.n_atoms = len(m)
+        self.inv_mass = handle_owner._real(1.0 / m)
+        self.c1 = float(np.exp(-self.friction * self.dt))
+        self.c2sq_kT_acc = (1.0 - self.c1 * self.c1) * KB * self.T * self.ACC
+        self.ekin_word = torch.zeros(1, dtype=torch.float64, device=handle_owner._device)
+
+    def _checked(self, **tensors):
+        """the library reads and writes raw pointers: anything but (n,3) contiguous tensors of the handle's precision on its
+        device would be read or written out of bounds"""
+        o = self._o
+        for name, t in tensors.items():
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == o._device.index):
+                raise ValueError('%s must be a tensor on the handle\'s device' % name)
+            if t.dtype != o._dtype:
+                raise ValueError('%s must be of the handle\'s precision (%s), got %s' % (name, o._dtype, t.dtype))
+            if tuple(t.shape) != (self.n_atoms, 3):
+                raise ValueError('%s must have shape (%d, 3), got %s' % (name, self.n_atoms, tuple(t.shape)))
+            if not t.is_contiguous():
+                raise ValueError('%s must be contiguous' % name)
+
+    def kick_drift(self, pos, vel, grad, want_ekin=False):
+        """first half: r(t + dt) and the velocities after the friction step; then step += 1"""
+        self._checked(pos=pos, vel=vel, grad=grad)
+        o = self._o
+        o._use_current_stream()
+        if want_ekin:
+            self.ekin_word.zero_()
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_langevin(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass),
+                                               0.5 * self.dt * self.ACC, self.dt, self.c1, self.c2sq_kT_acc, self.seed,
+                                               int(self.step) & (2 ** 64 - 1), P(self.ekin_word) if want_ekin else None),
+                   'admp_md_langevin')
+        self.step += 1
+
+    def kick(self, pos, vel, grad, want_ekin=False):
+        """second half: v(t + dt) with the gradient at r(t + dt); want_ekin: the kinetic energy of the new velocities lands
+        in ekin_word"""
+        self._checked(pos=pos, vel=vel, grad=grad)
+        o = self._o
+        o._use_current_stream()
+        if want_ekin:
+            self.ekin_word.zero_()
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_kick_drift(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass),
+                                                 0.5 * self.dt * self.ACC, 0.0, P(self.ekin_word) if want_ekin else None),
+                   'admp_md_kick_drift')
+
+    def kinetic_energy(self):
+        """(host read) sum m v^2 / 2 of the last call with want_ekin=True, in kJ/mol"""
+        return float(self.ekin_word[0]) / self.ACC
+
+    def temperature(self, n_dof=None):
+        """(host read) 2 Ekin / (n_dof kB) of the last call with want_ekin=True; n_dof defaults to 3 N"""
+        return 2.0 * self.kinetic_energy() / ((3 * self.n_atoms if n_dof is None else n_dof) * KB)

@@ -1,0 +1,73 @@
+#!/usr/bin/env python
+"""Langevin NVT loop (BAOAB) on the full MPID-style water potential: the calculators, lists and forces of nve_water.py
+(water_md.py) under the thermostat of admp_amd/md.py.  The first half of a step -- kick, half drift, friction + noise, half
+drift -- is ONE elementwise HIP kernel (admp_md_langevin) that draws its noise in registers from a counter-based generator
+(Philox-4x32-10: a function of (seed, step, atom) alone, so a run restarted at any step repeats its noise); the second half
+is the kick of velocity Verlet.  The velocities start from a Maxwell-Boltzmann draw of the same generator
+(admp_amd.md.maxwell_boltzmann), and the driver logs the kinetic temperature: after the minimised box has heated up
+(friction * time of a few units) it fluctuates around --temp with the relative width sqrt(2 / 3N).
+
+    python examples/md/nvt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1] [--pol]
+                                    [--single] [--mesh K] [--log 10] [--prune M] [--predict k]
+
+The other arguments are those of nve_water.py.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from water_md import MASS, add_arguments, setup, minimize      # noqa: E402
+from admp_amd import settings                                  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    add_arguments(ap)
+    ap.add_argument('--friction', type=float, default=0.05, help='1/fs')
+    ap.add_argument('--seed', type=int, default=1, help='of the initial velocities and of the thermostat\'s noise')
+    opt = ap.parse_args()
+    w = setup(opt)
+    from admp_amd.md import Langevin, maxwell_boltzmann
+    n_mol, pme, nbl, forces, epot_now, state = w.n_mol, w.pme, w.nbl, w.forces, w.epot_now, w.state
+    masses = np.tile(MASS, n_mol)
+    h = opt.dt
+    # units: A, fs, amu, kJ/mol
+    vel = maxwell_boltzmann(pme, masses, opt.temp, opt.seed)
+    lv = Langevin(pme, masses, h, opt.temp, opt.friction, opt.seed)
+    pos, pairs, e123, grad = minimize(w, opt, w.pos)
+    log = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for step in range(opt.steps):
+        lv.kick_drift(pos, vel, grad)                                  # B, A, O, A: in place, one kernel
+        if (step + 1) % opt.rebuild == 0:
+            pairs = nbl.allocate(pos)
+        if opt.prune and (step + 1) % opt.prune == 0:
+            nbl.prune(pos)
+        e123, grad = forces(pos, pairs)
+        rec = step % opt.log == 0 or step == opt.steps - 1
+        lv.kick(pos, vel, grad, want_ekin=rec)                         # B: v(t + h)
+        if rec:
+            log.append((step, epot_now(e123), lv.kinetic_energy(), lv.temperature()))
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    for (s, ep, ek, tk) in log:
+        print('step %5d  Epot %14.4f  Ekin %12.4f  T_kin %8.2f' % (s, ep, ek, tk))
+    ns_day = opt.steps * h * 1e-6 / wall * 86400.0
+    if opt.pol:
+        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
+    tk = np.array([r[3] for r in log if r[0] >= opt.steps // 2])
+    print('# %d waters, %s, %s, dt %.2f fs, Langevin %.1f K, friction %g /fs, seed %d: T_kin over the second half mean %.1f K '
+          'std %.1f K (%d records); %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps)'
+          % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles', settings.PRECISION, h, opt.temp, opt.friction, opt.seed,
+             tk.mean(), tk.std(), len(tk), wall / opt.steps * 1e3, ns_day, opt.rebuild))
+
+
+if __name__ == '__main__':
+    main()

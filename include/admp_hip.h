@@ -271,12 +271,26 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       centre, k), angle_par (n_angles,2) real = (k, theta0 in rad); minimum-image vectors;
  *                       E_dev[0] += bond energy, E_dev[1] += angle energy (doubles); grad_inout (Na,3) real += dE/dr
  *   admp_md_kick_drift  v -= half_dt_acc * grad / m (grad = +dE/dr, inv_mass (Na) real); then, if dt != 0, r += dt * v;
- *                       ekin_dev (optional) += sum m v^2 / 2 after the kick, in the caller's units */
+ *                       ekin_dev (optional) += sum m v^2 / 2 after the kick, in the caller's units
+ *   admp_md_langevin    first half of a BAOAB Langevin step in one pass: v -= half_dt_acc * grad / m; r += dt/2 * v;
+ *                       v = c1 * v + sqrt(c2sq_kT_acc / m) * xi; r += dt/2 * v, with c1 = exp(-gamma dt) in [0, 1] and
+ *                       c2sq_kT_acc = (1 - c1^2) kB T in the units of v^2 m (>= 0), both from the host in double; xi: three
+ *                       standard normals per atom, a function of (seed, step, stream 0, atom index) alone (Philox-4x32-10,
+ *                       Box-Muller in double: csrc/md_math.h), so a restart at `step` draws the same noise.  ekin_dev
+ *                       (optional) += sum m v^2 / 2 after the friction step.  The second half of the step is
+ *                       admp_md_kick_drift with dt = 0.
+ *   admp_md_random      the same generator written to memory: kind 0: out (n,4) uint32, the raw words; kind 1: out (n,3)
+ *                       real, the normals; counter = (atom, step low, step high, stream), key = (seed low, seed high)
+ * The last two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE). */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
                    const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
                    void* grad_inout);
 int admp_md_kick_drift(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
                        double half_dt_acc, double dt, double* ekin_dev);
+int admp_md_langevin(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
+                     double* ekin_dev);
+int admp_md_random(admp_handle* h, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
