@@ -5,6 +5,8 @@
 // At 97^3 (f64) the whole chain is ~0.9 GFLOP of f64 FMAs; the lines come out of L2 / Infinity Cache (7 MB spectrum).
 #include "dft_lines.h"
 #include "env.h"
+#include "mfma.h"
+#include "plane_mfma_plan.h"
 
 namespace admp {
 
@@ -360,7 +362,21 @@ __global__ __launch_bounds__(kDftBlock) void k_dft_x_mix(int N, int ncols, int N
 // measured 2 % slower than two; two lanes per z task, each summing half of the pair positions (three rounds of 24 steps
 // instead of two of 48, idle lanes running along for the shuffles): 17 % slower.  The z results are paired in place along y (row j <- x_j + x_{N-j}, row N-j <-
 // x_j - x_{N-j}: dft_pair_outputs_rows) between the two stages.
+// Round 10 stamped the two-workgroup kernels themselves (tools/ubench/plane_hybrid.hip, profiles/README.md r10a): the figures
+// above are those of one workgroup of a PAIR -- at 97^3 f64 the forward kernel spends 2.4 us loading, 8.4-8.6 us in the z lines,
+// 0.6 us pairing and 7.9-8.0 us in the y lines; a line phase waits for one wave's 48-step loop, not for the CU's f64 rate.
 constexpr int kZyBlock = 1024;
+
+// phase stamps for tools/ubench/plane_hybrid.hip (100 MHz wall clock of thread 0 of every workgroup, taken behind a barrier
+// that the kernels do not otherwise have at their end); compiled out otherwise
+#ifdef ADMP_ZY_TRACE
+__device__ long long* g_zy_trace;
+#define ZY_TRACE(slot) do { if (threadIdx.x == 0) g_zy_trace[((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (slot)] = wall_clock64(); } while (0)
+#define ZY_TRACE_END(slot) do { __syncthreads(); ZY_TRACE(slot); } while (0)
+#else
+#define ZY_TRACE(slot) do {} while (0)
+#define ZY_TRACE_END(slot) do {} while (0)
+#endif
 
 template <class T>
 struct ZyLayout {          // LDS carve-up of the plane kernels (bytes); the same for both directions
@@ -505,7 +521,119 @@ __device__ __forceinline__ void zy_plane_spread(const PlaneSpread<T>& sp, int px
   }
 }
 
-template <class T, int KQ, bool SPREAD>
+// One matrix unit of the y lines (plane_mfma_plan.h): P = C a, R = S b for 16 outputs k and the two parts of 8 complex columns.
+// The twiddle operand is A[i = lane & 15][position], the data operand B[position][lane & 15] = the paired rows of Z (row
+// 1 + jj: sums, row N - 1 - jj: differences), one word per lane and step of 4 positions; a lane ends up with ONE component of
+// X[k] and X[N-k] and takes the other product's partner component from lane ^ 8 (tools/experiments/dft_mfma.hip).  out = the
+// plane's spectrum at this workgroup's first column, os its row stride.
+template <class T, int SIGN>
+__device__ __forceinline__ void dft_y_unit(const PlaneMfmaPlan& mp, int u, const Cx<T>* Z, const Cx<T>* tw, Cx<T>* out, int os) {
+  typedef typename Mfma<T>::Acc Acc;
+  const int N = mp.N, H = mp.H, mt = u % mp.MT, ct = u / mp.MT;
+  const int lane = threadIdx.x & 63, hi = plane_mfma_pos0(lane);
+  const int i = plane_mfma_tw_row(mt, lane), c = plane_mfma_col(ct, lane), comp = plane_mfma_comp(lane);
+  TwIdx ti(i < H ? i : 0, hi, N);
+  const bool live = c < mp.ncols;
+  const T* zc = reinterpret_cast<const T*>(Z + (live ? c : 0)) + comp;
+  const int rs = 2 * mp.ncols;                                  // row stride in words
+  // two operand sets in flight: the LDS reads of a step are issued before the products of the step before it
+  struct Ops { Cx<T> w; T b[2]; };
+  auto fetch = [&](Ops& o, int kk) {
+    o.w = tw[ti.m];
+    ti.step();
+    const bool ok = live && kk < H;
+    o.b[0] = ok ? zc[(1 + kk) * rs] : T(0);
+    o.b[1] = ok ? zc[(N - 1 - kk) * rs] : T(0);
+  };
+  Acc P = {0, 0, 0, 0}, R = {0, 0, 0, 0};
+  T s0 = T(0);                                                  // this lane's share of the column sum (k = 0 and N / 2)
+  auto mul = [&](const Ops& o) {
+    s0 += o.b[0];
+    P = Mfma<T>::mma(o.w.re, o.b[0], P);
+    R = Mfma<T>::mma(o.w.im, o.b[1], R);
+  };
+  Ops A, B;
+  fetch(A, hi);
+  for (int kk = hi; kk < mp.KP; kk += 8) {
+    const bool two = kk + 4 < mp.KP;                            // (uniform: KP is a multiple of 4)
+    if (two) fetch(B, kk + 4);
+    mul(A);
+    if (kk + 8 < mp.KP) fetch(A, kk + 8);
+    if (two) mul(B);
+  }
+  const T x0 = zc[0], xn = (N & 1) ? T(0) : zc[(N / 2) * rs];
+  T* o = reinterpret_cast<T*>(out + (live ? c : 0)) + comp;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int k = plane_mfma_out_k(mt, lane, r);
+    const T other = __shfl_xor(R[r], 8, 64);
+    if (live && k <= H) {
+      T base = x0 + P[r];
+      if ((N & 1) == 0) base += (k & 1) ? -xn : xn;
+      const T q = comp ? T(SIGN) * other : -T(SIGN) * other;    // im: + sgn R.re ; re: - sgn R.im
+      o[2 * (long)k * os] = base + q;
+      o[2 * (long)(N - k) * os] = base - q;
+    }
+  }
+  if (mt == 0) {                                                // (uniform) X_0 and X_{N/2}: position j = 1 + hi + 4 n
+    T s1 = (hi & 1) ? s0 : -s0;
+    s0 += __shfl_xor(s0, 16, 64); s1 += __shfl_xor(s1, 16, 64);
+    s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
+    if (hi == 0 && live) {
+      o[0] = x0 + s0 + xn;
+      if ((N & 1) == 0) o[2 * (long)(N / 2) * os] = x0 + s1 + (((N / 2) & 1) ? -xn : xn);
+    }
+  }
+}
+
+// One matrix unit of the forward z lines (PlaneMfmaZPlan): 16 outputs k against 16 real lines; the twiddle operand is
+// A[i = lane & 15][position], the data operand B[position][lane & 15] = the pair sums of line l (.re for P, .im for R).
+template <class T>
+__device__ __forceinline__ void dft_z_unit(const PlaneMfmaZPlan& zp, int u, const Cx<T>* p, const T* x0, const T* xn,
+                                           const Cx<T>* tw, Cx<T>* Z) {
+  typedef typename Mfma<T>::Acc Acc;
+  const int N = zp.N, H = zp.H, mt = u % zp.MT, lt = u / zp.MT;
+  const int lane = threadIdx.x & 63, hi = lane >> 4;
+  const int kt = plane_mfma_z_tw_k(zp, mt, lane), l = plane_mfma_z_line(lt, lane);
+  TwIdx ti((kt <= N / 2 ? kt : 0) - 1, hi, N);                  // (TwIdx takes the output minus one)
+  const bool live = l < zp.nlines;
+  const Cx<T>* pl = p + (live ? l : 0);
+  struct Ops { Cx<T> w, v; };
+  auto fetch = [&](Ops& o, int kk) {
+    o.w = tw[ti.m];
+    ti.step();
+    o.v = (live && kk < H) ? pl[kk * zp.nlines] : Cx<T>{T(0), T(0)};
+  };
+  Acc P = {0, 0, 0, 0}, R = {0, 0, 0, 0};
+  auto mul = [&](const Ops& o) {
+    P = Mfma<T>::mma(o.w.re, o.v.re, P);
+    R = Mfma<T>::mma(o.w.im, o.v.im, R);
+  };
+  Ops A, B;
+  fetch(A, hi);
+  for (int kk = hi; kk < zp.KP; kk += 8) {
+    const bool two = kk + 4 < zp.KP;                            // (uniform: KP is a multiple of 4)
+    if (two) fetch(B, kk + 4);
+    mul(A);
+    if (kk + 8 < zp.KP) fetch(A, kk + 8);
+    if (two) mul(B);
+  }
+  if (live) {
+    const T a0 = x0[l], an = xn[l];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int k = plane_mfma_z_out_k(zp, mt, lane, r);
+      if (k < zp.k0 + zp.nout) {
+        T re = a0 + P[r];
+        if ((N & 1) == 0) re += (k & 1) ? -an : an;
+        Z[l * zp.nout + k - zp.k0] = Cx<T>{re, -R[r]};
+      }
+    }
+  }
+}
+
+// MF (double precision): the z and the y lines as matrix units on waves [0, Wm) of their plans, the task loops on the others
+template <class T, int KQ, bool SPREAD, bool MF = false>
 __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T* __restrict__ mesh, Cx<T>* __restrict__ spec,
                                                          const Cx<T>* __restrict__ tw2g, const Cx<T>* __restrict__ tw3g,
                                                          long mesh_stride, long spec_stride, PlaneSpread<T> sp) {
@@ -521,6 +649,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
   Cx<T>* Z = reinterpret_cast<Cx<T>*>(dft_smem + L.b);          // [N2][Kl]
   const T* plane = mesh + blockIdx.y * mesh_stride + (long)blockIdx.x * N2 * N3;
   Cx<T>* out = spec + blockIdx.y * spec_stride + (long)blockIdx.x * N2 * Kh;
+  ZY_TRACE(0);
   for (int t = threadIdx.x; t < N3; t += kZyBlock) tw3[t] = tw3g[t];
   for (int t = threadIdx.x; t < N2; t += kZyBlock) tw2[t] = tw2g[t];
   if (SPREAD) {
@@ -538,9 +667,15 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
     }
   }
   __syncthreads();
+  ZY_TRACE(1);
   // z lines: task = (line l, group g of KQ of this workgroup's outputs)
   const int TK3 = (Kl + KQ - 1) / KQ;
-  for (int task = threadIdx.x; task < N2 * TK3; task += kZyBlock) {
+  const PlaneMfmaZPlan zp = plane_mfma_z_plan(N3, kz0, Kl, N2, kZyBlock / 64);
+  const bool zshare = MF && zp.nunits > 0;                      // (every line and output, or none)
+  if (zshare) {
+    for (int u = threadIdx.x >> 6; u < zp.nunits; u += zp.Wm) dft_z_unit<T>(zp, u, p, x0, xn, tw3, Z);
+  }
+  for (int task = zshare ? N2 * TK3 : (int)threadIdx.x; task < N2 * TK3; task += kZyBlock) {
     const int l = task / TK3, g = task - l * TK3;
     int k[KQ];
 #pragma unroll
@@ -552,6 +687,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
       if (g + q * TK3 < Kl) Z[l * Kl + g + q * TK3] = X[q];
   }
   __syncthreads();
+  ZY_TRACE(2);
   // pair the rows along y in place
   for (int t = threadIdx.x; t < H2 * Kl; t += kZyBlock) {
     const int jj = t / Kl, c = t - jj * Kl;
@@ -560,8 +696,35 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
     Z[(N2 - 1 - jj) * Kl + c] = Cx<T>{a.re - b.re, a.im - b.im};
   }
   __syncthreads();
+  ZY_TRACE(3);
   // y lines: task = (group g, column c): neighbouring threads store neighbouring kz
   const int Kh2 = N2 / 2 + 1, TK2 = (Kh2 + KQ - 1) / KQ;
+  if (MF) {
+    const PlaneMfmaPlan mp = plane_mfma_y_plan(N2, Kl, kZyBlock / 64);
+    const int wave = threadIdx.x >> 6, nv = Kl - mp.nm;
+    if (wave < mp.Wm) {
+      for (int u = wave; u < mp.nunits; u += mp.Wm) dft_y_unit<T, -1>(mp, u, Z, tw2, out + kz0, Kh);
+    } else {
+      for (int task = (int)threadIdx.x - 64 * mp.Wm; task < TK2 * nv; task += kZyBlock - 64 * mp.Wm) {
+        const int g = task / nv, c = mp.nm + task - g * nv;
+        int k[KQ];
+#pragma unroll
+        for (int q = 0; q < KQ; ++q) k[q] = (g + q * TK2 < Kh2) ? g + q * TK2 : 0;
+        Cx<T> Xk[KQ], Xnk[KQ];
+        dft_pair_outputs_rows<T, -1, KQ>(N2, k, Kl, Z + c, tw2, Xk, Xnk);
+#pragma unroll
+        for (int q = 0; q < KQ; ++q) {
+          const int kq = g + q * TK2;
+          if (kq < Kh2) {
+            out[(long)kq * Kh + kz0 + c] = Xk[q];
+            if (kq != 0 && 2 * kq != N2) out[(long)(N2 - kq) * Kh + kz0 + c] = Xnk[q];
+          }
+        }
+      }
+    }
+    ZY_TRACE_END(4);
+    return;
+  }
   for (int task = threadIdx.x; task < TK2 * Kl; task += kZyBlock) {
     const int g = task / Kl, c = task - g * Kl;
     int k[KQ];
@@ -578,6 +741,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
       }
     }
   }
+  ZY_TRACE_END(4);
 }
 
 template <class T, int KQ>
@@ -597,6 +761,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
   T* acc = accum ? accum + (long)blockIdx.x * N2 * N3 : nullptr;      // SCF increment: phi += this mesh in the same pass
   const int Kh2 = N2 / 2 + 1, TK2 = (Kh2 + KQ - 1) / KQ;
   const int g0 = (int)(((long)TK2 * blockIdx.z) / gridDim.z), g1 = (int)(((long)TK2 * (blockIdx.z + 1)) / gridDim.z);
+  ZY_TRACE(0);
   for (int t = threadIdx.x; t < N3; t += kZyBlock) tw3[t] = tw3g[t];
   for (int t = threadIdx.x; t < N2; t += kZyBlock) tw2[t] = tw2g[t];
   if (threadIdx.x == 0) {            // the y lines this workgroup produces: both members of its output pairs
@@ -623,6 +788,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
     Z[(N2 - 1 - jj) * Kh + c] = Cx<T>{a.re - b.re, a.im - b.im};
   }
   __syncthreads();
+  ZY_TRACE(1);
   for (int task = threadIdx.x; task < (g1 - g0) * Kh; task += kZyBlock) {
     const int g = g0 + task / Kh, c = task % Kh;
     int k[KQ];
@@ -640,6 +806,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
     }
   }
   __syncthreads();
+  ZY_TRACE(2);
   // z lines back: line l reads its half spectrum V[l][0 .. Kh)
   const int TK3 = (Kh + KQ - 1) / KQ, nl = s_nlines;
   for (int task = threadIdx.x; task < nl * TK3; task += kZyBlock) {
@@ -665,6 +832,7 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
       }
     }
   }
+  ZY_TRACE_END(3);
 }
 
 // ---- launchers.  K = mesh dimensions, tw = (cos, sin) tables of K[0], K[1], K[2] back to back.
@@ -757,8 +925,14 @@ bool dft_zy_spread_fits(const int K[3], int na) {
 }
 template <class T>
 bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec, int inverse, int nb, long mesh_stride,
-                   long spec_stride, T* accum, const PlaneSpread<T>* sp) {
+                   long spec_stride, T* accum, const PlaneSpread<T>* sp, int* mfma_share) {
   const size_t sh = ZyLayout<T>(K[1], K[2]).total;
+  // the matrix-core share of the forward z and y lines (plane_mfma_plan.h), double precision; ADMP_DFT_PLANE_MFMA=0 launches the
+  // vector kernels (read per call: the parity test runs both forms in one process)
+  const bool mf = sizeof(T) == 8 && !inverse && env_flag("ADMP_DFT_PLANE_MFMA", true) &&
+                  (plane_mfma_y_plan(K[1], (K[2] / 2 + 1) / 2, kZyBlock / 64).CT > 0 ||
+                   plane_mfma_z_plan(K[2], 0, (K[2] / 2 + 1) / 2, K[1], kZyBlock / 64).MT > 0);
+  if (mfma_share) *mfma_share = mf ? 1 : 0;
   const Cx<T>* t1 = reinterpret_cast<const Cx<T>*>(tw) + K[0];
   const Cx<T>* t2 = t1 + K[1];
   const dim3 grid(K[0], nb, 2);                  // two workgroups per plane
@@ -769,6 +943,17 @@ bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec
     kern<<<grid, kZyBlock, sh, st>>>(K[1], K[2], reinterpret_cast<const Cx<T>*>(spec), mesh, t1, t2, mesh_stride, spec_stride / 2,
                                      nb == 1 ? accum : nullptr);
     return accum != nullptr && nb == 1;
+  }
+  if constexpr (sizeof(T) == 8) {
+    if (mf) {
+      static size_t attr_mf[2] = {0, 0};
+      auto kern = sp ? k_dft_zy_fwd<T, 2, true, true> : k_dft_zy_fwd<T, 2, false, true>;
+      size_t& have = attr_mf[sp ? 1 : 0];
+      if (have < sh) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); have = sh; }
+      kern<<<grid, kZyBlock, sh, st>>>(K[1], K[2], mesh, reinterpret_cast<Cx<T>*>(spec), t1, t2, mesh_stride, spec_stride / 2,
+                                       sp ? *sp : PlaneSpread<T>());
+      return false;
+    }
   }
   if (sp) {
     static size_t attr_sp = 0;
@@ -787,7 +972,7 @@ bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec
 #define INST(T)                                                                                   \
   template bool dft_zy_fits<T>(const int*);                                                       \
   template bool dft_zy_spread_fits<T>(const int*, int);                                           \
-  template bool launch_dft_zy<T>(hipStream_t, const int*, const T*, T*, T*, int, int, long, long, T*, const PlaneSpread<T>*); \
+  template bool launch_dft_zy<T>(hipStream_t, const int*, const T*, T*, T*, int, int, long, long, T*, const PlaneSpread<T>*, int*); \
   template bool launch_dft_z<T>(hipStream_t, const int*, const T*, T*, T*, int, int, long, long, T*); \
   template void launch_dft_y<T>(hipStream_t, const int*, const T*, T*, int, int, long);           \
   template void launch_dft_x_conv<T>(hipStream_t, const int*, const T*, T*, const DftTabs<T>&, double*, int, int, long); \

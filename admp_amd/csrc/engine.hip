@@ -190,6 +190,8 @@ struct EngineBase {
   int64_t scf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // x passes of the direct-DFT convolution of one mesh (admp_xpass_stats): [0] circulant form, [1] forward * G * inverse
   int64_t xpass_stats[2] = {0, 0};
+  // launches of the plane kernels of the direct-DFT convolution (admp_plane_mfma_stats): [0] with a matrix-core share, [1] without
+  int64_t plane_mfma_stats[2] = {0, 0};
   // closing pair kernels of polarizable calls (admp_pair_rider_stats): [0] rode in an x pass, [1] launched on their own
   int64_t pair_rider_stats[2] = {0, 0};
   const void* U_src = nullptr;  // admp_set_dipole_source: read-only initial dipoles of the NEXT polarizable evaluation
@@ -1097,8 +1099,10 @@ struct Engine : EngineBase {
       const T* tw = dft_tw.as<T>();
       const bool planes = dft_zy_fits<T>(K);         // z and y lines of a plane in one workgroup (dft_kernels.hip)
       ARG_CHECK(!sp || planes, "internal: plane spread without the plane kernels");
-      if (planes && sp) { TIMED("dft_spread_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, sp); }
-      else if (planes) { TIMED("dft_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0); }
+      int mf = 0;
+      if (planes && sp) { TIMED("dft_spread_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, sp, &mf); }
+      else if (planes) { TIMED("dft_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, nullptr, &mf); }
+      if (planes) ++plane_mfma_stats[mf ? 0 : 1];
       else {
         { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 0); }
         { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec_p, 0); }
@@ -1110,7 +1114,11 @@ struct Engine : EngineBase {
       ++xpass_stats[ct ? 0 : 1];
       { TIMED("dft_x_kspace"); launch_dft_x_pass<T>(stream, K, tw, spec_p, tabs, Ed, slot, ct, rider, prider); }
       bool added;
-      if (planes) { TIMED("dft_yz_inv"); added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum); }
+      if (planes) {
+        TIMED("dft_yz_inv");
+        added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum, nullptr, &mf);
+        ++plane_mfma_stats[mf ? 0 : 1];
+      }
       else {
         { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec_p, 1); }
         { TIMED("dft_z_c2r"); added = launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum); }
@@ -3444,6 +3452,12 @@ int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out2, "null");
     for (int k = 0; k < 2; ++k) { out2[k] = e.xpass_stats[k]; if (reset) e.xpass_stats[k] = 0; }
+  });
+}
+int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(out2, "null");
+    for (int k = 0; k < 2; ++k) { out2[k] = e.plane_mfma_stats[k]; if (reset) e.plane_mfma_stats[k] = 0; }
   });
 }
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,

@@ -213,7 +213,8 @@ template <class T>
 bool dft_zy_spread_fits(const int K[3], int na);
 template <class T>
 bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec, int inverse, int nb = 1, long mesh_stride = 0,
-                   long spec_stride = 0, T* accum = nullptr, const PlaneSpread<T>* sp = nullptr /* forward only */);
+                   long spec_stride = 0, T* accum = nullptr, const PlaneSpread<T>* sp = nullptr /* forward only */,
+                   int* mfma_share = nullptr /* out: 1 where the launch carries a matrix-core share (plane_mfma_plan.h) */);
 template <class T>
 bool launch_dft_z(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec, int inverse, int nb = 1,
                   long mesh_stride = 0, long spec_stride = 0,                                     // r2c / c2r along z

@@ -436,6 +436,12 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(self._h, self._L.admp_xpass_stats(self._h, out, 1 if reset else 0), 'admp_xpass_stats')
         return {'circulant': int(out[0]), 'transforms': int(out[1])}
 
+    def plane_mfma_stats(self, reset=False):
+        """Launches of the plane kernels of the direct-DFT mesh convolution so far (admp_plane_mfma_stats): dict of counters."""
+        out = (ctypes.c_int64 * 2)()
+        _lib.check(self._h, self._L.admp_plane_mfma_stats(self._h, out, 1 if reset else 0), 'admp_plane_mfma_stats')
+        return {'matrix_share': int(out[0]), 'vector': int(out[1])}
+
     def pair_rider_stats(self, reset=False):
         """Where the closing pair kernels of the polarizable calls ran so far (admp_pair_rider_stats): dict of counters."""
         out = (ctypes.c_int64 * 2)()

@@ -26,3 +26,5 @@ for k in range(steps):
     seq.append(int(f.n_cycle))
 print('ms per step (synchronised):', ' '.join('%.3f' % m for m in ms[-12:]))
 print(name, 'updates per step:', ''.join(str(min(s, 9)) for s in seq), 'mean %.2f' % (sum(seq[5:]) / float(len(seq) - 5)))
+if hasattr(f, 'plane_mfma_stats'):
+    print(name, 'plane launches (matrix share, vector):', f.plane_mfma_stats(), ' SCF forms:', f.scf_stats())
