@@ -56,6 +56,9 @@ PROTOTYPES = {
     'admp_md_kick_drift': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp]),
     'admp_md_langevin': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _u64, _u64, _vp]),
     'admp_md_random': (_i32, [_vp, _i32, _i64, _u64, _u64, _u32, _vp]),
+    'admp_md_bonded_box': (_i32, [_vp, _vp, _dp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'admp_md_virial': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    'admp_md_scale': (_i32, [_vp, _i32, _vp, _vp, _dbl]),
     'admp_neighbor_count': (_i32, [_vp, _i32, _vp, _dp, _dbl, _c.POINTER(_i64)]),
     'admp_neighbor_fill': (_i32, [_vp, _vp]),
     'admp_set_pairs_from_positions': (_i32, [_vp, _vp, _dp, _dbl]),

@@ -331,6 +331,11 @@ struct EngineBase {
   virtual void md_langevin(int n, void* pos, void* vel, const void* grad, const void* inv_mass, double half_dt_acc, double dt,
                            double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin_dev) = 0;
   virtual void md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) = 0;
+  virtual void md_bonded_box(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na,
+                             const int32_t* aidx, const void* apar, double* E_dev, double* S_dev) = 0;
+  virtual void md_virial(int n, const void* pos, const void* vel, const void* grad, const void* inv_mass, uint64_t seed,
+                         uint64_t step, double* out_dev) = 0;
+  virtual void md_scale(int n, void* pos, void* vel, double mu) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -2486,6 +2491,42 @@ struct Engine : EngineBase {
     launch_md_random<T>(stream, kind, n, seed, step, stream_id, out);
     HIP_TRY(hipGetLastError());
   }
+  // the isotropic barostat's three (admp_amd/md.py CRescaleBarostat): every argument is checked before the first launch
+  void md_bonded_box(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na, const int32_t* aidx,
+                     const void* apar, double* E_dev, double* S_dev) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(box && E_dev && S_dev && nb >= 0 && na >= 0 && nb <= INT_MAX / 4 - na, "bad argument");
+    ARG_CHECK(nb + na == 0 || pos, "positions missing");
+    ARG_CHECK((nb == 0 || (bidx && bpar)) && (na == 0 || (aidx && apar)), "bond / angle lists missing");
+    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
+    double inv[9], vol;
+    Box<T> bx = make_box(box, inv, &vol);
+    TIMED("md_bonded_box");
+    launch_md_bonded_box<T>(stream, nb, bidx, reinterpret_cast<const T*>(bpar), na, aidx, reinterpret_cast<const T*>(apar),
+                            reinterpret_cast<const T*>(pos), bx, E_dev, S_dev);
+    HIP_TRY(hipGetLastError());
+  }
+  void md_virial(int n, const void* pos, const void* vel, const void* grad_, const void* inv_mass, uint64_t seed, uint64_t step,
+                 double* out_dev) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && out_dev && (n == 0 || (pos && vel && grad_ && inv_mass)), "bad argument");
+    TIMED("md_virial");
+    HIP_TRY(hipMemsetAsync(out_dev, 0, 21 * sizeof(double), stream));
+    launch_md_virial<T>(stream, n, reinterpret_cast<const T*>(pos), reinterpret_cast<const T*>(vel),
+                        reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), seed, step, out_dev);
+    HIP_TRY(hipGetLastError());
+  }
+  void md_scale(int n, void* pos, void* vel, double mu) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && (n == 0 || (pos && vel)), "bad argument");
+    ARG_CHECK(std::isfinite(mu) && mu > 0.0 && std::isfinite(1.0 / mu), "the scale factor must be finite and positive");
+    TIMED("md_scale");
+    launch_md_scale<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), mu, 1.0 / mu);
+    HIP_TRY(hipGetLastError());
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3393,6 +3434,20 @@ int admp_md_langevin(admp_handle* h, int n_atoms, void* positions, void* velocit
 }
 int admp_md_random(admp_handle* h, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) {
   return guarded(h, [&](EngineBase& e) { e.md_random(kind, n, seed, step, stream, out); });
+}
+int admp_md_bonded_box(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
+                       const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
+                       double* S_dev) {
+  return guarded(h, [&](EngineBase& e) {
+    e.md_bonded_box(positions, box, n_bonds, bond_idx, bond_par, n_angles, angle_idx, angle_par, E_dev, S_dev);
+  });
+}
+int admp_md_virial(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad,
+                   const void* inv_mass, uint64_t seed, uint64_t step, double* out_dev) {
+  return guarded(h, [&](EngineBase& e) { e.md_virial(n_atoms, positions, velocities, grad, inv_mass, seed, step, out_dev); });
+}
+int admp_md_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, double mu) {
+  return guarded(h, [&](EngineBase& e) { e.md_scale(n_atoms, positions, velocities, mu); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

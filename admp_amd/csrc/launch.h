@@ -672,5 +672,16 @@ void launch_md_langevin(hipStream_t st, int n, T* pos, T* vel, const T* grad, co
                         double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin);
 template <class T>
 void launch_md_random(hipStream_t st, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out);
+// isotropic barostat: S (9 doubles) += sum shift (x) dE/dd over the bond / angle vectors that cross the cell, E as
+// launch_md_bonded; out[0..8] += sum m v (x) v, out[9..17] += sum r (x) g, out[18..20] = normals of (seed, step, stream 2,
+// atom 0) (launched for n = 0 too); r *= mu, v *= inv_mu
+template <class T>
+void launch_md_bonded_box(hipStream_t st, int nb, const int* bidx, const T* bpar, int na, const int* aidx, const T* apar,
+                          const T* pos, const Box<T>& box, double* E, double* S);
+template <class T>
+void launch_md_virial(hipStream_t st, int n, const T* pos, const T* vel, const T* grad, const T* inv_mass, uint64_t seed,
+                      uint64_t step, double* out);
+template <class T>
+void launch_md_scale(hipStream_t st, int n, T* pos, T* vel, double mu, double inv_mu);
 
 }  // namespace admp

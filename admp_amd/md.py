@@ -9,6 +9,11 @@ logs, so an MD step adds no host synchronisation of its own to those of the calc
 (admp_md_langevin) that draws its noise in registers from a counter-based generator (csrc/md_math.h: Philox-4x32-10, a
 function of (seed, step, stream, atom) alone, so a restart at any step repeats the noise); `maxwell_boltzmann` draws the
 initial velocities from the same generator (admp_md_random).  Used by examples/md/nvt_water.py.
+
+`CRescaleBarostat` is the isotropic barostat: stochastic cell rescaling (Bernetti and Bussi 2020).  One application reads the
+two 3x3 sums a pressure needs and its normal from one launch (admp_md_virial), takes dE/dbox summed over the caller's
+calculators (`HarmonicBonded.get_box_gradient` is the bonded share, admp_md_bonded_box), and rescales positions, velocities
+(admp_md_scale) and the caller's box.  Used by examples/md/npt_water.py.
 """
 import ctypes
 
@@ -19,7 +24,22 @@ from . import _lib
 from ._device import HipForceBase
 
 KB = 0.0083144626          # kJ/mol/K
-STREAM_LANGEVIN, STREAM_MAXWELL = 0, 1      # csrc/md_math.h: the two users of the generator never share a counter
+STREAM_LANGEVIN, STREAM_MAXWELL, STREAM_BAROSTAT = 0, 1, 2      # csrc/md_math.h: the users of the generator never share a counter
+BAR_PER_KJ_MOL_A3 = 16605.39      # 1 kJ/mol/A^3 in bar
+
+
+def _checked(o, n_atoms, **tensors):
+    """the library reads and writes raw pointers: anything but (n,3) contiguous tensors of the handle's precision on its
+    device would be read or written out of bounds"""
+    for name, t in tensors.items():
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == o._device.index):
+            raise ValueError('%s must be a tensor on the handle\'s device' % name)
+        if t.dtype != o._dtype:
+            raise ValueError('%s must be of the handle\'s precision (%s), got %s' % (name, o._dtype, t.dtype))
+        if tuple(t.shape) != (n_atoms, 3):
+            raise ValueError('%s must have shape (%d, 3), got %s' % (name, n_atoms, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
 
 
 class HarmonicBonded(HipForceBase):
@@ -69,6 +89,25 @@ class HarmonicBonded(HipForceBase):
         g = torch.zeros((self.n_atoms, 3), dtype=self._dtype, device=self._device)
         self.add_forces(positions, box, g)
         return np.float64(self.energy()), self._like(g, positions)
+
+    def get_energy_and_box_gradient(self, positions, box):
+        """(E, dE/dbox (3,3)) at fixed Cartesian positions -- the calculators' convention.  Only the bond and angle vectors
+        that the minimum image translates by a lattice vector contribute: the kernel sums shift^T (x) dE/dd over them
+        (admp_md_bonded_box), dE/dbox = box^-T S is formed here.  One launch, one host read; `energy_words` is not touched."""
+        self._use_current_stream()
+        pos = self._real(positions, (self.n_atoms, 3))
+        h = np.array(box.detach().cpu().numpy() if isinstance(box, torch.Tensor) else box, dtype=np.float64).reshape(3, 3)
+        boxa, _ = self._harr('box', h, 9)
+        words = torch.zeros(11, dtype=torch.float64, device=self._device)      # (E bonds, E angles, S row-major)
+        P = self._ptr
+        _lib.check(self._h, self._L.admp_md_bonded_box(self._h, P(pos), boxa, len(self._bidx), P(self._bidx), P(self._bpar),
+                                                       len(self._aidx), P(self._aidx), P(self._apar), P(words), P(words[2:])),
+                   'admp_md_bonded_box')
+        w = words.cpu().numpy()
+        return np.float64(w[0] + w[1]), np.linalg.inv(h).T @ w[2:].reshape(3, 3)
+
+    def get_box_gradient(self, positions, box):
+        return self.get_energy_and_box_gradient(positions, box)[1]
 
 
 class VelocityVerlet:
@@ -163,18 +202,7 @@ class Langevin:
         self.ekin_word = torch.zeros(1, dtype=torch.float64, device=handle_owner._device)
 
     def _checked(self, **tensors):
-        """the library reads and writes raw pointers: anything but (n,3) contiguous tensors of the handle's precision on its
-        device would be read or written out of bounds"""
-        o = self._o
-        for name, t in tensors.items():
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == o._device.index):
-                raise ValueError('%s must be a tensor on the handle\'s device' % name)
-            if t.dtype != o._dtype:
-                raise ValueError('%s must be of the handle\'s precision (%s), got %s' % (name, o._dtype, t.dtype))
-            if tuple(t.shape) != (self.n_atoms, 3):
-                raise ValueError('%s must have shape (%d, 3), got %s' % (name, self.n_atoms, tuple(t.shape)))
-            if not t.is_contiguous():
-                raise ValueError('%s must be contiguous' % name)
+        _checked(self._o, self.n_atoms, **tensors)
 
     def kick_drift(self, pos, vel, grad, want_ekin=False):
         """first half: r(t + dt) and the velocities after the friction step; then step += 1"""
@@ -210,3 +238,89 @@ class Langevin:
     def temperature(self, n_dof=None):
         """(host read) 2 Ekin / (n_dof kB) of the last call with want_ekin=True; n_dof defaults to 3 N"""
         return 2.0 * self.kinetic_energy() / ((3 * self.n_atoms if n_dof is None else n_dof) * KB)
+
+
+class CRescaleBarostat:
+    """Isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020) at `temperature` (K) and
+    `pressure_bar`, with relaxation time `tau_p_fs` and isothermal compressibility `compressibility_per_bar`; units as in
+    VelocityVerlet, pressures in bar.  With eps = ln V, one application advances the cell by dt_p (the caller applies it every
+    dt_p / dt steps, after the closing kick):
+
+        d eps = (beta_T / tau_p) (P_inst - P0) dt_p + sqrt(2 kB T beta_T dt_p / (V tau_p)) xi,   mu = exp(d eps / 3)
+        r <- mu r,  box <- mu box,  v <- v / mu
+
+    xi is the first normal of (seed, step, stream 2, atom 0) of csrc/md_math.h; `step` counts the applications and may be set
+    (a restart draws the same noise again).  P_inst = (2 K / 3 - dE/d eps) / V with dE/d eps = (sum_ab box_ab (dE/dbox)_ab +
+    sum_i r_i . g_i) / 3: `get_box_gradient` of every calculator is dE/dbox at fixed Cartesian positions, so the positions'
+    share is added here.  The caller sums dE/dbox over its calculators; the barostat does not know them."""
+    ACC = VelocityVerlet.ACC
+
+    def __init__(self, handle_owner, masses, dt_p_fs, temperature, pressure_bar, tau_p_fs, compressibility_per_bar, seed):
+        self._o = handle_owner
+        self.dt_p = float(dt_p_fs)
+        self.T = float(temperature)
+        self.P0 = float(pressure_bar)
+        self.tau_p = float(tau_p_fs)
+        self.beta_T = float(compressibility_per_bar)
+        self.seed = int(seed)
+        self.step = 0
+        if self.T < 0 or self.beta_T < 0 or self.dt_p < 0 or not self.tau_p > 0 or not 0 <= self.seed < 2 ** 64:
+            raise ValueError('temperature, compressibility and dt_p must not be negative; tau_p must be positive; the seed is an '
+                             'unsigned 64-bit number')
+        if not all(np.isfinite(x) for x in (self.dt_p, self.T, self.P0, self.tau_p, self.beta_T)):
+            raise ValueError('the barostat\'s parameters must be finite')
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if not np.all(m > 0):
+            raise ValueError('masses must be positive')
+        self.n_atoms = len(m)
+        self.inv_mass = handle_owner._real(1.0 / m)
+        self._words = torch.zeros(21, dtype=torch.float64, device=handle_owner._device)
+
+    def sums(self, pos, vel, grad):
+        """(kin, rg, xi): kin (3,3) = sum m v (x) v in kJ/mol (its trace is twice the kinetic energy), rg (3,3) = sum r (x) g
+        with g = +dE/dr in kJ/mol, xi the normal of this application.  One launch and one host read; sums in double."""
+        _checked(self._o, self.n_atoms, pos=pos, vel=vel, grad=grad)
+        o = self._o
+        o._use_current_stream()
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_virial(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass), self.seed,
+                                             int(self.step) & (2 ** 64 - 1), P(self._words)), 'admp_md_virial')
+        w = self._words.cpu().numpy()
+        return w[0:9].reshape(3, 3) / self.ACC, w[9:18].reshape(3, 3).copy(), float(w[18])
+
+    @staticmethod
+    def _cell(box):
+        h = np.asarray(box, dtype=np.float64).reshape(3, 3)
+        return h, abs(float(np.linalg.det(h)))
+
+    def pressure(self, box, dEdbox_total, kin, rg):
+        """(host) P_inst in bar: (2 K / 3 - dE/d eps) / V"""
+        h, vol = self._cell(box)
+        dE_deps = (float((h * np.asarray(dEdbox_total, dtype=np.float64)).sum()) + float(np.trace(rg))) / 3.0
+        return (float(np.trace(kin)) / 3.0 - dE_deps) / vol * BAR_PER_KJ_MOL_A3
+
+    def pressure_tensor(self, box, dEdbox_total, kin, rg):
+        """(host) (kin - box^T dE/dbox - rg) / V in bar, for logging: a third of its trace is `pressure`.  On a triclinic cell
+        the reference's k-point order and spread operators leave it unsymmetric."""
+        h, vol = self._cell(box)
+        return (np.asarray(kin) - h.T @ np.asarray(dEdbox_total, dtype=np.float64) - np.asarray(rg)) / vol * BAR_PER_KJ_MOL_A3
+
+    def apply(self, pos, vel, box, p_inst, xi):
+        """one application: d eps and mu on the host in double, positions and velocities rescaled by one kernel, `box` (a
+        float64 ndarray) multiplied IN PLACE by mu; then step += 1.  Returns mu."""
+        _checked(self._o, self.n_atoms, pos=pos, vel=vel)
+        if not (isinstance(box, np.ndarray) and box.dtype == np.float64 and box.size == 9 and box.flags.writeable):
+            raise ValueError('box must be a writeable float64 ndarray of 9 elements (it is scaled in place)')
+        _, vol = self._cell(box)
+        kT_bar = KB * self.T * BAR_PER_KJ_MOL_A3 / vol                      # kB T / V in bar
+        d_eps = self.beta_T / self.tau_p * (float(p_inst) - self.P0) * self.dt_p + \
+            np.sqrt(2.0 * kT_bar * self.beta_T * self.dt_p / self.tau_p) * float(xi)
+        mu = float(np.exp(d_eps / 3.0))
+        if not (np.isfinite(mu) and mu > 0.0):
+            raise ValueError('the scale factor is not finite (P_inst %r, xi %r)' % (p_inst, xi))
+        o = self._o
+        o._use_current_stream()
+        _lib.check(o._h, o._L.admp_md_scale(o._h, self.n_atoms, o._ptr(pos), o._ptr(vel), mu), 'admp_md_scale')
+        box *= mu
+        self.step += 1
+        return mu

@@ -1,6 +1,6 @@
-"""What the MD drivers of this directory share (nve_water.py, nvt_water.py): the water force field's bonded constants, the
-command-line arguments, the calculators with their Verlet lists and the `forces` closure, and the capped steepest descent
-that relaxes the synthetic box before a run."""
+"""What the MD drivers of this directory share (nve_water.py, nvt_water.py, npt_water.py): the water force field's bonded
+constants, the command-line arguments, the calculators with their Verlet lists, the `forces` closure and the `box_gradient`
+closure of the NPT driver, and the capped steepest descent that relaxes the synthetic box before a run."""
 import os
 import sys
 import types
@@ -52,7 +52,9 @@ def add_arguments(ap):
 
 def setup(opt):
     """calculators, lists and forces of the box of opt.waters molecules; returns a namespace with pos (device tensor), box,
-    n_mol, dtype, pme (the calculator that lends its handle and stream to the integrator), nbl, forces, epot_now, state"""
+    n_mol, dtype, pme (the calculator that lends its handle and stream to the integrator), nbl, forces, epot_now, state; for
+    the NPT driver also tt (the pair-interaction object), par (the parameter tensors) and box_gradient.  `box` is ONE ndarray
+    that every closure reads at each call: a barostat that scales it in place changes the cell for all of them."""
     settings.PRECISION = 'single' if opt.single else 'double'
     if opt.pol:
         settings.POL_CONV = opt.thresh      # a tight SCF: the reference's default (10) is too loose for energy conservation
@@ -139,8 +141,20 @@ def setup(opt):
     def epot_now(e123):
         return float(e123) + bond.energy()
 
+    def box_gradient(p, pairs):
+        """dE/dbox (3,3) at fixed Cartesian positions summed over the four calculators, at the list and (--pol) from the
+        dipoles of the last forces() call; four evaluations, used every --nbaro steps by npt_water.py"""
+        if opt.pol:
+            d = pme.get_energy_and_box_gradient(p, box, pairs, Q, pol, thole, mS, pS, dS, U_init=state['U'])[1]
+        else:
+            d = pme.get_energy_and_box_gradient(p, box, pairs, Q, mS)[1]
+        d = d + disp.get_energy_and_box_gradient(p, box, pairs, cl, mS)[1]
+        d = d + tt_obj.get_energy_and_box_gradient(p, box, pairs, mS, a_, b_, q_, c6)[1]
+        return d + bond.get_energy_and_box_gradient(p, box)[1]
+
+    par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
-                                 forces=forces, epot_now=epot_now, state=state)
+                                 forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient)
 
 
 def minimize(w, opt, pos):

@@ -281,7 +281,18 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       admp_md_kick_drift with dt = 0.
  *   admp_md_random      the same generator written to memory: kind 0: out (n,4) uint32, the raw words; kind 1: out (n,3)
  *                       real, the normals; counter = (atom, step low, step high, stream), key = (seed low, seed high)
- * The last two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE). */
+ *   admp_md_bonded_box  the box-gradient pass of admp_md_bonded (same lists): for every bond and angle vector the lattice
+ *                       translation of the minimum image, shift = d_min - d_raw; S_dev (9 doubles, row-major) +=
+ *                       sum shift^T (x) dE/dd; E_dev[0..1] += the energies as above; no gradient is written.  The caller
+ *                       forms dE/dbox = box^-T S (fixed Cartesian positions).  ADMP_E_ARG for a singular or non-finite box.
+ *   admp_md_virial      one pass over the atoms for what a pressure needs: out_dev (21 doubles, zeroed by the call):
+ *                       [0..8] = sum_i v_i (x) v_i / inv_mass_i, [9..17] = sum_i r_i (x) grad_i, [18..20] = the three normals
+ *                       of (seed, step, stream 2, atom 0) in double.  Products and sums in double on both precisions.
+ *                       n_atoms = 0 writes zeros and the normals.
+ *   admp_md_scale       r *= mu, v *= 1 / mu in place (isotropic cell rescaling; the caller scales its box); mu from the
+ *                       host in double, rounded to the handle's precision once.  ADMP_E_ARG unless mu is finite and > 0.
+ * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE);
+ * the last three check every argument (n < 0 included) before anything is launched. */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
                    const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
                    void* grad_inout);
@@ -291,6 +302,12 @@ int admp_md_langevin(admp_handle* h, int n_atoms, void* positions, void* velocit
                      double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
                      double* ekin_dev);
 int admp_md_random(admp_handle* h, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out);
+int admp_md_bonded_box(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
+                       const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
+                       double* S_dev);
+int admp_md_virial(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad,
+                   const void* inv_mass, uint64_t seed, uint64_t step, double* out_dev);
+int admp_md_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, double mu);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
