@@ -46,8 +46,9 @@ def covalent_to_csr(covalent_map, n_atoms):
         np.add.at(ptr, rows + 1, 1)
         ptr = np.cumsum(ptr)
     val = np.asarray(val).astype(np.int64)
-    if val.size and (val.min() < 0 or val.max() > 15):
-        raise ValueError('covalent_map entries must lie in 0..15')
+    if val.size and (val.min() < 0 or val.max() > 7):
+        # three bits of a neighbour-table entry (28..30) hold the class; bit 31 marks a charge-only partner
+        raise ValueError('covalent_map entries must lie in 0..7 (got %d..%d)' % (val.min(), val.max()))
     return (np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(col, dtype=np.int32),
             np.ascontiguousarray(val, dtype=np.int32))
 

@@ -9,6 +9,7 @@
 // The minimum-image distance uses the same arithmetic as the pair kernel (min_image, admp/spatial.py:13-32).
 #include <hipcub/hipcub.hpp>
 
+#include "cell_plan.h"
 #include "launch.h"
 
 namespace admp {
@@ -238,8 +239,7 @@ __global__ __launch_bounds__(256) void k_cell_rows(Topology top, const T* __rest
 // atoms j = l, l + 16, ...), positions staged through LDS.  Two launches (count, fill) replace the six of the cell
 // path, whose dispatch latency dominates the rebuild at this size (3072 atoms: 0.21 ms -> see DESIGN.md 6).
 // Row order: lane-major, j ascending within a lane -- fixed and reproducible.
-constexpr int kBruteMax = 4096;
-constexpr int kBruteTile = 1024;
+constexpr int kBruteTile = 1024;      // (kBruteMax: cell_plan.h)
 
 template <class T, int MODE>
 __global__ __launch_bounds__(256) void k_brute_rows(Topology top, const T* __restrict__ pos, Box<T> box, T rc2,
@@ -307,12 +307,7 @@ template <class T>
 int cell_count_pairs(hipStream_t st, int na, const T* pos, const Box<T>& box, const double* heights, double rc,
                      CellScratch& cs, long long* n_pairs) {
   CellGrid cg;
-  for (int d = 0; d < 3; ++d) {
-    int n = (int)(heights[d] / rc);
-    cg.n[d] = n < 1 ? 1 : (n > 1024 ? 1024 : n);
-  }
-  // keep the cell table bounded for huge dilute boxes
-  while ((long)cg.n[0] * cg.n[1] * cg.n[2] > 64L * 1024 * 1024) { for (int d = 0; d < 3; ++d) cg.n[d] = (cg.n[d] + 1) / 2; }
+  cell_grid_dims(heights, rc, cg.n);      // (cell_plan.h: floor(height / rc), bounded for huge dilute boxes)
   cg.ncell = cg.n[0] * cg.n[1] * cg.n[2];
   cs.n[0] = cg.n[0]; cs.n[1] = cg.n[1]; cs.n[2] = cg.n[2];
   if (cs.ensure(na, cg.ncell) != 0) return (int)hipErrorOutOfMemory;
@@ -376,11 +371,7 @@ int cell_build_table(hipStream_t st, const Topology& top, const T* pos, const Bo
     return 0;
   }
   CellGrid cg;
-  for (int d = 0; d < 3; ++d) {
-    int n = (int)(heights[d] / rc);
-    cg.n[d] = n < 1 ? 1 : (n > 1024 ? 1024 : n);
-  }
-  while ((long)cg.n[0] * cg.n[1] * cg.n[2] > 64L * 1024 * 1024) { for (int d = 0; d < 3; ++d) cg.n[d] = (cg.n[d] + 1) / 2; }
+  cell_grid_dims(heights, rc, cg.n);
   cg.ncell = cg.n[0] * cg.n[1] * cg.n[2];
   cs.n[0] = cg.n[0]; cs.n[1] = cg.n[1]; cs.n[2] = cg.n[2];
   if (cs.ensure(na, cg.ncell) != 0) return (int)hipErrorOutOfMemory;
@@ -430,17 +421,19 @@ int CellScratch::ensure(int na, int ncell) {
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan2, pi, pi, ncell + 1, (hipStream_t)0);
   if (scan2 > scan) scan = scan2;
   scan += 256;
-  if (na > cap_atoms || ncell > cap_cells || scan > scan_bytes) {
+  // the partial counts are 16 words per atom up to kBruteMax atoms and 4 above: fewer atoms can need MORE words
+  const size_t part = cell_partial_words(na);
+  if (na > cap_atoms || ncell > cap_cells || scan > scan_bytes || part > cap_part) {
     release();
-    cap_atoms = na; cap_cells = ncell; scan_bytes = scan;
+    cap_atoms = na; cap_cells = ncell; scan_bytes = scan; cap_part = part;
     if (hipMalloc(&start, sizeof(int) * (ncell + 1)) != hipSuccess) return -1;
     if (hipMalloc(&cursor, sizeof(int) * (ncell + 1)) != hipSuccess) return -1;
     if (hipMalloc(&sorted, sizeof(int) * (size_t)na) != hipSuccess) return -1;
     if (hipMalloc(&count, sizeof(long long) * ((size_t)na + 1)) != hipSuccess) return -1;
     if (hipMalloc(&offs, sizeof(long long) * ((size_t)na + 1)) != hipSuccess) return -1;
     if (hipMalloc(&spos, 32 * (size_t)na + 32) != hipSuccess) return -1;
-    // partial row lengths: 4 per row (cell sweep) or 16 per row (brute-force rows of tiny systems)
-    if (hipMalloc(&deg4, sizeof(int) * (na <= 4096 ? 16 : 4) * ((size_t)na + 1)) != hipSuccess) return -1;
+    // partial row lengths: 4 per row (cell sweep) or 16 per row (brute-force rows of tiny systems), cap_part words
+    if (hipMalloc(&deg4, sizeof(int) * cap_part) != hipSuccess) return -1;
     if (hipMalloc(&scan_tmp, scan) != hipSuccess) return -1;
     (void)hipMemset(count, 0, sizeof(long long) * ((size_t)na + 1));   // count[na] stays 0: the scans' total slot
   }
@@ -455,6 +448,7 @@ void CellScratch::release() {
   count = offs = nullptr;
   scan_tmp = nullptr;
   cap_atoms = cap_cells = 0;
+  cap_part = 0;
   scan_bytes = 0;
 }
 

@@ -2531,6 +2531,7 @@ struct Engine : EngineBase {
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
   int nb_na = 0; const T* nb_pos = nullptr; Box<T> nb_box; double nb_rc = 0;
+  long long nb_found = 0;      // pairs the pending count reported
   void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) override {
     ARG_CHECK(na > 0 && pos && box && rc > 0 && n_pairs, "bad argument");
     double inv[9], vol;
@@ -2544,14 +2545,19 @@ struct Engine : EngineBase {
     TIMED("neighbor_count");
     int r = cell_count_pairs<T>(stream, na, nb_pos, nb_box, heights, rc, cells, &n);
     if (r != 0) throw Err{ADMP_E_HIP, std::string("cell_count_pairs: ") + hipGetErrorString((hipError_t)r)};
+    nb_found = n;
     *n_pairs = (int64_t)n;
   }
   void nbr_fill(int32_t* pairs) override {
-    ARG_CHECK(nb_pos && pairs, "admp_neighbor_count must precede admp_neighbor_fill");
+    ARG_CHECK(nb_pos, "admp_neighbor_count must precede admp_neighbor_fill");
+    // no pair within rc (one atom, a dilute gas) is a valid answer: nothing to write, the output may be NULL
+    ARG_CHECK(pairs || nb_found == 0, "null output for a non-empty pair list");
+    const T* pos = nb_pos;
+    nb_pos = nullptr;                            // the pending count is spent, whatever the fill returns
+    if (nb_found == 0) return;
     TIMED("neighbor_fill");
-    int r = cell_fill_pairs<T>(stream, nb_na, nb_pos, nb_box, nb_rc, cells, pairs);
+    int r = cell_fill_pairs<T>(stream, nb_na, pos, nb_box, nb_rc, cells, pairs);
     if (r != 0) throw Err{ADMP_E_HIP, std::string("cell_fill_pairs: ") + hipGetErrorString((hipError_t)r)};
-    nb_pos = nullptr;
   }
 
   // admp_prune_pairs: from now on the calculators walk the entries of the current table that lie below rc (see EngineBase::pruned)

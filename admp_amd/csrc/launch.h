@@ -567,9 +567,10 @@ struct CellScratch {
   int* start = nullptr; int* cursor = nullptr; int* sorted = nullptr;
   long long* count = nullptr; long long* offs = nullptr;
   void* spos = nullptr;        // cell-sorted packed records (x, y, z, atom id), 4 reals (<= 32 B) per atom
-  int* deg4 = nullptr;         // 4 partial row lengths per atom (one per lane of k_cell_rows)
+  int* deg4 = nullptr;         // partial row lengths: 4 per atom (lanes of k_cell_rows) or 16 (k_brute_rows), cap_part words
   void* scan_tmp = nullptr; size_t scan_bytes = 0;
   int cap_atoms = 0, cap_cells = 0;
+  size_t cap_part = 0;         // words behind deg4 (cell_plan.h cell_partial_words: NOT monotonic in the atom count)
   int ensure(int na, int ncell);
   void release();
 };

@@ -253,7 +253,17 @@ int admp_pscale_grad(admp_handle* h, const void* positions, const double* box, c
  * of the reference's drivers (examples/water_1024/run_admp.py:109-112): the producer of `pairs`.
  * Cell list on the GPU, any lattice with rc <= half of every box height.  Two phases so the caller can size
  * the output: count -> allocate (n_pairs, 2) int32 on the device -> fill (rows i < j, grouped by i, j ascending
- * within a cell sweep).  positions is a DEVICE pointer to (n_atoms, 3) reals and must stay valid until fill. */
+ * within a cell sweep).  positions is a DEVICE pointer to (n_atoms, 3) reals and must stay valid until fill.
+ *   Empty list: no pair within rc (one atom, a dilute gas) is a valid answer.  count then reports 0, and fill accepts a
+ *   NULL pairs_out (a zero-row device array has no address), writes nothing and ends the pending count like any fill;
+ *   NULL after a non-zero count is ADMP_E_ARG.  A handle may be given a new topology of any size afterwards (the search's
+ *   scratch is sized per call, tests/test_gpu_neighbour.py).
+ *   Covalent classes: the table entries built by admp_set_pairs / admp_set_pairs_from_positions carry the class of
+ *   admp_set_topology in three bits, so classes are 0..7 (admp_amd._device.covalent_to_csr refuses more).
+ *   Precision: a pair is listed when the minimum-image distance EVALUATED IN THE HANDLE'S PRECISION (min_image: d = r_i - r_j,
+ *   s = d box^-1, d = (s - floor(s + 1/2)) box) is below rc.  In double this is the float64 reference's set exactly.  In
+ *   single a pair may be classified differently only within band = 8 * 2^-24 * (max |position component| + largest column
+ *   sum of |box|) of rc (inputs rounded to f32, one subtraction, two 3-term products); measured margins: profiles/README.md. */
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc,
                         int64_t* n_pairs);
 int admp_neighbor_fill(admp_handle* h, int32_t* pairs_out);
