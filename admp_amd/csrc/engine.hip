@@ -336,6 +336,12 @@ struct EngineBase {
   virtual void md_virial(int n, const void* pos, const void* vel, const void* grad, const void* inv_mass, uint64_t seed,
                          uint64_t step, double* out_dev) = 0;
   virtual void md_scale(int n, void* pos, void* vel, double mu) = 0;
+  virtual void md_mts_plan(int n_atoms, int nb, const int32_t* bidx, const double* bpar, int na, const int32_t* aidx,
+                           const double* apar, int tile_atoms) = 0;
+  virtual void md_mts_step(int n, void* pos, void* vel, const void* grad_slow, const void* inv_mass, const double* box,
+                           double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc, uint64_t seed,
+                           uint64_t outer_step, double* E_dev, void* grad_fast) = 0;
+  virtual void md_mts_info(int64_t* out) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -632,6 +638,8 @@ struct Engine : EngineBase {
     if (ind.col) (void)hipFree(ind.col);
     cells.release();
     sl.release();
+    mts.ints.release();
+    mts.reals.release();
     free_programs();
     if (Eh) (void)hipHostFree(Eh);
     prof.destroy();
@@ -2527,6 +2535,74 @@ struct Engine : EngineBase {
     launch_md_scale<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), mu, 1.0 / mu);
     HIP_TRY(hipGetLastError());
   }
+  // the multiple-time-step integrator (mts_kernels.hip; admp_amd/md.py MTSLangevin): the plan of the bonded lists is made on
+  // the host (mts_plan.h) and kept on the handle until the next one replaces it
+  struct MtsState {
+    bool have = false;
+    int n_atoms = 0, tile_atoms = 0, max_component = 0, n_bonds = 0, n_angles = 0, threads = 0;
+    size_t lds_bytes = 0;
+    int64_t launches = 0;
+    MtsTiles<T> tiles{};
+    DevBuf ints, reals;
+  } mts;
+  void md_mts_plan(int n_atoms, int nb, const int32_t* bidx, const double* bpar, int na, const int32_t* aidx, const double* apar,
+                   int tile_atoms) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && nb >= 0 && na >= 0, "bad argument");
+    ARG_CHECK((nb == 0 || (bidx && bpar)) && (na == 0 || (aidx && apar)), "bond / angle lists missing");
+    const MtsPlan p = mts_make_plan(n_atoms, nb, bidx, bpar, na, aidx, apar, tile_atoms == 0 ? kMtsDefaultTileAtoms : tile_atoms);
+    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
+    // one block of ints and one of reals (the parameters rounded to the handle's precision once)
+    const std::vector<int>* iv[8] = {&p.tile_atom0, &p.atom_id, &p.tile_bond0, &p.bond_slot, &p.tile_angle0, &p.angle_slot, &p.ref0, &p.ref};
+    std::vector<int> hi;
+    size_t off[8];
+    for (int k = 0; k < 8; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
+    std::vector<T> hr(p.bond_par.begin(), p.bond_par.end());
+    hr.insert(hr.end(), p.angle_par.begin(), p.angle_par.end());
+    HIP_TRY(hipStreamSynchronize(stream));      // a step of the plan being replaced may still read the old arrays
+    mts.have = false;
+    mts.ints.need(hi.size() * sizeof(int));
+    mts.reals.need((hr.size() + 1) * sizeof(T));
+    HIP_TRY(hipMemcpy(mts.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!hr.empty()) HIP_TRY(hipMemcpy(mts.reals.p, hr.data(), hr.size() * sizeof(T), hipMemcpyHostToDevice));
+    const int* di = mts.ints.template as<int>();
+    MtsTiles<T>& m = mts.tiles;
+    m.n_tiles = p.n_tiles; m.dims = p.dims;
+    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_bond0 = di + off[2]; m.bond_slot = di + off[3];
+    m.tile_angle0 = di + off[4]; m.angle_slot = di + off[5]; m.ref0 = di + off[6]; m.ref = di + off[7];
+    m.bond_par = mts.reals.template as<T>(); m.angle_par = m.bond_par + p.bond_par.size();
+    mts.n_atoms = n_atoms; mts.tile_atoms = p.tile_atoms; mts.max_component = p.max_component; mts.n_bonds = nb; mts.n_angles = na;
+    mts.threads = mts_threads(p.tile_atoms);
+    mts.lds_bytes = mts_lds_bytes(p.dims, sizeof(T));
+    mts.have = true;
+  }
+  void md_mts_step(int n, void* pos, void* vel, const void* grad_slow, const void* inv_mass, const double* box,
+                   double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc, uint64_t seed,
+                   uint64_t outer_step, double* E_dev, void* grad_fast) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(mts.have, "admp_md_mts_plan must precede admp_md_mts_step");
+    ARG_CHECK(n == mts.n_atoms, "n_atoms differs from the plan's");
+    ARG_CHECK(n_inner >= 1, "n_inner must be at least 1");
+    ARG_CHECK(pos && vel && grad_slow && inv_mass && box, "bad argument");
+    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
+    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
+    double inv[9], vol;
+    Box<T> bx = make_box(box, inv, &vol);
+    TIMED("md_mts");
+    launch_md_mts<T>(stream, mts.tiles, mts.threads, mts.lds_bytes, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
+                     reinterpret_cast<const T*>(grad_slow), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc_outer, dt_outer,
+                     n_inner, c1, c2sq_kT_acc, seed, outer_step, E_dev, reinterpret_cast<T*>(grad_fast));
+    HIP_TRY(hipGetLastError());
+    mts.launches += 1;
+  }
+  void md_mts_info(int64_t* out) override {
+    ARG_CHECK(out, "bad argument");
+    const int64_t v[8] = {mts.have ? mts.tiles.n_tiles : 0, mts.tile_atoms, mts.max_component, mts.n_atoms, mts.n_bonds, mts.n_angles,
+                          (int64_t)mts.lds_bytes, mts.launches};
+    for (int k = 0; k < 8; ++k) out[k] = mts.have || k == 7 ? v[k] : 0;
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3454,6 +3530,21 @@ int admp_md_virial(admp_handle* h, int n_atoms, const void* positions, const voi
 }
 int admp_md_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, double mu) {
   return guarded(h, [&](EngineBase& e) { e.md_scale(n_atoms, positions, velocities, mu); });
+}
+int admp_md_mts_plan(admp_handle* h, int n_atoms, int n_bonds, const int32_t* bond_idx, const double* bond_par, int n_angles,
+                     const int32_t* angle_idx, const double* angle_par, int tile_atoms) {
+  return guarded(h, [&](EngineBase& e) { e.md_mts_plan(n_atoms, n_bonds, bond_idx, bond_par, n_angles, angle_idx, angle_par, tile_atoms); });
+}
+int admp_md_mts_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad_slow, const void* inv_mass,
+                     const double* box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc,
+                     uint64_t seed, uint64_t outer_step, double* E_dev, void* grad_fast_out) {
+  return guarded(h, [&](EngineBase& e) {
+    e.md_mts_step(n_atoms, positions, velocities, grad_slow, inv_mass, box, half_dt_acc_outer, dt_outer, n_inner, c1, c2sq_kT_acc,
+                  seed, outer_step, E_dev, grad_fast_out);
+  });
+}
+int admp_md_mts_info(admp_handle* h, int64_t* out8) {
+  return guarded(h, [&](EngineBase& e) { e.md_mts_info(out8); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

@@ -8,6 +8,7 @@
 
 #include "env.h"
 #include "frame_math.h"
+#include "mts_plan.h"
 #include "pfa_maps.h"
 #include "pme_math.h"
 #include "spline_math.h"
@@ -684,5 +685,20 @@ void launch_md_virial(hipStream_t st, int n, const T* pos, const T* vel, const T
                       uint64_t step, double* out);
 template <class T>
 void launch_md_scale(hipStream_t st, int n, T* pos, T* vel, double mu, double inv_mu);
+
+// ---- mts_kernels.hip: the multiple-time-step integrator, n_inner BAOAB steps on the bonded terms between the half kicks of
+// the slow gradient, one workgroup per tile of whole molecules.  MtsTiles: the device copy of an MtsPlan (mts_plan.h; the
+// parameters in the handle's precision).  threads = mts_threads(tile capacity), lds_bytes = mts_lds_bytes(dims, sizeof(T)).
+template <class T>
+struct MtsTiles {
+  int n_tiles;
+  MtsDims dims;
+  const int *tile_atom0, *atom_id, *tile_bond0, *bond_slot, *tile_angle0, *angle_slot, *ref0, *ref;
+  const T *bond_par, *angle_par;
+};
+template <class T>
+void launch_md_mts(hipStream_t st, const MtsTiles<T>& P, int threads, size_t lds_bytes, T* pos, T* vel, const T* grad_slow,
+                   const T* inv_mass, const Box<T>& box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1,
+                   double c2sq_kT_acc, uint64_t seed, uint64_t outer_step, double* E, T* grad_fast);
 
 }  // namespace admp

@@ -14,6 +14,10 @@ initial velocities from the same generator (admp_md_random).  Used by examples/m
 two 3x3 sums a pressure needs and its normal from one launch (admp_md_virial), takes dE/dbox summed over the caller's
 calculators (`HarmonicBonded.get_box_gradient` is the bonded share, admp_md_bonded_box), and rescales positions, velocities
 (admp_md_scale) and the caller's box.  Used by examples/md/npt_water.py.
+
+`MTSLangevin` is the multiple-time-step integrator (impulse r-RESPA with two levels): the bonded terms of a `HarmonicBonded`
+advance by n inner BAOAB steps inside one kernel, whole molecules resident in LDS (admp_md_mts_plan / admp_md_mts_step), and
+the calculators are called once per outer step.  Used by examples/md/mts_water.py.
 """
 import ctypes
 
@@ -238,6 +242,118 @@ class Langevin:
     def temperature(self, n_dof=None):
         """(host read) 2 Ekin / (n_dof kB) of the last call with want_ekin=True; n_dof defaults to 3 N"""
         return 2.0 * self.kinetic_energy() / ((3 * self.n_atoms if n_dof is None else n_dof) * KB)
+
+
+class MTSLangevin:
+    """Impulse multiple time stepping with two levels (r-RESPA; OpenMM's MTSLangevinIntegrator): the bonded terms of `bonded`
+    (a HarmonicBonded: it lends its handle, its lists and its energy words) advance by `n_inner` BAOAB steps of length
+    dt_outer / n_inner inside one kernel (admp_md_mts_step), everything the calculators compute acts once per outer step:
+
+        kick_drift:  v -= (dt_outer/2) 1e-4 grad_slow / m;  n_inner x [B A O A on the bonded terms, f at the new r, B]
+        (the calculators: grad_slow at the new r, WITHOUT the bonded terms)
+        kick:        v -= (dt_outer/2) 1e-4 grad_slow / m                                         (admp_md_kick_drift, dt = 0)
+
+    Units as in VelocityVerlet; c1 = exp(-friction dt_outer / n_inner); the noise of inner step k of outer step s is that of
+    (seed, s n_inner + k, stream 0, atom), so n_inner = 1 is `Langevin` on the summed gradient and friction 0 is NVE r-RESPA.
+    `step` counts the kick_drift calls and may be set (a restart draws the same noise again).  The atoms are integrated in
+    tiles of whole molecules (connected components of the lists) of at most `tile_atoms` atoms (None: the library's default);
+    a larger molecule is refused with ValueError.  r and v do not depend on tile_atoms, bit for bit."""
+    ACC = VelocityVerlet.ACC
+    MAX_TILE_ATOMS = 256          # csrc/mts_plan.h kMtsMaxTileAtoms
+
+    def __init__(self, bonded, masses, dt_outer_fs, n_inner, temperature=0.0, friction_per_fs=0.0, seed=0, tile_atoms=None):
+        if not isinstance(bonded, HarmonicBonded):
+            raise ValueError('bonded must be a HarmonicBonded')
+        self._o = bonded
+        self.dt = float(dt_outer_fs)
+        self.n_inner = int(n_inner)
+        self.T = float(temperature)
+        self.friction = float(friction_per_fs)
+        self.seed = int(seed)
+        self.step = 0
+        if self.T < 0 or self.friction < 0 or self.dt < 0 or not 0 <= self.seed < 2 ** 64:
+            raise ValueError('temperature, friction and dt must not be negative; the seed is an unsigned 64-bit number')
+        if self.n_inner < 1 or self.n_inner != n_inner:
+            raise ValueError('n_inner must be an integer of at least 1')
+        if tile_atoms is not None and not (tile_atoms == int(tile_atoms) and 1 <= tile_atoms <= self.MAX_TILE_ATOMS):
+            raise ValueError('tile_atoms must be None or between 1 and %d' % self.MAX_TILE_ATOMS)
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if not np.all(m > 0):
+            raise ValueError('masses must be positive')
+        if len(m) != bonded.n_atoms:
+            raise ValueError('%d masses for the %d atoms of bonded' % (len(m), bonded.n_atoms))
+        self.n_atoms = len(m)
+        self.inv_mass = bonded._real(1.0 / m)
+        self.c1 = float(np.exp(-self.friction * self.dt / self.n_inner))
+        self.c2sq_kT_acc = (1.0 - self.c1 * self.c1) * KB * self.T * self.ACC
+        self.ekin_word = torch.zeros(1, dtype=torch.float64, device=bonded._device)
+        self._tile_atoms = 0 if tile_atoms is None else int(tile_atoms)
+        self._plan()
+
+    def _plan(self):
+        """the handle keeps one plan: made here, and again by kick_drift when another MTSLangevin on the same `bonded` has
+        replaced it since"""
+        bonded = self._o
+        bidx = np.ascontiguousarray(bonded._bidx.cpu().numpy(), dtype=np.int32)
+        aidx = np.ascontiguousarray(bonded._aidx.cpu().numpy(), dtype=np.int32)
+        bpar = np.ascontiguousarray(bonded._bpar.cpu().numpy(), dtype=np.float64)
+        apar = np.ascontiguousarray(bonded._apar.cpu().numpy(), dtype=np.float64)
+        rc = bonded._L.admp_md_mts_plan(bonded._h, self.n_atoms, len(bidx), bidx.ctypes.data, bpar.ctypes.data, len(aidx),
+                                        aidx.ctypes.data, apar.ctypes.data, self._tile_atoms)
+        if rc == -1:                                                  # ADMP_E_ARG: the plan's refusal
+            msg = bonded._L.admp_last_error(bonded._h)
+            raise ValueError('admp_md_mts_plan: %s' % (msg.decode() if msg else ''))
+        _lib.check(bonded._h, rc, 'admp_md_mts_plan')
+        bonded._mts_planned_by = self
+
+    def kick_drift(self, pos, vel, grad_slow, box, fast_grad=None):
+        """first half of an outer step in one kernel: r(t + dt_outer) and the velocities short of the closing kick;
+        bonded.energy_words += (E_bonds, E_angles) at the new positions; fast_grad (optional) = the bonded gradient there;
+        then step += 1"""
+        tensors = dict(pos=pos, vel=vel, grad_slow=grad_slow)
+        if fast_grad is not None:
+            tensors['fast_grad'] = fast_grad
+        _checked(self._o, self.n_atoms, **tensors)
+        o = self._o
+        o._use_current_stream()
+        if getattr(o, '_mts_planned_by', None) is not self:
+            self._plan()
+        boxa, _ = o._harr('box', box, 9)
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_mts_step(o._h, self.n_atoms, P(pos), P(vel), P(grad_slow), P(self.inv_mass), boxa,
+                                               0.5 * self.dt * self.ACC, self.dt, self.n_inner, self.c1, self.c2sq_kT_acc,
+                                               self.seed, int(self.step) & (2 ** 64 - 1), P(o.energy_words), P(fast_grad)),
+                   'admp_md_mts_step')
+        self.step += 1
+
+    def kick(self, pos, vel, grad_slow, want_ekin=False):
+        """closing half kick of the outer step with the calculators' gradient at r(t + dt_outer); want_ekin: the kinetic energy
+        of the new velocities lands in ekin_word"""
+        _checked(self._o, self.n_atoms, pos=pos, vel=vel, grad_slow=grad_slow)
+        o = self._o
+        o._use_current_stream()
+        if want_ekin:
+            self.ekin_word.zero_()
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_kick_drift(o._h, self.n_atoms, P(pos), P(vel), P(grad_slow), P(self.inv_mass),
+                                                 0.5 * self.dt * self.ACC, 0.0, P(self.ekin_word) if want_ekin else None),
+                   'admp_md_kick_drift')
+
+    def kinetic_energy(self):
+        """(host read) sum m v^2 / 2 of the last kick(want_ekin=True), in kJ/mol"""
+        return float(self.ekin_word[0]) / self.ACC
+
+    def temperature(self, n_dof=None):
+        """(host read) 2 Ekin / (n_dof kB) of the last kick(want_ekin=True); n_dof defaults to 3 N"""
+        return 2.0 * self.kinetic_energy() / ((3 * self.n_atoms if n_dof is None else n_dof) * KB)
+
+    def plan_info(self):
+        """what the library planned: tiles, tile capacity, largest component, atoms, bonds, angles, LDS bytes per workgroup,
+        launches so far"""
+        out = (ctypes.c_int64 * 8)()
+        _lib.check(self._o._h, self._o._L.admp_md_mts_info(self._o._h, out), 'admp_md_mts_info')
+        keys = ('tiles', 'tile_atoms', 'largest_component', 'atoms', 'bonds', 'angles', 'lds_bytes', 'launches')
+        return dict(zip(keys, (int(x) for x in out)))
 
 
 class CRescaleBarostat:

@@ -1,4 +1,4 @@
-"""What the MD drivers of this directory share (nve_water.py, nvt_water.py, npt_water.py): the water force field's bonded
+"""What the MD drivers of this directory share (nve_water.py, nvt_water.py, npt_water.py, mts_water.py): the water force field's bonded
 constants, the command-line arguments, the calculators with their Verlet lists, the `forces` closure and the `box_gradient`
 closure of the NPT driver, and the capped steepest descent that relaxes the synthetic box before a run."""
 import os
@@ -111,9 +111,10 @@ def setup(opt):
     mS, pS, dS = par['mScales'], par['pScales'], par['dScales']
     state = {'U': None}
 
-    def forces(p, pairs):
+    def forces(p, pairs, bonded=True):
         """(potential energy of the three calculators -- numbers they return anyway --, +dE/dr of everything); the bonded
-        energy of this evaluation is in bond.energy_words (read by epot_now() when a line is logged)"""
+        energy of this evaluation is in bond.energy_words (read by epot_now() when a line is logged).  bonded=False: the
+        calculators alone, bond.energy_words untouched (mts_water.py: the integrator's kernel evaluates the bonded terms)"""
         if opt.pol:
             U0 = state['U']
             hist = state.setdefault('hist', [])
@@ -134,8 +135,9 @@ def setup(opt):
         e2, g2 = disp.get_forces(p, box, pairs, cl, mS)
         e3, g3 = tt(p, box, pairs, mS, a_, b_, q_, c6)
         g.add_(g2).add_(g3)
-        bond.reset_energy()
-        bond.add_forces(p, box, g)
+        if bonded:
+            bond.reset_energy()
+            bond.add_forces(p, box, g)
         return e1 + e2 + e3, g
 
     def epot_now(e123):

@@ -301,8 +301,31 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       n_atoms = 0 writes zeros and the normals.
  *   admp_md_scale       r *= mu, v *= 1 / mu in place (isotropic cell rescaling; the caller scales its box); mu from the
  *                       host in double, rounded to the handle's precision once.  ADMP_E_ARG unless mu is finite and > 0.
+ *   admp_md_mts_plan    the plan of the multiple-time-step integrator (csrc/mts_plan.h) from HOST lists in the layout of
+ *                       admp_md_bonded with HOST double parameters: the connected components of the bond and angle lists
+ *                       (an atom in no item is one of its own) packed whole into tiles of at most tile_atoms atoms, one
+ *                       workgroup each; tile_atoms 0 selects the library's default, which is also the maximum: 256.  The plan's
+ *                       device arrays live on the handle and replace an earlier plan (the call waits for the handle's
+ *                       stream).  ADMP_E_ARG, with admp_last_error naming the size and the smallest atom, for a component
+ *                       larger than tile_atoms; also for an index out of range or a tile whose items exceed 64 KiB of LDS.
+ *                       Duplicate items and items in any order are legal.
+ *   admp_md_mts_step    one outer step of impulse multiple time stepping (two-level r-RESPA, as OpenMM's
+ *                       MTSLangevinIntegrator) up to the calculators, in ONE launch: v -= half_dt_acc_outer * grad_slow / m;
+ *                       then n_inner BAOAB steps of length dt_outer / n_inner on the planned bonded terms, each
+ *                       v -= (half_dt_acc_outer / n_inner) f / m; r += half v; v = c1 v + sqrt(c2sq_kT_acc / m) xi;
+ *                       r += half v; f = bonded gradient at r; v -= ... f / m, with c1 = exp(-gamma dt_outer / n_inner) and
+ *                       c2sq_kT_acc as in admp_md_langevin.  xi of inner step k of outer step s: the normals of (seed,
+ *                       s * n_inner + k modulo 2^64, stream 0, atom) -- with n_inner = 1 the noise of admp_md_langevin; c1 = 1
+ *                       draws nothing.  The closing half kick is admp_md_kick_drift with dt = 0 and the gradient of the
+ *                       calculators at the new positions.  Forces are summed in the order of the caller's lists, bonds before
+ *                       angles, without float atomics: r and v are bit-identical from run to run and for every tile_atoms.
+ *                       Optional, from the bonded evaluation at the returned positions: E_dev[0] += bond energy, E_dev[1] +=
+ *                       angle energy (doubles); grad_fast_out (Na,3) real = the bonded gradient.  box: host, 9 doubles.
+ *                       ADMP_E_ARG for n_inner < 1, a step without a plan, or n_atoms other than the plan's.
+ *   admp_md_mts_info    out8: tiles, tile capacity, largest component, atoms, bonds, angles, LDS bytes per workgroup, launches
+ *                       so far (zeros but for the launches on a handle without a plan)
  * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE);
- * the last three check every argument (n < 0 included) before anything is launched. */
+ * admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is launched. */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
                    const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
                    void* grad_inout);
@@ -318,6 +341,12 @@ int admp_md_bonded_box(admp_handle* h, const void* positions, const double* box,
 int admp_md_virial(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad,
                    const void* inv_mass, uint64_t seed, uint64_t step, double* out_dev);
 int admp_md_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, double mu);
+int admp_md_mts_plan(admp_handle* h, int n_atoms, int n_bonds, const int32_t* bond_idx, const double* bond_par, int n_angles,
+                     const int32_t* angle_idx, const double* angle_par, int tile_atoms);
+int admp_md_mts_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad_slow, const void* inv_mass,
+                     const double* box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc,
+                     uint64_t seed, uint64_t outer_step, double* E_dev, void* grad_fast_out);
+int admp_md_mts_info(admp_handle* h, int64_t* out8);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
