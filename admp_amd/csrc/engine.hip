@@ -322,6 +322,9 @@ struct EngineBase {
                           const double* mS, const double* pS, const void* U, void* sumX, void* sumXw) = 0;
   virtual void pscale_grad(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                            const double* mS, const double* pS, const void* U, double* out) = 0;
+  virtual void pair_real(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
+                         const double* mS, const double* pS, const void* U, const void* F, int which, int flags, int on_device,
+                         double* E_out, void* grad, void* pot, void* fld, int32_t* info) = 0;
   virtual void mscale_grad(int kind, const void* pos, const double* box, const void* par, int pmax, int ns, double* out,
                            int on_device) = 0;
   virtual void md_bonded(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na,
@@ -3195,6 +3198,85 @@ struct Engine : EngineBase {
     HIP_TRY(hipStreamSynchronize(stream));
   }
 
+  // admp_pair_real: one real-space pair kernel and its raw rows -- what an evaluation does up to that kernel (stage_begin:
+  // sites, classes, cut table) and the kernel through the evaluation's own launcher, nothing of the mesh chain and no SCF
+  // (tests compare the rows with a float64 reference).  which 0: k_pair_full (flags bit 0: the charge-only forms are allowed,
+  // as in a call without dE/dQ_local), 1: k_pair_field over the polarizable rows (the other rows of fld come back zero),
+  // 2: k_pair_field_ind after the SCF's own Jacobi step on the field F (dU = -pol F / DIELECTRIC in the site rows), over the
+  // SCF's sub-table and sorted list of polarizable sites: fld = the increment alone.
+  void pair_real(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
+                 const double* mS, const double* pS, const void* U_, const void* F_, int which, int flags, int on_device,
+                 double* E_out, void* grad_, void* pot_, void* fld_, int32_t* info) override {
+    ARG_CHECK(snranks == 1, "admp_pair_real works on a single rank only (slab-decomposed handle)");
+    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(which >= 0 && which <= 2, "which must be 0 (closing pair kernel), 1 (SCF field kernel) or 2 (its increment)");
+    ARG_CHECK(which == 0 || lpol, "the field kernels need a polarizable handle");
+    ARG_CHECK(pos_ && box && Ql_ && E_out && info, "null argument");
+    if (lpol) ARG_CHECK(pol_ && thole_ && U_ && pS, "polarizable handle needs pol, tholes, pScales and U");
+    if (which == 0) ARG_CHECK(grad_ && pot_ && (!lpol || fld_), "null output");
+    else ARG_CHECK(fld_ != nullptr, "null output");
+    if (which == 2) ARG_CHECK(F_ != nullptr, "the increment needs the field of its Jacobi step");
+    const size_t na = (size_t)top.na;
+    HIP_TRY(hipSetDevice(device));
+    U_src_now = nullptr;
+    const T* pos = stage_in(s_pos, pos_, 3 * na, on_device);
+    const T* Ql = stage_in(s_Q, Ql_, 9 * na, on_device);
+    const T* pol = lpol ? stage_in(s_pol, pol_, na, on_device) : nullptr;
+    const T* thole = lpol ? stage_in(s_thole, thole_, na, on_device) : nullptr;
+    const T* U = lpol ? stage_in(s_U, U_, 3 * na, on_device) : nullptr;
+    if (which == 2 && on_device) {      // the Jacobi step updates the dipoles in place: in a copy, the caller's are an input
+      s_U.need(3 * na * sizeof(T));
+      HIP_TRY(hipMemcpyAsync(s_U.p, U_, 3 * na * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      U = s_U.as<T>();
+    }
+    grad.need(3 * na * sizeof(T));
+    if (which == 0) mono_ok = (flags & 1) != 0;
+    stage_begin(pos, box, Ql, pol, thole, ns, mS, pS, const_cast<T*>(U));
+    int n_rows = ev.n_home;
+    double E[4];
+    if (which == 0) {
+      stage_pair_full(grad.as<T>(), lpol ? fld_pair.as<T>() : nullptr);
+    } else if (which == 1) {
+      HIP_TRY(hipMemsetAsync(fld_pair.p, 0, 3 * na * sizeof(T), stream));
+      n_rows = nact_rows();
+      first_pair_field();
+    } else {
+      read_energies(E_RECIP, E, false);      // the count of polarizable sites, as the SCF's first check reads it
+      nact_seen();
+      n_rows = nact_known();
+      HIP_TRY(hipMemcpyAsync(field.p, F_, 3 * na * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemsetAsync(fld_pair.p, 0, 3 * na * sizeof(T), stream));
+      if (!cut_on && (ind_nbr_gen != nbr_gen || ind_act_gen != act_gen)) {      // the sub-table, as scf_increment keeps it
+        TIMED("ind_table");
+        int rc = build_ind_table<T>(stream, top.na, nbr, sites.as<Site<T>>(), ind);
+        if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
+        ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
+      }
+      scf_jacobi(n_rows);
+      if (n_rows > 0) { TIMED("pair_field_ind"); launch_pair_field_ind<T>(stream, pair_field_ind_args(n_rows)); }
+    }
+    ev.active = false;
+    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    nact_seen();
+    int w[2];
+    std::memcpy(w, &Eh[E_NACT], sizeof(w));
+    *E_out = which == 0 ? E[0] : 0.0;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (which == 0) {
+      HIP_TRY(hipMemcpyAsync(grad_, grad.p, 3 * na * sizeof(T), kind, stream));
+      HIP_TRY(hipMemcpyAsync(pot_, pot.p, 9 * na * sizeof(T), kind, stream));
+    }
+    if (lpol && fld_) HIP_TRY(hipMemcpyAsync(fld_, fld_pair.p, 3 * na * sizeof(T), kind, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    int c[4];
+    pair_launch_choice(which, n_rows, lpol, sizeof(T), c);
+    info[0] = c[0];
+    info[1] = cut_on ? 1 : 0;
+    info[2] = (which < 2 && (which == 0 ? mono_ok : true) && c[2] && rq_d.p && !(w[1] & CLS_STALE)) ? 1 : 0;
+    info[3] = c[3];
+    scf.forget();
+  }
+
   // dE/dpScales[k] at the dipoles given (device pointers): class sums of pair_pscale_deriv, folded like dE/dmScales
   void pscale_grad(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                    const double* mS, const double* pS, const void* U, double* out) override {
@@ -3615,6 +3697,15 @@ int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset) {
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
                        int32_t* info16) {
   return guarded(h, [&](EngineBase& e) { e.mesh_convolve(box, which, mesh_inout, on_device, E_out, info16); });
+}
+int admp_pair_real(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                   const void* tholes, int n_scales, const double* mScales, const double* pScales, const void* U,
+                   const void* F, int which, int flags, int on_device, double* E_out, void* grad, void* pot, void* fld,
+                   int32_t* info4) {
+  return guarded(h, [&](EngineBase& e) {
+    e.pair_real(positions, box, Q_local, pol, tholes, n_scales, mScales, pScales, U, F, which, flags, on_device, E_out, grad,
+                pot, fld, info4);
+  });
 }
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {

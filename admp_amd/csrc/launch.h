@@ -364,6 +364,8 @@ int sort_ints(hipStream_t st, int* keys, int* keys_tmp, int n, void** scratch, s
 template <class T>
 int build_ind_table(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, IndTable& it);
 int pair_lanes_per_row(int n_rows);   // 4/8/16 by row count; env ADMP_PAIR_LPR overrides
+// the launchers' choices for a record of n_rows rows (kind 0: k_pair_full, 1: k_pair_field, 2: k_pair_field_ind), see pair_kernels.hip
+void pair_launch_choice(int kind, int n_rows, int lpol, size_t real_bytes, int out4[4]);
 // sumX[i] = sum_j dE_ij/d ln(au_ij), sumXw[i] = sum_j (same) * d ln(au_ij)/d thole_i  (pme_math.h pair_thole_logderiv)
 template <class T>
 void launch_thole_sums(hipStream_t st, int na, const NbrTable& nb, const Site<T>* sites, const Box<T>& box,

@@ -850,6 +850,18 @@ static void finish_args(PairFieldArgs<T>& a, int lpr) {
   a.nblocks = grid_for(a.na, lpr); a.grid = xcd_grid(a.nblocks);
 }
 
+// What the two launchers below pick for a record of `n_rows` rows (admp_pair_real reports it; the rules and switches stay
+// in this file): out4 = {lanes per row, 0, the charge-only forms are not switched off (ADMP_PAIR_MONO), minimum-waves
+// instance of k_pair_full (0 for the field kernels, which have one)}.  kind 0: k_pair_full, 1: k_pair_field,
+// 2: k_pair_field_ind.
+void pair_launch_choice(int kind, int n_rows, int lpol, size_t real_bytes, int out4[4]) {
+  out4[0] = kind == 0 ? pair_lanes_per_row(n_rows) : field_lanes_per_row(n_rows, kind == 2);
+  out4[1] = 0;
+  out4[2] = pair_mono_off() ? 0 : 1;
+  const int minw = real_bytes == 4 ? pair_min_waves<float>() : pair_min_waves<double>();
+  out4[3] = kind == 0 ? ((lpol && minw < 2) ? 1 : 2) : 0;
+}
+
 template <class T>
 void launch_pair_full(hipStream_t st, PairFullArgs<T> a, int lpol) {
   if (a.na <= 0) return;

@@ -448,6 +448,37 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(self._h, self._L.admp_pair_rider_stats(self._h, out, 1 if reset else 0), 'admp_pair_rider_stats')
         return {'rode': int(out[0]), 'own_launch': int(out[1])}
 
+    def pair_real(self, positions, box, pairs, Q_local, mScales, pol=None, tholes=None, pScales=None, U=None, which=0,
+                  flags=1, field=None):
+        """One real-space pair kernel alone (admp_pair_real): which = 0 the closing kernel (flags bit 0: charge-only forms
+        allowed), 1 the SCF field kernel, at the dipoles `U` as given; 2 the incremental field kernel after the SCF's Jacobi
+        step on `field` (dU = -pol field / DIELECTRIC).  Returns a dict: E, grad (Na,3), pot (Na,9) = dE/dQ_global, fld (Na,3) =
+        dE/dU in harmonic order (device tensors; None where the kernel has no such output) and info (lanes per row, cutoff
+        instance, charge-only forms in effect, minimum-waves instance).  A diagnostic for tests."""
+        self._use_current_stream()
+        L, h, na = self._L, self._h, self.n_atoms
+        self.set_pairs(pairs)
+        pos = self._real(positions, (na, 3))
+        Q = self._pad_Q(Q_local)
+        mS = self._host64(mScales)
+        pol_t = th_t = U_t = pS = F_t = None
+        if self.lpol:
+            pol_t, th_t, U_t = self._real(pol, (na,)), self._real(tholes, (na,)), self._real(U, (na, 3))
+            pS = _lib.darr(self._host64(pScales, len(mS)))
+            F_t = self._real(field, (na, 3)) if field is not None else None
+
+        def new(k):
+            return torch.empty((na, k), dtype=self._dtype, device=self._device)
+        grad, pot = (new(3), new(9)) if which == 0 else (None, None)
+        fld = new(3) if self.lpol else None
+        E = ctypes.c_double(0.0)
+        info = (ctypes.c_int * 4)()
+        P = self._ptr
+        rc = L.admp_pair_real(h, P(pos), _lib.darr(self._host64(box, 9)), P(Q), P(pol_t), P(th_t), len(mS), _lib.darr(mS), pS,
+                              P(U_t), P(F_t), int(which), int(flags), 1, ctypes.byref(E), P(grad), P(pot), P(fld), info)
+        _lib.check(h, rc, 'admp_pair_real')
+        return {'E': E.value, 'grad': grad, 'pot': pot, 'fld': fld, 'info': tuple(int(v) for v in info)}
+
     def optimize_Uind(self, positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=None,
                       maxiter=None, thresh=None):
         """Jacobi SCF of the induced dipoles; returns (U, converged, i) like admp/pme.py:111-143."""

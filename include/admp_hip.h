@@ -455,6 +455,31 @@ int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset);
 #define ADMP_MESH_PATH_TWO_LEVEL 4     /* Good-Thomas split (pfa_kernels.hip) */
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
                        int32_t* info16);
+/* One real-space pair kernel alone, and its raw per-atom rows (test entry; single rank: a slab-decomposed handle returns
+ * ADMP_E_ARG).  The call does what an evaluation does up to that kernel -- sites prepared at the dipoles U as given (no SCF),
+ * site classes compiled into the neighbour table, the inner table of admp_set_cutoff -- and launches it through the
+ * evaluation's own launcher; nothing of the mesh chain runs.
+ *   which = 0: the closing kernel k_pair_full.  flags bit 0 set: the charge-only pair forms are allowed, as in a call
+ *              without dE_dQlocal; clear: general arithmetic on every row.
+ *   which = 1: the SCF field kernel k_pair_field over the polarizable rows (polarizable handle; `flags` unused).
+ *   which = 2: the incremental field kernel k_pair_field_ind.  `F` (Na,3, like U) is the total field of the Jacobi step the
+ *              kernel follows: the step forms dU = -pol F / DIELECTRIC on the polarizable sites exactly as in the SCF (in a
+ *              copy of U), the kernel walks the SCF's own polarizable-polarizable sub-table and sorted site list, and fld
+ *              returns the increment alone, sum_j T_ij dU_j.  `F` is ignored (may be NULL) for which = 0 and 1.
+ * Outputs, words of the handle's type on the device (on_device != 0) or on the host, like the inputs:
+ *   *E_out (host)  the real-space energy (which = 0; else 0)
+ *   grad (Na,3)    dE/dr of the pair terms at fixed global multipoles          (which = 0)
+ *   pot  (Na,9)    dE/dQ_global; on a charge-only row walked in the reduced forms only slot 0 is formed   (which = 0)
+ *   fld  (Na,3)    dE/dU in harmonic order (z, x, y); polarizable handles; which >= 1: zero on rows that are not polarizable
+ * info4 = {lanes per row of the launch, 1 if the rows ended at the cutoff's inner table, 1 if the charge-only forms were in
+ * effect (allowed, compiled in and the table's classes not stale; 0 for which = 2, which has none), minimum-waves instance
+ * of k_pair_full (0 for which >= 1)}.
+ * The class bookkeeping is an evaluation's: a first call compiles the classes, a call after the sites changed class sees a
+ * stale table (general forms) and the call after that a recompiled one. */
+int admp_pair_real(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                   const void* tholes, int n_scales, const double* mScales, const double* pScales, const void* U,
+                   const void* F, int which, int flags, int on_device, double* E_out, void* grad, void* pot, void* fld,
+                   int32_t* info4);
 /* Where the closing pair kernel of the polarizable calls ran: out2 = {inside the x pass of a mesh convolution (small
  * double-precision systems on the direct-DFT mesh, one stream; ADMP_PAIR_RIDER=0 turns it off), in a launch of its own}. */
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset);

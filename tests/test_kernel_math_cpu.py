@@ -9,6 +9,7 @@ import torch
 
 from oracle import admp_oracle as O
 from tests.hostshim_util import lib, dp, c64, i32, scale_tables
+from tests.pair_ref import oracle_pair
 
 F64 = torch.float64
 
@@ -36,16 +37,6 @@ def random_sites(n, L, seed, min_sep=1.2):
 def all_pairs(n):
     i, j = np.triu_indices(n, 1)
     return np.stack([i, j], axis=1).astype(np.int32)
-
-
-def oracle_pair(pos, box, pairs, nbonds_dense, Qg, Uh, pol, thole, mS, pS, kappa, lpol):
-    p = T(pos).requires_grad_(True)
-    q = T(Qg).requires_grad_(True)
-    u = T(Uh).requires_grad_(True)
-    e = O.pme_real(p, T(box), pairs, q, u if lpol else None, T(pol) if lpol else None,
-                   T(thole) if lpol else None, T(mS), T(pS) if lpol else None, nbonds_dense, kappa, 2, lpol)
-    gs = torch.autograd.grad(e, [p, q] + ([u] if lpol else []))
-    return float(e.detach()), [g.numpy() for g in gs]
 
 
 @pytest.mark.parametrize('lpol', [False, True])
