@@ -345,6 +345,15 @@ struct EngineBase {
                            double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc, uint64_t seed,
                            uint64_t outer_step, double* E_dev, void* grad_fast) = 0;
   virtual void md_mts_info(int64_t* out) = 0;
+  virtual void md_con_plan(int n_atoms, int n_cons, const int32_t* pairs, const double* lengths, int tile_atoms) = 0;
+  virtual void md_con_step(int n, void* pos, void* vel, const void* grad, const void* inv_mass, const double* box, double half_dt_acc,
+                           double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double tol, int max_sweeps,
+                           int32_t* counters_dev) = 0;
+  virtual void md_con_kick(int n, const void* pos, void* vel, const void* grad, const void* inv_mass, const double* box,
+                           double half_dt_acc, double dt, double tol, int max_sweeps, double* ekin_dev, int32_t* counters_dev) = 0;
+  virtual void md_con_project(int n, void* pos, const void* ref, const void* inv_mass, const double* box, double tol, int max_sweeps,
+                              int32_t* counters_dev) = 0;
+  virtual void md_con_info(int64_t* out) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -643,6 +652,8 @@ struct Engine : EngineBase {
     sl.release();
     mts.ints.release();
     mts.reals.release();
+    con.ints.release();
+    con.reals.release();
     free_programs();
     if (Eh) (void)hipHostFree(Eh);
     prof.destroy();
@@ -2606,6 +2617,101 @@ struct Engine : EngineBase {
                           (int64_t)mts.lds_bytes, mts.launches};
     for (int k = 0; k < 8; ++k) out[k] = mts.have || k == 7 ? v[k] : 0;
   }
+  // distance constraints (con_kernels.hip; admp_amd/md.py Constraints, ConstrainedLangevin): the plan of the constraint list is
+  // made on the host (con_plan.h) and kept on the handle until the next one replaces it
+  struct ConState {
+    bool have = false;
+    int n_atoms = 0, tile_atoms = 0, max_cluster = 0, n_cons = 0, n_clusters = 0, threads = 0;
+    size_t lds_bytes = 0;      // of k_con_project, the largest of the three
+    int64_t launches = 0;
+    ConTiles<T> tiles{};
+    DevBuf ints, reals;
+  } con;
+  void md_con_plan(int n_atoms, int n_cons, const int32_t* pairs, const double* lengths, int tile_atoms) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && n_cons >= 0, "bad argument");
+    ARG_CHECK(n_cons == 0 || (pairs && lengths), "constraint lists missing");
+    const ConPlan p = con_make_plan(n_atoms, n_cons, pairs, lengths, tile_atoms == 0 ? kConDefaultTileAtoms : tile_atoms);
+    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
+    const std::vector<int>* iv[5] = {&p.tile_atom0, &p.atom_id, &p.tile_clu0, &p.clu_con0, &p.con_slot};
+    std::vector<int> hi;
+    size_t off[5];
+    for (int k = 0; k < 5; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
+    const std::vector<T> hr(p.con_d2.begin(), p.con_d2.end());      // d^2 rounded to the handle's precision once
+    HIP_TRY(hipStreamSynchronize(stream));      // a launch of the plan being replaced may still read the old arrays
+    con.have = false;
+    con.ints.need(hi.size() * sizeof(int));
+    con.reals.need((hr.size() + 1) * sizeof(T));
+    HIP_TRY(hipMemcpy(con.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!hr.empty()) HIP_TRY(hipMemcpy(con.reals.p, hr.data(), hr.size() * sizeof(T), hipMemcpyHostToDevice));
+    const int* di = con.ints.template as<int>();
+    ConTiles<T>& m = con.tiles;
+    m.n_tiles = p.n_tiles; m.dims = p.dims;
+    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_clu0 = di + off[2]; m.clu_con0 = di + off[3]; m.con_slot = di + off[4];
+    m.con_d2 = con.reals.template as<T>();
+    con.n_atoms = n_atoms; con.tile_atoms = p.tile_atoms; con.max_cluster = p.max_cluster; con.n_cons = n_cons;
+    con.n_clusters = p.n_clusters;
+    con.threads = mts_threads(p.tile_atoms);
+    con.lds_bytes = con_lds_bytes(p.dims, sizeof(T), true);
+    con.have = true;
+  }
+  // what the three launches share: every argument is checked before anything is launched
+  Box<T> md_con_checked(const char* what, int n, const void* inv_mass, const double* box, double tol, int max_sweeps) {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    if (!con.have) throw Err{ADMP_E_ARG, std::string("admp_md_con_plan must precede ") + what};
+    ARG_CHECK(n >= 0 && n == con.n_atoms, "n_atoms differs from the plan's");
+    ARG_CHECK(inv_mass && box, "bad argument");
+    ARG_CHECK(tol >= 0.0 && std::isfinite(tol), "the tolerance must be finite and not negative");
+    ARG_CHECK(max_sweeps >= 1, "max_sweeps must be at least 1");
+    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
+    double inv[9], vol;
+    return make_box(box, inv, &vol);
+  }
+  void md_con_step(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, const double* box, double half_dt_acc,
+                   double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double tol, int max_sweeps,
+                   int32_t* counters_dev) override {
+    const Box<T> bx = md_con_checked("admp_md_con_step", n, inv_mass, box, tol, max_sweeps);
+    ARG_CHECK(pos && vel && grad_, "bad argument");
+    ARG_CHECK(dt > 0.0 && std::isfinite(dt) && std::isfinite(half_dt_acc), "dt must be positive and finite");
+    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
+    TIMED("md_con_step");
+    launch_con_step<T>(stream, con.tiles, con.threads, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
+                       reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc, dt, c1, c2sq_kT_acc, seed,
+                       step, tol, max_sweeps, counters_dev);
+    HIP_TRY(hipGetLastError());
+    con.launches += 1;
+  }
+  void md_con_kick(int n, const void* pos, void* vel, const void* grad_, const void* inv_mass, const double* box, double half_dt_acc,
+                   double dt, double tol, int max_sweeps, double* ekin_dev, int32_t* counters_dev) override {
+    const Box<T> bx = md_con_checked("admp_md_con_kick", n, inv_mass, box, tol, max_sweeps);
+    ARG_CHECK(pos && vel, "bad argument");
+    ARG_CHECK(grad_ || half_dt_acc == 0.0, "a kick needs a gradient (half_dt_acc 0 with a NULL gradient is a pure projection)");
+    ARG_CHECK(dt > 0.0 && std::isfinite(dt) && std::isfinite(half_dt_acc), "dt must be positive and finite");
+    TIMED("md_con_kick");
+    launch_con_kick<T>(stream, con.tiles, con.threads, reinterpret_cast<const T*>(pos), reinterpret_cast<T*>(vel),
+                       reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc, dt, tol, max_sweeps,
+                       ekin_dev, counters_dev);
+    HIP_TRY(hipGetLastError());
+    con.launches += 1;
+  }
+  void md_con_project(int n, void* pos, const void* ref, const void* inv_mass, const double* box, double tol, int max_sweeps,
+                      int32_t* counters_dev) override {
+    const Box<T> bx = md_con_checked("admp_md_con_project", n, inv_mass, box, tol, max_sweeps);
+    ARG_CHECK(pos && ref, "bad argument");
+    TIMED("md_con_project");
+    launch_con_project<T>(stream, con.tiles, con.threads, reinterpret_cast<T*>(pos), reinterpret_cast<const T*>(ref),
+                          reinterpret_cast<const T*>(inv_mass), bx, tol, max_sweeps, counters_dev);
+    HIP_TRY(hipGetLastError());
+    con.launches += 1;
+  }
+  void md_con_info(int64_t* out) override {
+    ARG_CHECK(out, "bad argument");
+    const int64_t v[8] = {con.tiles.n_tiles, con.tile_atoms, con.max_cluster, con.n_atoms, con.n_cons, con.n_clusters,
+                          (int64_t)con.lds_bytes, con.launches};
+    for (int k = 0; k < 8; ++k) out[k] = con.have || k == 7 ? v[k] : 0;
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3627,6 +3733,31 @@ int admp_md_mts_step(admp_handle* h, int n_atoms, void* positions, void* velocit
 }
 int admp_md_mts_info(admp_handle* h, int64_t* out8) {
   return guarded(h, [&](EngineBase& e) { e.md_mts_info(out8); });
+}
+int admp_md_con_plan(admp_handle* h, int n_atoms, int n_constraints, const int32_t* pairs, const double* lengths, int tile_atoms) {
+  return guarded(h, [&](EngineBase& e) { e.md_con_plan(n_atoms, n_constraints, pairs, lengths, tile_atoms); });
+}
+int admp_md_con_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
+                     double tolerance, int max_sweeps, int32_t* counters_dev) {
+  return guarded(h, [&](EngineBase& e) {
+    e.md_con_step(n_atoms, positions, velocities, grad, inv_mass, box, half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, tolerance,
+                  max_sweeps, counters_dev);
+  });
+}
+int admp_md_con_kick(admp_handle* h, int n_atoms, const void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, double half_dt_acc, double dt, double tolerance, int max_sweeps, double* ekin_dev,
+                     int32_t* counters_dev) {
+  return guarded(h, [&](EngineBase& e) {
+    e.md_con_kick(n_atoms, positions, velocities, grad, inv_mass, box, half_dt_acc, dt, tolerance, max_sweeps, ekin_dev, counters_dev);
+  });
+}
+int admp_md_con_project(admp_handle* h, int n_atoms, void* positions, const void* reference, const void* inv_mass, const double* box,
+                        double tolerance, int max_sweeps, int32_t* counters_dev) {
+  return guarded(h, [&](EngineBase& e) { e.md_con_project(n_atoms, positions, reference, inv_mass, box, tolerance, max_sweeps, counters_dev); });
+}
+int admp_md_con_info(admp_handle* h, int64_t* out8) {
+  return guarded(h, [&](EngineBase& e) { e.md_con_info(out8); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

@@ -8,6 +8,7 @@
 
 #include "env.h"
 #include "frame_math.h"
+#include "con_plan.h"
 #include "mts_plan.h"
 #include "pfa_maps.h"
 #include "pme_math.h"
@@ -702,5 +703,27 @@ template <class T>
 void launch_md_mts(hipStream_t st, const MtsTiles<T>& P, int threads, size_t lds_bytes, T* pos, T* vel, const T* grad_slow,
                    const T* inv_mass, const Box<T>& box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1,
                    double c2sq_kT_acc, uint64_t seed, uint64_t outer_step, double* E, T* grad_fast);
+
+// ---- con_kernels.hip: pairwise distance constraints (SHAKE on the displacement of the first half of a BAOAB step, RATTLE on
+// the velocities of the second, a position projection), one workgroup per tile of whole clusters.  ConTiles: the device copy of
+// a ConPlan (con_plan.h; d^2 in the handle's precision).  threads = mts_threads(tile capacity); the launchers size the LDS
+// themselves (con_lds_bytes).  counters (optional, device): [0] += clusters that stopped unconverged, [1] = max(sweeps).
+template <class T>
+struct ConTiles {
+  int n_tiles;
+  ConDims dims;
+  const int *tile_atom0, *atom_id, *tile_clu0, *clu_con0, *con_slot;
+  const T* con_d2;
+};
+template <class T>
+void launch_con_step(hipStream_t st, const ConTiles<T>& P, int threads, T* pos, T* vel, const T* grad, const T* inv_mass,
+                     const Box<T>& box, double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
+                     double tol, int max_sweeps, int* counters);
+template <class T>
+void launch_con_kick(hipStream_t st, const ConTiles<T>& P, int threads, const T* pos, T* vel, const T* grad, const T* inv_mass,
+                     const Box<T>& box, double half_dt_acc, double dt, double tol, int max_sweeps, double* ekin, int* counters);
+template <class T>
+void launch_con_project(hipStream_t st, const ConTiles<T>& P, int threads, T* pos, const T* ref, const T* inv_mass, const Box<T>& box,
+                        double tol, int max_sweeps, int* counters);
 
 }  // namespace admp

@@ -18,6 +18,11 @@ calculators (`HarmonicBonded.get_box_gradient` is the bonded share, admp_md_bond
 `MTSLangevin` is the multiple-time-step integrator (impulse r-RESPA with two levels): the bonded terms of a `HarmonicBonded`
 advance by n inner BAOAB steps inside one kernel, whole molecules resident in LDS (admp_md_mts_plan / admp_md_mts_step), and
 the calculators are called once per outer step.  Used by examples/md/mts_water.py.
+
+`Constraints` holds pairwise distance constraints (rigid water, constrained X-H bonds) and projects positions and velocities
+onto them; `ConstrainedLangevin` is constrained BAOAB on them -- SHAKE on the displacement of the first half step, RATTLE on
+the velocities of the second, one kernel each with whole clusters resident in LDS (admp_md_con_plan / admp_md_con_step /
+admp_md_con_kick / admp_md_con_project).  Used by examples/md/rigid_water.py.
 """
 import ctypes
 
@@ -354,6 +359,174 @@ class MTSLangevin:
         _lib.check(self._o._h, self._o._L.admp_md_mts_info(self._o._h, out), 'admp_md_mts_info')
         keys = ('tiles', 'tile_atoms', 'largest_component', 'atoms', 'bonds', 'angles', 'lds_bytes', 'launches')
         return dict(zip(keys, (int(x) for x in out)))
+
+
+class Constraints(HipForceBase):
+    """Pairwise distance constraints |x_j - x_i| = d (minimum-image vectors) with a handle of their own: pairs (nc, 2) int,
+    lengths (nc) in A, masses (n_atoms) in amu.  The connected components of the list ("clusters": a rigid water with O-H, O-H
+    and H-H is one) are solved iteratively, whole clusters resident in LDS, one lane sweeping a cluster's constraints in the
+    caller's order (admp_md_con_plan, csrc/con_plan.h): results are bit-identical from run to run and for every `tile_atoms`
+    (None: the library's default; a larger cluster is refused with ValueError, like every other flaw of the lists).
+
+    `tolerance` is relative to d: a sweep stops when every | |p|^2 - d^2 | <= 2 tolerance d^2 (positions) or
+    |s.(v_j - v_i)| dt <= tolerance d^2 (velocities); at most `max_sweeps` sweeps are made whatever happens, and a cluster
+    that stops unconverged counts in `failures()`.  In single precision a tolerance below a few 1e-7 cannot be met once the
+    solved displacement is added to the positions (eps |r| / d: 6e-8 x 30 A / 1 A); the value is passed on as it is, not
+    clamped -- watch `failures()`."""
+    MAX_TILE_ATOMS = 256          # csrc/con_plan.h kConMaxTileAtoms
+
+    def __init__(self, n_atoms, pairs, lengths, masses, tolerance=1e-6, max_sweeps=500, tile_atoms=None, device=None):
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.float64).reshape(-1))
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if len(pairs) != len(lengths):
+            raise ValueError('%d pairs for %d lengths' % (len(pairs), len(lengths)))
+        if len(m) != int(n_atoms):
+            raise ValueError('%d masses for %d atoms' % (len(m), int(n_atoms)))
+        if not (np.all(m > 0) and np.all(np.isfinite(m))):
+            raise ValueError('masses must be positive and finite')
+        if not (np.isfinite(tolerance) and tolerance >= 0):
+            raise ValueError('tolerance must be finite and not negative')
+        if max_sweeps != int(max_sweeps) or max_sweeps < 1:
+            raise ValueError('max_sweeps must be an integer of at least 1')
+        if tile_atoms is not None and not (tile_atoms == int(tile_atoms) and 1 <= tile_atoms <= self.MAX_TILE_ATOMS):
+            raise ValueError('tile_atoms must be None or between 1 and %d' % self.MAX_TILE_ATOMS)
+        if pairs.size and (pairs.min() < -2 ** 31 or pairs.max() >= 2 ** 31):
+            raise ValueError('atom index out of range')
+        super().__init__(n_atoms, None, None, None, device)
+        self.tolerance, self.max_sweeps = float(tolerance), int(max_sweeps)
+        self.masses = m
+        self.inv_mass = self._real(1.0 / m)
+        self._pairs, self._lengths = pairs.astype(np.int32), lengths
+        self._tile_atoms = 0 if tile_atoms is None else int(tile_atoms)
+        self.counters = torch.zeros(2, dtype=torch.int32, device=self._device)      # (failed clusters, most sweeps of a cluster)
+        rc = self._L.admp_md_con_plan(self._h, self.n_atoms, len(self._pairs), self._pairs.ctypes.data, self._lengths.ctypes.data,
+                                      self._tile_atoms)
+        if rc == -1:                                                  # ADMP_E_ARG: the plan's refusal
+            msg = self._L.admp_last_error(self._h)
+            raise ValueError('admp_md_con_plan: %s' % (msg.decode() if msg else ''))
+        _lib.check(self._h, rc, 'admp_md_con_plan')
+
+    @property
+    def n_constraints(self):
+        return len(self._pairs)
+
+    def project_positions(self, pos, box, ref=None):
+        """pos (in place) moved onto the constraints along the directions of `ref` (None: of pos itself): what a minimised or
+        perturbed configuration needs before a run.  Unconstrained atoms are not changed; a cluster's centre of mass moves
+        by rounding only."""
+        tensors = dict(pos=pos) if ref is None else dict(pos=pos, ref=ref)
+        _checked(self, self.n_atoms, **tensors)
+        self._use_current_stream()
+        boxa, _ = self._harr('box', box, 9)
+        P = self._ptr
+        _lib.check(self._h, self._L.admp_md_con_project(self._h, self.n_atoms, P(pos), P(pos if ref is None else ref),
+                                                        P(self.inv_mass), boxa, self.tolerance, self.max_sweeps, P(self.counters)),
+                   'admp_md_con_project')
+
+    def project_velocities(self, pos, vel, box, dt_fs=1.0):
+        """vel (in place) without its components along the constraints at pos: every |s.(v_j - v_i)| dt_fs <= tolerance d^2.
+        A cluster's linear momentum changes by rounding only."""
+        _checked(self, self.n_atoms, pos=pos, vel=vel)
+        if not (np.isfinite(dt_fs) and dt_fs > 0):
+            raise ValueError('dt_fs must be positive and finite')
+        self._use_current_stream()
+        boxa, _ = self._harr('box', box, 9)
+        P = self._ptr
+        _lib.check(self._h, self._L.admp_md_con_kick(self._h, self.n_atoms, P(pos), P(vel), None, P(self.inv_mass), boxa, 0.0,
+                                                     float(dt_fs), self.tolerance, self.max_sweeps, None, P(self.counters)),
+                   'admp_md_con_kick')
+
+    def failures(self):
+        """(host read) clusters that stopped unconverged since the last reset_failures(), summed over the calls"""
+        return int(self.counters[0])
+
+    def max_sweeps_seen(self):
+        """(host read) the most sweeps any cluster made in a call since the last reset_failures()"""
+        return int(self.counters[1])
+
+    def reset_failures(self):
+        self.counters.zero_()
+
+    def plan_info(self):
+        """what the library planned: tiles, tile capacity, largest cluster, atoms, constraints, clusters, LDS bytes per
+        workgroup, launches so far; and the lanes of a workgroup"""
+        out = (ctypes.c_int64 * 8)()
+        _lib.check(self._h, self._L.admp_md_con_info(self._h, out), 'admp_md_con_info')
+        keys = ('tiles', 'tile_atoms', 'largest_cluster', 'atoms', 'constraints', 'clusters', 'lds_bytes', 'launches')
+        info = dict(zip(keys, (int(x) for x in out)))
+        info['lanes'] = 64 if info['tile_atoms'] <= 64 else (128 if info['tile_atoms'] <= 128 else 256)
+        return info
+
+
+class ConstrainedLangevin:
+    """Constrained BAOAB (the splitting of OpenMM's LangevinMiddleIntegrator) on the constraints of a `Constraints`, which lends
+    its handle, masses, tolerance and failure counter; units as in VelocityVerlet:
+
+        kick_drift:  v -= (dt/2) 1e-4 grad / m;  delta = (dt/2) v;  v = c1 v + sig xi;  delta += (dt/2) v;  SHAKE on delta;
+                     v += (delta - delta_unconstrained) / dt;  r += delta                              (admp_md_con_step)
+        (the calculators: grad at the new r)
+        kick:        v -= (dt/2) 1e-4 grad / m;  RATTLE on v                                              (admp_md_con_kick)
+
+    one kernel each.  c1 = exp(-friction dt), xi the normals of (seed, step, stream 0, atom) of csrc/md_math.h; `step` counts
+    the kick_drift calls and may be set (a restart draws the same noise again).  friction 0 is RATTLE velocity Verlet.  The
+    kinetic temperature counts 3 N - n_constraints degrees of freedom by default."""
+    ACC = VelocityVerlet.ACC
+
+    def __init__(self, constraints, dt_fs, temperature=0.0, friction_per_fs=0.0, seed=0):
+        if not isinstance(constraints, Constraints):
+            raise ValueError('constraints must be a Constraints')
+        self._o = constraints
+        self.dt = float(dt_fs)
+        self.T = float(temperature)
+        self.friction = float(friction_per_fs)
+        self.seed = int(seed)
+        self.step = 0
+        if self.T < 0 or self.friction < 0 or not 0 <= self.seed < 2 ** 64:
+            raise ValueError('temperature and friction must not be negative; the seed is an unsigned 64-bit number')
+        if not (np.isfinite(self.dt) and self.dt > 0):
+            raise ValueError('dt must be positive and finite')
+        self.n_atoms = constraints.n_atoms
+        self.inv_mass = constraints.inv_mass
+        self.c1 = float(np.exp(-self.friction * self.dt))
+        self.c2sq_kT_acc = (1.0 - self.c1 * self.c1) * KB * self.T * self.ACC
+        self.ekin_word = torch.zeros(1, dtype=torch.float64, device=constraints._device)
+
+    def kick_drift(self, pos, vel, grad, box):
+        """first half: r(t + dt) on the constraints and the velocities short of the closing kick; then step += 1"""
+        o = self._o
+        _checked(o, self.n_atoms, pos=pos, vel=vel, grad=grad)
+        o._use_current_stream()
+        boxa, _ = o._harr('box', box, 9)
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_con_step(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass), boxa,
+                                               0.5 * self.dt * self.ACC, self.dt, self.c1, self.c2sq_kT_acc, self.seed,
+                                               int(self.step) & (2 ** 64 - 1), o.tolerance, o.max_sweeps, P(o.counters)),
+                   'admp_md_con_step')
+        self.step += 1
+
+    def kick(self, pos, vel, grad, box, want_ekin=False):
+        """second half: v(t + dt) with the gradient at r(t + dt), on the constraints; want_ekin: the kinetic energy of the new
+        velocities lands in ekin_word"""
+        o = self._o
+        _checked(o, self.n_atoms, pos=pos, vel=vel, grad=grad)
+        o._use_current_stream()
+        if want_ekin:
+            self.ekin_word.zero_()
+        boxa, _ = o._harr('box', box, 9)
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_con_kick(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass), boxa,
+                                               0.5 * self.dt * self.ACC, self.dt, o.tolerance, o.max_sweeps,
+                                               P(self.ekin_word) if want_ekin else None, P(o.counters)), 'admp_md_con_kick')
+
+    def kinetic_energy(self):
+        """(host read) sum m v^2 / 2 of the last kick(want_ekin=True), in kJ/mol"""
+        return float(self.ekin_word[0]) / self.ACC
+
+    def temperature(self, n_dof=None):
+        """(host read) 2 Ekin / (n_dof kB) of the last kick(want_ekin=True); n_dof defaults to 3 N - n_constraints"""
+        n_dof = 3 * self.n_atoms - self._o.n_constraints if n_dof is None else n_dof
+        return 2.0 * self.kinetic_energy() / (n_dof * KB)
 
 
 class CRescaleBarostat:

@@ -324,6 +324,33 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       ADMP_E_ARG for n_inner < 1, a step without a plan, or n_atoms other than the plan's.
  *   admp_md_mts_info    out8: tiles, tile capacity, largest component, atoms, bonds, angles, LDS bytes per workgroup, launches
  *                       so far (zeros but for the launches on a handle without a plan)
+ *   admp_md_con_plan    the plan of the distance constraints (csrc/con_plan.h) from HOST lists: pairs (n, 2) int32, lengths (n)
+ *                       double in A.  The connected components of the list ("clusters"; an atom in no constraint is one of its
+ *                       own) are packed whole into tiles of at most tile_atoms atoms, one workgroup each; tile_atoms 0 selects
+ *                       the library's default, which is also the maximum: 256.  A cluster's constraints are swept in the
+ *                       caller's order by one lane, without float atomics: results are bit-identical from run to run and for
+ *                       every tile_atoms.  The plan lives on the handle and replaces an earlier one (the call waits for the
+ *                       handle's stream).  ADMP_E_ARG, with admp_last_error naming the offender, for an index out of range,
+ *                       i == j, a length that is not positive and finite, a cluster larger than tile_atoms (size and smallest
+ *                       atom named) or a tile that needs more than 64 KiB of LDS.  Duplicates are kept.
+ *   admp_md_con_step    first half of a constrained BAOAB step (the splitting of OpenMM's LangevinMiddleIntegrator) in ONE
+ *                       launch: v -= half_dt_acc grad / m; delta = (dt/2) v; v = c1 v + sqrt(c2sq_kT_acc / m) xi (the normals of
+ *                       (seed, step, stream 0, atom); c1 = 1 draws nothing); delta += (dt/2) v; SHAKE on delta with the
+ *                       directions s_ij of the old positions: sweeps of g = (d^2 - |p|^2) / (2 (1/m_i + 1/m_j) s.p),
+ *                       p = s + delta_j - delta_i, delta_i -= (g/m_i) s, delta_j += (g/m_j) s until every |d^2 - |p|^2| <=
+ *                       2 tolerance d^2; v += (delta - delta_unconstrained) / dt; r += delta.  box: host, 9 doubles.
+ *   admp_md_con_kick    second half: v -= half_dt_acc grad / m at the new positions, then RATTLE: sweeps of k = s.(v_j - v_i) /
+ *                       (|s|^2 (1/m_i + 1/m_j)), v_i += (k/m_i) s, v_j -= (k/m_j) s until every |s.(v_j - v_i)| dt <=
+ *                       tolerance d^2.  half_dt_acc = 0 with grad NULL is a pure velocity projection.  ekin_dev (optional) +=
+ *                       sum m v^2 / 2 of the result, as admp_md_kick_drift.
+ *   admp_md_con_project positions moved onto the constraints by the SHAKE sweeps along the directions s_ij of `reference`
+ *                       (which may be `positions` itself); no velocities.
+ *                       All three stop after max_sweeps sweeps whatever happens; a cluster that stops unconverged, or whose
+ *                       SHAKE update meets s.p <= 0 (skipped), adds 1 to counters_dev[0]; counters_dev[1] = max(itself, the
+ *                       sweeps of any cluster) (two int32 device words, optional).  ADMP_E_ARG for a call without a plan,
+ *                       n_atoms other than the plan's, tolerance < 0, max_sweeps < 1 or dt <= 0.
+ *   admp_md_con_info    out8: tiles, tile capacity, largest cluster, atoms, constraints, clusters, LDS bytes per workgroup (of
+ *                       the projection, the largest), launches so far (zeros but for the launches without a plan)
  * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE);
  * admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is launched. */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
@@ -347,6 +374,16 @@ int admp_md_mts_step(admp_handle* h, int n_atoms, void* positions, void* velocit
                      const double* box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc,
                      uint64_t seed, uint64_t outer_step, double* E_dev, void* grad_fast_out);
 int admp_md_mts_info(admp_handle* h, int64_t* out8);
+int admp_md_con_plan(admp_handle* h, int n_atoms, int n_constraints, const int32_t* pairs, const double* lengths, int tile_atoms);
+int admp_md_con_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
+                     double tolerance, int max_sweeps, int32_t* counters_dev);
+int admp_md_con_kick(admp_handle* h, int n_atoms, const void* positions, void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, double half_dt_acc, double dt, double tolerance, int max_sweeps, double* ekin_dev,
+                     int32_t* counters_dev);
+int admp_md_con_project(admp_handle* h, int n_atoms, void* positions, const void* reference, const void* inv_mass, const double* box,
+                        double tolerance, int max_sweeps, int32_t* counters_dev);
+int admp_md_con_info(admp_handle* h, int64_t* out8);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
