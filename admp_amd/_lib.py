@@ -78,6 +78,8 @@ PROTOTYPES = {
     'admp_mesh_convolve': (_i32, [_vp, _dp, _i32, _vp, _i32, _dp, _ip]),
     'admp_pair_real': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _i32, _dp, _dp, _vp, _vp, _i32, _i32, _i32, _dp, _vp, _vp, _vp, _ip]),
     'admp_pair_rider_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
+    'admp_mesh_spread': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _ip]),
+    'admp_mesh_gather': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _dp, _vp, _vp, _vp, _ip]),
     'admp_set_comm': (_i32, [_vp, _vp]),
     'admp_slab_home': (_i32, [_vp, _vp, _ip, _ip]),
     'admp_rccl_unique_id': (_i32, [_vp]),
@@ -120,6 +122,9 @@ RCCL_ID_BYTES, RCCL_NTAGS = 128, 8
 # admp_mesh_convolve: words of its info array, values of info[0]
 MESH_INFO_WORDS = 16
 MESH_PATHS = ('rocfft', 'fused_x', 'direct_lines', 'direct_planes', 'two_level')
+
+# admp_mesh_spread: values of info[0]
+SPREAD_FORMS = ('scan', 'planes', 'bricks', 'plane_kernel')
 
 _lib = None
 

@@ -325,6 +325,11 @@ struct EngineBase {
   virtual void pair_real(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                          const double* mS, const double* pS, const void* U, const void* F, int which, int flags, int on_device,
                          double* E_out, void* grad, void* pot, void* fld, int32_t* info) = 0;
+  virtual void mesh_spread(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, const void* U,
+                           int which, int flags, int on_device, void* mesh_out, int32_t* info) = 0;
+  virtual void mesh_gather(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, const void* U,
+                           const void* phi, int which, int on_device, double* E_out, void* pot, void* grad, void* fld,
+                           int32_t* info) = 0;
   virtual void mscale_grad(int kind, const void* pos, const double* box, const void* par, int pmax, int ns, double* out,
                            int on_device) = 0;
   virtual void md_bonded(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na,
@@ -3383,6 +3388,131 @@ struct Engine : EngineBase {
     scf.forget();
   }
 
+  // admp_mesh_spread / admp_mesh_gather: the spread or the gather alone -- what an evaluation does up to that kernel
+  // (stage_begin: sites at the dipoles given, stencil records, the list of polarizable sites) and the kernel through the
+  // evaluation's own launcher (tests compare the mesh words and the rows with a float64 reference).  The scale tables of the
+  // pair kernels are not an input here: nothing of the real-space chain runs.
+  struct MeshIn { const T *pos, *Ql, *pol, *thole, *U; };
+  MeshIn mesh_stage(const char* who, const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_,
+                    const void* U_, int on_device) {
+    if (snranks != 1) throw Err{ADMP_E_ARG, std::string(who) + " works on a single rank only (slab-decomposed handle)"};
+    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(pos_ && box && Ql_, "null argument");
+    if (lpol) ARG_CHECK(pol_ && thole_ && U_, "polarizable handle needs pol, tholes and U");
+    const size_t na = (size_t)top.na;
+    HIP_TRY(hipSetDevice(device));
+    U_src_now = nullptr;
+    MeshIn in;
+    in.pos = stage_in(s_pos, pos_, 3 * na, on_device);
+    in.Ql = stage_in(s_Q, Ql_, 9 * na, on_device);
+    in.pol = lpol ? stage_in(s_pol, pol_, na, on_device) : nullptr;
+    in.thole = lpol ? stage_in(s_thole, thole_, na, on_device) : nullptr;
+    in.U = lpol ? stage_in(s_U, U_, 3 * na, on_device) : nullptr;
+    return in;
+  }
+  void mesh_begin(const MeshIn& in, const double* box) {
+    static const double one[1] = {1.0};
+    stage_begin(in.pos, box, in.Ql, in.pol, in.thole, 1, one, one, const_cast<T*>(in.U));
+  }
+  void mesh_spread(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, const void* U_,
+                   int which, int flags, int on_device, void* mesh_out, int32_t* info) override {
+    const MeshIn in = mesh_stage("admp_mesh_spread", pos_, box, Ql_, pol_, thole_, U_, on_device);
+    ARG_CHECK(which == 0 || which == 1, "which must be 0 (the spread kernels) or 1 (the forward plane kernel)");
+    ARG_CHECK(mesh_out && info, "null argument");
+    ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
+    ensure_mesh();
+    if (which == 1)
+      ARG_CHECK(use_dft && !use_pfa && dft_zy_spread_fits<T>(K, top.na),
+                "which = 1: this handle's evaluations do not spread in the forward plane kernel (type, atom count or mesh path)");
+    mesh_begin(in, box);
+    const size_t nreal = (size_t)K[0] * K[1] * K[2];
+    T* m = on_device ? reinterpret_cast<T*>(mesh_out) : mesh.as<T>();
+    const int4* recs = (flags & 2) ? nullptr : ev.bases;
+    const int tight = (flags & 1) ? 1 : 0;
+    const int dims[3] = {nloc0(), K[1], K[2]};
+    int c[4];
+    spread_launch_choice(ev.n_home, dims, c);
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    info[5] = -1;
+    if (which == 0) {
+      TIMED("spread");
+      int rc = launch_spread<T>(stream, ev.n_home, sites.as<Site<T>>(), lpol, ev.g, bins, m, ev.home, recs, 1, 0, tight);
+      if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
+      info[0] = c[0];
+      info[4] = (c[0] == ADMP_SPREAD_FORM_BRICKS && sizeof(T) == 4 && tight) ? 1 : 0;
+    } else {
+      ARG_CHECK(spread_fused(ev.n_home), "internal: plane spread refused after the sites were prepared");
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
+      slot_clean[E_RECIP] = false;
+      const PlaneSpread<T> sp = plane_spread(ev.n_home, sites.as<Site<T>>(), lpol, recs);
+      convolve(m, spec.as<T>(), gtab_cur, E_RECIP, nullptr, nullptr, &sp);
+      info[0] = ADMP_SPREAD_FORM_PLANE_KERNEL;
+      info[5] = use_pfa ? ADMP_MESH_PATH_TWO_LEVEL                      // the handle's path, as admp_mesh_convolve reports it
+                : use_dft ? (dft_zy_fits<T>(K) ? ADMP_MESH_PATH_DIRECT_PLANES : ADMP_MESH_PATH_DIRECT_LINES)
+                          : (use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT);
+    }
+    for (int d = 0; d < 3; ++d) info[1 + d] = c[1 + d];
+    info[6] = recs ? 1 : 0;
+    ev.active = false;
+    if (!on_device) HIP_TRY(hipMemcpyAsync(mesh_out, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
+    double E[4];
+    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    nact_seen();
+    scf.forget();
+  }
+  void mesh_gather(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, const void* U_,
+                   const void* phi_, int which, int on_device, double* E_out, void* pot_, void* grad_, void* fld_,
+                   int32_t* info) override {
+    const MeshIn in = mesh_stage("admp_mesh_gather", pos_, box, Ql_, pol_, thole_, U_, on_device);
+    ARG_CHECK(which == 0 || which == 1, "which must be 0 (the gather) or 1 (the field gather over the polarizable sites)");
+    ARG_CHECK(which == 0 || lpol, "the field gather needs a polarizable handle");
+    ARG_CHECK(phi_ && E_out && info, "null argument");
+    if (which == 0) ARG_CHECK(pot_ && grad_ && (!lpol || fld_), "null output");
+    else ARG_CHECK(fld_ != nullptr, "null output");
+    ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
+    const size_t na = (size_t)top.na, nreal = (size_t)K[0] * K[1] * K[2];
+    grad.need(3 * na * sizeof(T));
+    mesh_begin(in, box);
+    const T* phi = reinterpret_cast<const T*>(phi_);
+    if (!on_device) {
+      HIP_TRY(hipMemcpyAsync(mesh.p, phi_, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
+      phi = mesh.as<T>();
+    }
+    double E[4];
+    int n_rows = ev.n_home;
+    if (which == 0) {
+      HIP_TRY(hipMemsetAsync(pot.p, 0, 9 * na * sizeof(T), stream));
+      HIP_TRY(hipMemsetAsync(grad.p, 0, 3 * na * sizeof(T), stream));
+      if (lpol) HIP_TRY(hipMemsetAsync(fld_recip.p, 0, 3 * na * sizeof(T), stream));
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_SLOTS, 0, E_PARTS * sizeof(double), stream));
+      stage_gather(phi, grad.as<T>(), lpol ? fld_recip.as<T>() : nullptr, false, Ed_cur() + E_SLOTS);
+    } else {
+      read_energies(E_RECIP, E, false);      // the count of polarizable sites, as the SCF's first check reads it
+      nact_seen();
+      n_rows = nact_known();
+      HIP_TRY(hipMemsetAsync(fld_recip.p, 0, 3 * na * sizeof(T), stream));
+      TIMED("gather_field");
+      launch_gather_field<T>(stream, n_rows, sites.as<Site<T>>(), ev.g, phi, fld_recip.as<T>(), act_list());
+    }
+    ev.active = false;
+    read_energies(E_PARTS_SUM, E);
+    nact_seen();
+    *E_out = which == 0 ? E[1] : 0.0;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (which == 0) {
+      HIP_TRY(hipMemcpyAsync(pot_, pot.p, 9 * na * sizeof(T), kind, stream));
+      HIP_TRY(hipMemcpyAsync(grad_, grad.p, 3 * na * sizeof(T), kind, stream));
+    }
+    if (fld_ && (lpol || which == 1)) HIP_TRY(hipMemcpyAsync(fld_, fld_recip.p, 3 * na * sizeof(T), kind, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const int groups = (n_rows + 31) / 32;
+    info[0] = which;
+    info[1] = n_rows;
+    info[2] = groups;
+    info[3] = n_rows > 0 ? ((groups + 7) / 8) * 8 : 0;
+    scf.forget();
+  }
+
   // dE/dpScales[k] at the dipoles given (device pointers): class sums of pair_pscale_deriv, folded like dE/dmScales
   void pscale_grad(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                    const double* mS, const double* pS, const void* U, double* out) override {
@@ -3836,6 +3966,19 @@ int admp_pair_real(admp_handle* h, const void* positions, const double* box, con
   return guarded(h, [&](EngineBase& e) {
     e.pair_real(positions, box, Q_local, pol, tholes, n_scales, mScales, pScales, U, F, which, flags, on_device, E_out, grad,
                 pot, fld, info4);
+  });
+}
+int admp_mesh_spread(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                     const void* tholes, const void* U, int which, int flags, int on_device, void* mesh_out, int32_t* info8) {
+  return guarded(h, [&](EngineBase& e) {
+    e.mesh_spread(positions, box, Q_local, pol, tholes, U, which, flags, on_device, mesh_out, info8);
+  });
+}
+int admp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                     const void* tholes, const void* U, const void* phi_in, int which, int on_device, double* E_out, void* pot,
+                     void* grad, void* fld, int32_t* info4) {
+  return guarded(h, [&](EngineBase& e) {
+    e.mesh_gather(positions, box, Q_local, pol, tholes, U, phi_in, which, on_device, E_out, pot, grad, fld, info4);
   });
 }
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {

@@ -8,6 +8,7 @@
 
 #include "env.h"
 #include "frame_math.h"
+#include "brick_plan.h"
 #include "con_plan.h"
 #include "mts_plan.h"
 #include "pfa_maps.h"
@@ -424,34 +425,7 @@ template <class T>
 void launch_gather_virial(hipStream_t st, int na, const Site<T>* sites, int lpol, const RecipGeom<T>& g, const T* phi,
                           double* xw, double* yy, const int* list = nullptr /* the na atoms to gather at (nullptr: 0 .. na-1) */);
 
-// Mesh bricks for the LDS-tiled spread: dimension d is cut into nb[d] = ceil(K/16) bricks of 15..16
-// (>= 6) points, brick b covering [b*K/nb, (b+1)*K/nb).  An atom is binned by the brick of its
-// lowest stencil point; its 6-point stencil then reaches at most the next brick.
-struct BrickGrid {
-  int nb[3];
-  int ncell;
-};
-__host__ __device__ inline BrickGrid make_bricks(const int K[3]) {
-  BrickGrid b;
-  for (int d = 0; d < 3; ++d) b.nb[d] = (K[d] + 15) / 16;
-  b.ncell = b.nb[0] * b.nb[1] * b.nb[2];
-  return b;
-}
-// brick index of mesh index i on an axis of K points cut into nb bricks [b*K/nb, (b+1)*K/nb)
-__host__ __device__ inline int brick_of(int i, int nb, int K) { return ((i + 1) * nb - 1) / K; }
-// Packed brick code of a stencil with lowest indices base[3]: 9 bits per axis = brick of `base`, bits 27..29 = the
-// stencil (6 points) reaches into the next brick on that axis.  Computed once per atom (the integer divisions are the
-// expensive part of binning) by k_prepare_sites, stored in the .w of the atom's int4 base record.
-__host__ __device__ inline int brick_code(const int base[3], const int dims[3], const BrickGrid& bg) {
-  int code = 0;
-  for (int d = 0; d < 3; ++d) {
-    const int b = brick_of(base[d], bg.nb[d], dims[d]);
-    const int end = ((b + 1) * dims[d]) / bg.nb[d];          // first index past the brick of `base`
-    code |= b << (9 * d);
-    if (bg.nb[d] > 1 && base[d] + 5 >= end) code |= 1 << (27 + d);
-  }
-  return code;
-}
+// BrickGrid, make_bricks, brick_of, brick_code: brick_plan.h
 // below this atom count the spread uses global atomics (8 lanes per atom) instead of binned LDS bricks
 // (default 20000; env ADMP_SPREAD_BRICK_MIN overrides, 0 forces the brick path -- used by the parity tests)
 int spread_brick_min_atoms();
@@ -480,6 +454,9 @@ int launch_spread(hipStream_t st, int na, const Site<T>* sites, int lpol, const 
                   int reuse_bins = 0 /* binned kernel: positions unchanged since the previous call, keep its brick lists */,
                   int tight = 1 /* binned kernel, f32: fixed-point scale from the stencil-window bound (0: entry count; SCF increments) */);
 size_t spread_scan_bytes(int ncell);
+// which kernel launch_spread takes for na atoms on a mesh of these local dimensions (admp_mesh_spread reports it; the rules and
+// switches stay in recip_kernels.hip): out4 = {0 scan, 1 planes, 2 bricks; bricks along x, y, z}
+void spread_launch_choice(int na, const int dims[3], int out4[4]);
 // k-space layout [K0][ny][K2/2+1] holding mesh rows y0 .. y0+ny-1 (ny = K1, y0 = 0 on one rank).
 // which: 1 = electrostatics (Ck_1, gamma point dropped, x DIELECTRIC), 6/8/10 = dispersion kernels
 template <class T>

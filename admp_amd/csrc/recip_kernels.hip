@@ -6,6 +6,7 @@
 #include <cstring>
 #include <hipcub/hipcub.hpp>
 
+#include "../../include/admp_hip.h"
 #include "disp_math.h"
 #include "launch.h"
 #include "reduce.h"
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(256) void k_spread_bricks(const Site<T>* __restrict
   using W = typename BrickWord<T>::type;
   __shared__ W tile[16 * 16 * kBrickRow];
   __shared__ unsigned s_bmax;
-  __shared__ unsigned short s_order[kBrickChunk];
+  __shared__ unsigned short s_order[kBrickChunk + 128];   // (each class padded to whole groups of 64)
   __shared__ int s_hist[4];
   __shared__ unsigned s_hist3[344];
   __shared__ unsigned char s_kind[kBrickChunk];     // class of the first chunk's entries, found while pass 1 has their rows
@@ -411,23 +412,27 @@ __global__ __launch_bounds__(256) void k_spread_bricks(const Site<T>* __restrict
       }
     }
     __syncthreads();
-    const int n_gen = s_hist[SK_GENERAL], n_dip = s_hist[SK_DIPOLE];
+    // every class starts on a group boundary (the last group of a class is partly idle): an entry always takes the form
+    // of its own class, whatever places the counters handed out.  A group that mixed two classes and took the general
+    // form for both rounded the lower class's entries differently from call to call, as the places are arrival order.
+    const int n_gen = s_hist[SK_GENERAL], n_dip = s_hist[SK_DIPOLE], n_chg = nch - n_gen - n_dip;
+    const int o_dip = (n_gen + 63) & ~63, o_chg = o_dip + ((n_dip + 63) & ~63);
 #pragma unroll
     for (int k = 0; k < kBrickChunk / 256; ++k) {
       const int e = threadIdx.x + 256 * k;
-      if (e < nch) s_order[(kind[k] == SK_GENERAL ? 0 : (kind[k] == SK_DIPOLE ? n_gen : n_gen + n_dip)) + slot[k]] = (unsigned short)e;
+      if (e < nch) s_order[(kind[k] == SK_GENERAL ? 0 : (kind[k] == SK_DIPOLE ? o_dip : o_chg)) + slot[k]] = (unsigned short)e;
     }
     __syncthreads();
-    // 64 consecutive places of the sorted chunk per wave instruction: one class, except where two classes meet (that
-    // group takes the general form, which is right for every entry)
-    const int groups = (nch + 63) >> 6;
+    // 64 consecutive places of the sorted chunk per wave instruction: one class
+    const int groups = (o_chg + n_chg + 63) >> 6;
     for (int grp = threadIdx.x >> 6; grp < groups; grp += 4) {
-      const int first = grp << 6, last = min(first + 64, nch);
+      const int first = grp << 6;
       const int place = first + lane;
-      if (place >= nch) continue;
+      const int end = first >= o_chg ? o_chg + n_chg : (first >= o_dip ? o_dip + n_dip : n_gen);
+      if (place >= end) continue;
       const Site<T>& site = sites[entries[beg + c0 + s_order[place]]];
-      if (first >= n_gen + n_dip) brick_add_entry<T, SK_CHARGE>(tile, site, lpol, g, lo, n, scale);
-      else if (first >= n_gen && last <= n_gen + n_dip) brick_add_entry<T, SK_DIPOLE>(tile, site, lpol, g, lo, n, scale);
+      if (first >= o_chg) brick_add_entry<T, SK_CHARGE>(tile, site, lpol, g, lo, n, scale);
+      else if (first >= o_dip) brick_add_entry<T, SK_DIPOLE>(tile, site, lpol, g, lo, n, scale);
       else brick_add_entry<T, SK_GENERAL>(tile, site, lpol, g, lo, n, scale);
     }
   }
@@ -461,10 +466,13 @@ __global__ __launch_bounds__(256) void k_spread_bricks(const Site<T>* __restrict
 constexpr int kTileRow = 17;
 constexpr int kTileWords = 16 * 16 * kTileRow;
 
+// The tile holds 64-bit fixed-point words (fixed_bits of the brick kernel, at both precisions): integer adds commute, so
+// the mesh does not depend on the order in which the columns arrive.  `scale` is a power of two and goes into the folded
+// multipoles (exact), so that every term comes out scaled.
 template <class T, int SUB, class GetEntry>
-__device__ __forceinline__ void spread_entry_list(double* tile, T (*wts)[64], int (*ebase)[3], int ne, GetEntry entry,
+__device__ __forceinline__ void spread_entry_list(unsigned long long* tile, T (*wts)[64], int (*ebase)[3], int ne, GetEntry entry,
                                                   const Site<T>* __restrict__ sites, int lpol, const RecipGeom<T>& g,
-                                                  const int lo[3], const int n[3]) {
+                                                  const int lo[3], const int n[3], T scale) {
   for (int sub = 0; sub < ne; sub += SUB) {
     const int cnt = min(SUB, ne - sub);
     if (threadIdx.x < 4 * cnt) {
@@ -488,11 +496,11 @@ __device__ __forceinline__ void spread_entry_list(double* tile, T (*wts)[64], in
         T r[3], Q[9], c1[3], c2[6];
         site_qtot(site, lpol, r, Q);
         fold_multipole(g, Q, c1, c2);
-        w[54] = Q[0];
+        w[54] = scale * Q[0];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) w[55 + k] = c1[k];
+        for (int k = 0; k < 3; ++k) w[55 + k] = scale * c1[k];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) w[58 + k] = c2[k];
+        for (int k = 0; k < 6; ++k) w[58 + k] = scale * c2[k];
       }
     }
     __syncthreads();
@@ -508,13 +516,13 @@ __device__ __forceinline__ void spread_entry_list(double* tile, T (*wts)[64], in
       const T P0 = w[54] * mm + w[55] * d0 * m1 + w[56] * m0 * d1 + w[58] * e0 * m1 + w[59] * m0 * e1 + w[61] * d0 * d1;
       const T P1 = w[57] * mm + w[62] * d0 * m1 + w[63] * m0 * d1;
       const T P2 = w[60] * mm;
-      double* row = tile + (ja * 16 + jb) * kTileRow;
+      unsigned long long* row = tile + (ja * 16 + jb) * kTileRow;
       const int bc = ebase[e][2];
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
         const int jc = wrap_add(bc, c, g.K[2]) - lo[2];
         if ((unsigned)jc < (unsigned)n[2])
-          atomicAdd(&row[jc], (double)(P0 * w[36 + c] + P1 * w[42 + c] + P2 * w[48 + c]));
+          atomicAdd(&row[jc], fixed_bits((double)(P0 * w[36 + c] + P1 * w[42 + c] + P2 * w[48 + c])));
       }
     }
     __syncthreads();
@@ -530,13 +538,14 @@ __device__ __forceinline__ void brick_range(const BrickGrid& bg, int dim0, int d
   }
 }
 template <class T>
-__device__ __forceinline__ void store_tile(const double* tile, const RecipGeom<T>& g, const int lo[3], const int n[3],
-                                           T* __restrict__ mesh) {
+__device__ __forceinline__ void store_tile(const unsigned long long* tile, double inv_scale, const RecipGeom<T>& g,
+                                           const int lo[3], const int n[3], T* __restrict__ mesh) {
   const int nyz = n[1] * n[2], ntot = n[0] * nyz;
   const float inv_yz = 1.0f / (float)nyz, inv_z = 1.0f / (float)n[2];
   for (int t = threadIdx.x; t < ntot; t += 256) {
     const int ja = fast_div(t, nyz, inv_yz), rem = t - ja * nyz, jb = fast_div(rem, n[2], inv_z), jc = rem - jb * n[2];
-    mesh[((long)(lo[0] + ja) * g.K[1] + (lo[1] + jb)) * g.K[2] + lo[2] + jc] = (T)tile[(ja * 16 + jb) * kTileRow + jc];
+    mesh[((long)(lo[0] + ja) * g.K[1] + (lo[1] + jb)) * g.K[2] + lo[2] + jc] =
+        (T)brick_value(tile[(ja * 16 + jb) * kTileRow + jc], inv_scale);
   }
 }
 
@@ -548,54 +557,100 @@ constexpr int kScanChunk = 3072;   // atoms scanned per round (bounds the LDS en
                                    // just under the 64 KB a workgroup may declare: 1024 waters take one round)
 constexpr int kScanSub = 32;       // entries whose weights are staged at a time
 
+// one scan round: the atoms [c0, min(na, c0 + kScanChunk)) whose stencil meets the brick, into ents[0 .. *nent), in arrival order
+template <class T>
+__device__ __forceinline__ void scan_round(int c0, int na, const Site<T>* __restrict__ sites, const int4* __restrict__ bases,
+                                           const RecipGeom<T>& g, const BrickGrid& bg, const int* __restrict__ list,
+                                           const int lo[3], const int n[3], int* ents, int* nent) {
+  if (threadIdx.x == 0) *nent = 0;
+  __syncthreads();
+  const int cend = min(na, c0 + kScanChunk);
+  // all records of the round are fetched before the first test (12 independent loads per thread in flight)
+  constexpr int kPer = kScanChunk / 256;
+  int idx[kPer];
+  int4 rec[kPer];
+#pragma unroll
+  for (int r = 0; r < kPer; ++r) {
+    const int s = c0 + (int)threadIdx.x + 256 * r;
+    idx[r] = s < cend ? (list ? list[s] : s) : -1;
+  }
+#pragma unroll
+  for (int r = 0; r < kPer; ++r) rec[r] = idx[r] >= 0 ? atom_bases(sites, bases, g, bg, idx[r]) : make_int4(0, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < kPer; ++r) {
+    // the stencil [base, base+5] (periodic) meets this brick's [lo, lo+n) iff, with u = base - lo (mod dim),
+    // u < n or u + 5 >= dim -- no integer division in the scan
+    const int base[3] = {rec[r].x, rec[r].y, rec[r].z};
+    bool hit = idx[r] >= 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      int u = base[d] - lo[d];
+      if (u < 0) u += g.dim(d);
+      hit = hit && (u < n[d] || u + 5 >= g.dim(d));
+    }
+    if (hit) ents[atomicAdd(nent, 1)] = idx[r];
+  }
+  __syncthreads();
+}
+
+// The tile is summed in fixed point, so two calls give the same mesh bit for bit whatever order the LDS adds arrive in.
+// Pass 0 scans for the brick's entries and bounds their folded multipoles (the f64 rule of k_spread_bricks, pass 1 there);
+// pass 1 spreads.  Systems of one round (<= kScanChunk atoms) keep the entry list of pass 0 and scan once.
 template <class T>
 __global__ __launch_bounds__(256) void k_spread_scan(int na, const Site<T>* __restrict__ sites, int lpol, RecipGeom<T> g,
                                                      BrickGrid bg, T* __restrict__ mesh, const int* __restrict__ list,
                                                      const int4* __restrict__ bases) {
   sites += (size_t)blockIdx.y * na;                                            // batch of scalar channels (dispersion)
   mesh += (size_t)blockIdx.y * ((size_t)g.nloc0 * g.K[1] * g.K[2]);
-  __shared__ double tile[kTileWords];
+  __shared__ unsigned long long tile[kTileWords];
   __shared__ int ents[kScanChunk];
   __shared__ int nent;
+  __shared__ unsigned s_bmax;
   __shared__ T wts[kScanSub][64];
   __shared__ int ebase[kScanSub][3];
   int lo[3], n[3];
   brick_range(bg, g.dim(0), g.dim(1), g.dim(2), lo, n);
-  for (int t = threadIdx.x; t < kTileWords; t += 256) tile[t] = 0.0;
+  for (int t = threadIdx.x; t < kTileWords; t += 256) tile[t] = 0ull;
+  if (threadIdx.x == 0) s_bmax = 0u;
+  T amax = T(0);      // the largest row (or column) sum of |Aop|: |c1|_1 <= amax |d|_1, |c2|_1 <= 2 amax^2 |Theta/3|_1
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    amax = fmax(amax, m_abs(g.Aop[j]) + m_abs(g.Aop[3 + j]) + m_abs(g.Aop[6 + j]));
+    amax = fmax(amax, m_abs(g.Aop[3 * j]) + m_abs(g.Aop[3 * j + 1]) + m_abs(g.Aop[3 * j + 2]));
+  }
+  float bm = 0.f;
+  int cnt = 0;
   for (int c0 = 0; c0 < na; c0 += kScanChunk) {
-    if (threadIdx.x == 0) nent = 0;
-    __syncthreads();
-    const int cend = min(na, c0 + kScanChunk);
-    // all records of the round are fetched before the first test (12 independent loads per thread in flight)
-    constexpr int kPer = kScanChunk / 256;
-    int idx[kPer];
-    int4 rec[kPer];
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-      const int s = c0 + (int)threadIdx.x + 256 * r;
-      idx[r] = s < cend ? (list ? list[s] : s) : -1;
+    scan_round<T>(c0, na, sites, bases, g, bg, list, lo, n, ents, &nent);
+    const int ne = nent;
+    cnt += ne;
+    for (int k = threadIdx.x; k < ne; k += 256) {
+      T r[3], Q[9];
+      site_qtot(sites[ents[k]], lpol, r, Q);
+      const T d1 = m_abs(Q[1]) + m_abs(Q[2]) + m_abs(Q[3]);
+      const T q2 = m_abs(Q[4]) + m_abs(Q[5]) + m_abs(Q[6]) + m_abs(Q[7]) + m_abs(Q[8]);
+      bm = fmaxf(bm, (float)(m_abs(Q[0]) + amax * d1 + T(2) * amax * amax * q2));
     }
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) rec[r] = idx[r] >= 0 ? atom_bases(sites, bases, g, bg, idx[r]) : make_int4(0, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-      // the stencil [base, base+5] (periodic) meets this brick's [lo, lo+n) iff, with u = base - lo (mod dim),
-      // u < n or u + 5 >= dim -- no integer division in the scan
-      const int base[3] = {rec[r].x, rec[r].y, rec[r].z};
-      bool hit = idx[r] >= 0;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        int u = base[d] - lo[d];
-        if (u < 0) u += g.dim(d);
-        hit = hit && (u < n[d] || u + 5 >= g.dim(d));
-      }
-      if (hit) ents[atomicAdd(&nent, 1)] = idx[r];
-    }
-    __syncthreads();
-    spread_entry_list<T, kScanSub>(tile, wts, ebase, nent, [&](int k) { return ents[k]; }, sites, lpol, g, lo, n);
+    __syncthreads();                                   // the next round resets nent and refills ents
+  }
+  if (bm > 0.f) atomicMax(&s_bmax, __float_as_uint(bm * 1.0001f));      // non-negative floats order like their bits
+  __syncthreads();
+  const double bmax = (double)__uint_as_float(s_bmax);
+  int ex = 20;
+  if (bmax > 0.0) {
+    ex = 58 - ilogb(bmax * (double)(cnt > 0 ? cnt : 1));     // 2^ex * 8 bound < 2^62: no word can overflow ...
+    const int e1 = 49 - ilogb(bmax);                         // ... and 2^ex * bmax < 2^50: every term fits the mantissa trick
+    ex = ex < e1 ? ex : e1;
+    ex = ex > 60 ? 60 : ex;
+  }
+  const T scale = (T)ldexp(1.0, ex);
+  const double inv_scale = ldexp(1.0, -ex);
+  for (int c0 = 0; c0 < na; c0 += kScanChunk) {
+    if (na > kScanChunk) scan_round<T>(c0, na, sites, bases, g, bg, list, lo, n, ents, &nent);
+    spread_entry_list<T, kScanSub>(tile, wts, ebase, nent, [&](int k) { return ents[k]; }, sites, lpol, g, lo, n, scale);
   }
   __syncthreads();
-  store_tile(tile, g, lo, n, mesh);
+  store_tile(tile, inv_scale, g, lo, n, mesh);
 }
 
 // Small systems (too few atoms to fill the chip brick by brick, and launch-latency bound): global float
@@ -1134,14 +1189,14 @@ int launch_spread(hipStream_t st, int na, const Site<T>* sites, int lpol, const 
     RC(hipMemsetAsync(mesh, 0, sizeof(T) * (size_t)g.nloc0 * g.K[1] * g.K[2] * (size_t)(nb > 0 ? nb : 1), st));
     return 0;
   }
-  // the binned brick kernel expresses a stencil as ONE run of local indices per axis, which needs >= 2 bricks per axis
-  // (a stencil that wraps around inside a single brick is two runs): meshes of <= 16 points per axis take the scan kernel
-  const bool one_brick_axis = bg.nb[0] == 1 || bg.nb[1] == 1 || bg.nb[2] == 1;
-  if (!spread_wants_bricks(na, bg.ncell) || one_brick_axis) {
-    // measured (f32, reference K rule): 12 288 atoms scan 0.052 / bricks 0.066 / global atomics 0.130 ms; 18 000 atoms
-    // 0.070 / 0.083 / 0.189; 30 000 atoms 0.144 / 0.109 -- the scan kernel serves everything below the brick threshold
-    static const int scan_max = env_int("ADMP_SPREAD_SCAN_MAX", 20000);
-    if (na <= scan_max || one_brick_axis) {
+  // (spread_launch_choice holds the rule: admp_mesh_spread reports the same call's answer)
+  int choice[4];
+  spread_launch_choice(na, dims, choice);
+  if (choice[0] != ADMP_SPREAD_FORM_BRICKS) {
+    // measured (f32, reference K rule, before the scan kernel's bound pass): 12 288 atoms scan 0.052 / bricks 0.066 / global
+    // atomics 0.130 ms; 18 000 atoms 0.070 / 0.083 / 0.189; 30 000 atoms 0.144 / 0.109 -- the scan kernel serves everything
+    // below the brick threshold
+    if (choice[0] == ADMP_SPREAD_FORM_SCAN) {
       k_spread_scan<T><<<dim3(bg.ncell, nb), 256, 0, st>>>(na, sites, lpol, g, bg, mesh, list, bases);
       return 0;
     }
@@ -1204,6 +1259,20 @@ bool spread_wants_bricks(int na, int ncell) {
 int spread_brick_min_atoms() {
   static const int v = env_int("ADMP_SPREAD_BRICK_MIN", 20000);
   return v < 0 ? 0 : v;
+}
+
+// The form launch_spread takes (out4[0], ADMP_SPREAD_FORM_*) and the brick counts per axis.  launch_spread itself asks here,
+// and so does admp_mesh_spread for its report.
+// The binned brick kernel expresses a stencil as ONE run of local indices per axis, which needs >= 2 bricks per axis
+// (a stencil that wraps around inside a single brick is two runs): meshes of <= 16 points per axis take the scan kernel
+void spread_launch_choice(int na, const int dims[3], int out4[4]) {
+  static const int scan_max = env_int("ADMP_SPREAD_SCAN_MAX", 20000);
+  const BrickGrid bg = make_bricks(dims);
+  const bool one_brick_axis = bg.nb[0] == 1 || bg.nb[1] == 1 || bg.nb[2] == 1;
+  out4[0] = ADMP_SPREAD_FORM_BRICKS;
+  if (!spread_wants_bricks(na, bg.ncell) || one_brick_axis)
+    out4[0] = (na <= scan_max || one_brick_axis) ? ADMP_SPREAD_FORM_SCAN : ADMP_SPREAD_FORM_PLANES;
+  for (int d = 0; d < 3; ++d) out4[1 + d] = bg.nb[d];
 }
 
 // bytes of hipcub scan scratch for a mesh (used by the engine to size BinScratch)

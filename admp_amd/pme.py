@@ -479,6 +479,52 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(h, rc, 'admp_pair_real')
         return {'E': E.value, 'grad': grad, 'pot': pot, 'fld': fld, 'info': tuple(int(v) for v in info)}
 
+    def _mesh_inputs(self, positions, pairs, Q_local, pol, tholes, U):
+        self._use_current_stream()
+        na = self.n_atoms
+        self.set_pairs(pairs)
+        pol_t = th_t = U_t = None
+        if self.lpol:
+            pol_t, th_t, U_t = self._real(pol, (na,)), self._real(tholes, (na,)), self._real(U, (na, 3))
+        return self._real(positions, (na, 3)), self._pad_Q(Q_local), pol_t, th_t, U_t
+
+    def mesh_spread(self, positions, box, pairs, Q_local, pol=None, tholes=None, U=None, which=0, flags=1):
+        """The B-spline spread alone (admp_mesh_spread), at the dipoles `U` as given: which = 0 the spread kernels (flags bit 0:
+        stencil-window scale of the f32 brick kernel, bit 1: no stencil records), returns the mesh; which = 1 the forward plane
+        kernel of the direct-DFT convolution spreads and the convolution runs on, returns phi.  Returns (device tensor
+        (K1, K2, K3), info dict).  A diagnostic for tests."""
+        pos, Q, pol_t, th_t, U_t = self._mesh_inputs(positions, pairs, Q_local, pol, tholes, U)
+        out = torch.empty((self.K1, self.K2, self.K3), dtype=self._dtype, device=self._device)
+        info = (ctypes.c_int * 8)()
+        P = self._ptr
+        rc = self._L.admp_mesh_spread(self._h, P(pos), _lib.darr(self._host64(box, 9)), P(Q), P(pol_t), P(th_t), P(U_t),
+                                      int(which), int(flags), 1, P(out), info)
+        _lib.check(self._h, rc, 'admp_mesh_spread')
+        v = [int(x) for x in info]
+        return out, {'form': _lib.SPREAD_FORMS[v[0]], 'bricks': tuple(v[1:4]), 'tight': v[4],
+                     'path': _lib.MESH_PATHS[v[5]] if v[5] >= 0 else None, 'records': v[6]}
+
+    def mesh_gather(self, positions, box, pairs, Q_local, phi, pol=None, tholes=None, U=None, which=0):
+        """The gather alone on a mesh `phi` of the caller's (admp_mesh_gather): which = 0 k_gather_staged -- E = 1/2 sum Q . pot,
+        pot (Na,9) = dE/dQ_global, grad (Na,3) at fixed global multipoles, fld (Na,3) Cartesian dE/dU on polarizable handles;
+        which = 1 k_gather_field_staged over the polarizable sites -- fld alone, zero elsewhere.  Returns a dict of device
+        tensors and info (kernel, rows, workgroups with rows, workgroups launched).  A diagnostic for tests."""
+        pos, Q, pol_t, th_t, U_t = self._mesh_inputs(positions, pairs, Q_local, pol, tholes, U)
+        na = self.n_atoms
+        phi_t = self._real(phi, (self.K1, self.K2, self.K3))
+
+        def new(k):
+            return torch.empty((na, k), dtype=self._dtype, device=self._device)
+        grad, pot = (new(3), new(9)) if which == 0 else (None, None)
+        fld = new(3) if self.lpol else None
+        E = ctypes.c_double(0.0)
+        info = (ctypes.c_int * 4)()
+        P = self._ptr
+        rc = self._L.admp_mesh_gather(self._h, P(pos), _lib.darr(self._host64(box, 9)), P(Q), P(pol_t), P(th_t), P(U_t),
+                                      P(phi_t), int(which), 1, ctypes.byref(E), P(pot), P(grad), P(fld), info)
+        _lib.check(self._h, rc, 'admp_mesh_gather')
+        return {'E': E.value, 'pot': pot, 'grad': grad, 'fld': fld, 'info': tuple(int(v) for v in info)}
+
     def optimize_Uind(self, positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=None,
                       maxiter=None, thresh=None):
         """Jacobi SCF of the induced dipoles; returns (U, converged, i) like admp/pme.py:111-143."""

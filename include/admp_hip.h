@@ -517,6 +517,39 @@ int admp_pair_real(admp_handle* h, const void* positions, const double* box, con
                    const void* tholes, int n_scales, const double* mScales, const double* pScales, const void* U,
                    const void* F, int which, int flags, int on_device, double* E_out, void* grad, void* pot, void* fld,
                    int32_t* info4);
+/* The B-spline spread of the multipoles alone, and the mesh it leaves (test entry; single rank: a slab-decomposed handle
+ * returns ADMP_E_ARG).  Needs topology, Ewald parameters and pairs (an empty pair list will do).  The call prepares the
+ * sites at the dipoles U as given (no SCF), as an evaluation does, and spreads through the evaluation's own launchers.
+ *   which = 0: launch_spread, the spread that opens an evaluation; mesh_out receives the K1 K2 K3 words of the mesh.
+ *              flags bit 0 set: the fixed-point scale of the f32 brick kernel comes from the stencil-window bound (an
+ *              evaluation's form); clear: from the entry count (the form of the SCF increments).
+ *              flags bit 1 set: no stencil records are handed over, the kernels recompute them (the increments' form).
+ *   which = 1: the forward plane kernel of the direct-DFT convolution builds its planes from the sites (no spread kernel, no
+ *              mesh) and the convolution runs on; mesh_out receives phi = IFFT(G FFT(mesh)), unnormalised, for the handle's
+ *              own G table.  Only where an evaluation would do the same (double precision, at most 8192 atoms, a mesh on
+ *              the plane kernels): ADMP_E_ARG otherwise, never another path.  flags bit 1 as above.
+ * Words of the handle's type on the device (on_device != 0) or on the host, inputs and mesh_out alike.
+ * info8 = {form that ran (ADMP_SPREAD_FORM_*), bricks along x, y, z, 1 if the stencil-window scale was in effect (brick form,
+ * single precision, flags bit 0), which = 1: the ADMP_MESH_PATH_* of the convolution (else -1), 1 if stencil records were
+ * handed to the kernels, 0}. */
+#define ADMP_SPREAD_FORM_SCAN 0          /* k_spread_scan: every brick's workgroup scans all atoms */
+#define ADMP_SPREAD_FORM_PLANES 1        /* k_spread_planes: global float atomics, 8 lanes per atom */
+#define ADMP_SPREAD_FORM_BRICKS 2        /* k_bin + k_spread_bricks: binned, fixed-point LDS tiles */
+#define ADMP_SPREAD_FORM_PLANE_KERNEL 3  /* zy_plane_spread inside the forward plane kernel of the direct DFT */
+int admp_mesh_spread(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                     const void* tholes, const void* U, int which, int flags, int on_device, void* mesh_out, int32_t* info8);
+/* The gather alone, on a phi of the caller's (K1 K2 K3 words; test entry, single rank, prerequisites and site preparation as
+ * admp_mesh_spread).  The output rows are zeroed by the call.
+ *   which = 0: k_gather_staged with the atom-side energy: pot (Na,9) = the reciprocal dE/dQ_global, grad (Na,3) = dE/dr at
+ *              fixed global multipoles, fld (Na,3) = the Cartesian reciprocal dE/dU (slots 11c, 11s, 10 of pot) on polarizable
+ *              handles (else ignored), *E_out = 1/2 sum_i Q_i . pot_i summed from the partial words.
+ *   which = 1: k_gather_field_staged over the handle's own list of polarizable sites (polarizable handle): fld (Na,3) = the
+ *              Cartesian reciprocal dE/dU of the listed atoms, zero on every other row; pot, grad unused, *E_out = 0.
+ * info4 = {kernel (0: k_gather_staged, 1: k_gather_field_staged), rows gathered, workgroups that have rows, workgroups
+ * launched}.  Not reached from here: the closing epilogue of the gather, compact rows added to a field, batches. */
+int admp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                     const void* tholes, const void* U, const void* phi_in, int which, int on_device, double* E_out, void* pot,
+                     void* grad, void* fld, int32_t* info4);
 /* Where the closing pair kernel of the polarizable calls ran: out2 = {inside the x pass of a mesh convolution (small
  * double-precision systems on the direct-DFT mesh, one stream; ADMP_PAIR_RIDER=0 turns it off), in a launch of its own}. */
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset);

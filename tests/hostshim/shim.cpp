@@ -195,6 +195,45 @@ static void gather(int na, const double* pos, const double* Q, const double* box
   }
 }
 
+// The site of an atom without axis atoms as k_prepare_sites leaves it (identity frame, Q_local through rot_harm, the dipole
+// added in the handle's type) and its spread / gather: what admp_mesh_spread / admp_mesh_gather compute, atom by atom in T,
+// summed over the atoms in double (tests/mesh_ref.py measures the rounding of this chain against a wider reference).
+template <class T>
+static void mesh_site(int i, const double* pos, const double* Q, const double* U, T r[3], T q[9]) {
+  const T x[3] = {1, 0, 0}, y[3] = {0, 1, 0}, z[3] = {0, 0, 1};
+  T ql[9], cx[3], cy[3], cz[3];
+  for (int k = 0; k < 3; ++k) r[k] = (T)pos[3 * i + k];
+  for (int k = 0; k < 9; ++k) ql[k] = (T)Q[9 * i + k];
+  frame_cols(x, y, z, cx, cy, cz);
+  rot_harm(ql, cx, cy, cz, q);
+  if (U) { q[1] += (T)U[3 * i + 2]; q[2] += (T)U[3 * i]; q[3] += (T)U[3 * i + 1]; }
+}
+template <class T>
+static void mesh_spread(int na, const double* pos, const double* Q, const double* U, const double* boxh, const int* K,
+                        double* mesh) {
+  RecipGeom<T> g = make_geom<T>(boxh, K);
+  for (int i = 0; i < na; ++i) {
+    T r[3], q[9];
+    mesh_site<T>(i, pos, Q, U, r, q);
+    spread_atom(g, r, q, [&](long idx, T v) { mesh[idx] += (double)v; });
+  }
+}
+template <class T>
+static void mesh_gather(int na, const double* pos, const double* Q, const double* U, const double* boxh, const int* K,
+                        const double* phi, double* pot, double* grad, double* fld) {
+  RecipGeom<T> g = make_geom<T>(boxh, K);
+  for (int i = 0; i < na; ++i) {
+    T r[3], q[9], F[NF], P[9] = {0}, gr[3] = {0, 0, 0}, gx[3];
+    mesh_site<T>(i, pos, Q, U, r, q);
+    gather_atom(g, r, [&](long idx) { return (T)phi[idx]; }, F);
+    unfold_potential(g, q, F, P, gr);
+    for (int k = 0; k < 9; ++k) pot[9 * i + k] = P[k];
+    for (int k = 0; k < 3; ++k) grad[3 * i + k] = gr[k];
+    gather_atom_field(g, r, [&](long idx) { return (T)phi[idx]; }, gx);
+    for (int k = 0; k < 3; ++k) fld[3 * i + k] = gx[k];
+  }
+}
+
 template <class T>
 static double disp_real(int na, const double* pos, const double* c, const double* boxh, long np, const int32_t* pairs,
                         const int32_t* nb, const double* mtab, double kappa, int pmax, double* grad) {
@@ -327,6 +366,16 @@ void shim_gather(int prec, int na, const double* pos, const double* Q, const dou
                  const double* phi, double* pot, double* grad, double* fieldonly) {
   if (prec == 4) gather<float>(na, pos, Q, boxh, K, phi, pot, grad, fieldonly);
   else gather<double>(na, pos, Q, boxh, K, phi, pot, grad, fieldonly);
+}
+void shim_mesh_spread(int prec, int na, const double* pos, const double* Q, const double* U, const double* boxh, const int* K,
+                      double* mesh) {
+  if (prec == 4) mesh_spread<float>(na, pos, Q, U, boxh, K, mesh);
+  else mesh_spread<double>(na, pos, Q, U, boxh, K, mesh);
+}
+void shim_mesh_gather(int prec, int na, const double* pos, const double* Q, const double* U, const double* boxh, const int* K,
+                      const double* phi, double* pot, double* grad, double* fld) {
+  if (prec == 4) mesh_gather<float>(na, pos, Q, U, boxh, K, phi, pot, grad, fld);
+  else mesh_gather<double>(na, pos, Q, U, boxh, K, phi, pot, grad, fld);
 }
 void shim_bspline6(double f, double* out24) {
   bspline6<double>(f, out24, out24 + 6, out24 + 12, out24 + 18);
