@@ -359,6 +359,12 @@ struct EngineBase {
   virtual void md_con_project(int n, void* pos, const void* ref, const void* inv_mass, const double* box, double tol, int max_sweeps,
                               int32_t* counters_dev) = 0;
   virtual void md_con_info(int64_t* out) = 0;
+  virtual void md_mol_plan(int n_atoms, const int32_t* group_of, int tile_atoms) = 0;
+  virtual void md_mol_sums(int n, const void* pos, const void* vel, const void* grad, const void* inv_mass, const double* box,
+                           uint64_t seed, uint64_t step, double* out_dev) = 0;
+  virtual void md_mol_scale(int n, void* pos, void* vel, const void* inv_mass, const double* box, double mu_minus_1,
+                            double inv_mu_minus_1) = 0;
+  virtual void md_mol_info(int64_t* out) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -2717,6 +2723,81 @@ struct Engine : EngineBase {
                           (int64_t)con.lds_bytes, con.launches};
     for (int k = 0; k < 8; ++k) out[k] = con.have || k == 7 ? v[k] : 0;
   }
+  // molecular cell scaling (mol_kernels.hip; admp_amd/md.py MolecularCRescaleBarostat): the plan of the group partition is made
+  // on the host (mol_plan.h) and kept on the handle, in a slot of its own next to the two above, until the next one replaces it
+  struct MolState {
+    bool have = false;
+    int n_atoms = 0, tile_atoms = 0, max_group = 0, n_groups = 0, threads = 0;
+    size_t lds_bytes = 0;
+    int64_t launches = 0;
+    MolTiles tiles{};
+    DevBuf ints;
+  } mol;
+  void md_mol_plan(int n_atoms, const int32_t* group_of, int tile_atoms) override {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && group_of, "bad argument");
+    const MolPlan p = mol_make_plan(n_atoms, group_of, tile_atoms == 0 ? kMolDefaultTileAtoms : tile_atoms);
+    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
+    const std::vector<int>* iv[5] = {&p.tile_atom0, &p.atom_id, &p.tile_grp0, &p.grp_atom0, &p.slot_grp};
+    std::vector<int> hi;
+    size_t off[5];
+    for (int k = 0; k < 5; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
+    HIP_TRY(hipStreamSynchronize(stream));      // a launch of the plan being replaced may still read the old arrays
+    mol.have = false;
+    mol.ints.need(hi.size() * sizeof(int));
+    HIP_TRY(hipMemcpy(mol.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int* di = mol.ints.template as<int>();
+    MolTiles& m = mol.tiles;
+    m.n_tiles = p.n_tiles; m.dims = p.dims;
+    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_grp0 = di + off[2]; m.grp_atom0 = di + off[3]; m.slot_grp = di + off[4];
+    mol.n_atoms = n_atoms; mol.tile_atoms = p.tile_atoms; mol.max_group = p.max_group; mol.n_groups = p.n_groups;
+    mol.threads = mts_threads(p.tile_atoms);
+    mol.lds_bytes = mol_lds_bytes(p.dims, sizeof(T));
+    mol.have = true;
+  }
+  // what the two launches share: every argument is checked before anything is launched
+  Box<T> md_mol_checked(const char* what, int n, const void* inv_mass, const double* box) {
+    HIP_TRY(hipSetDevice(device));
+    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
+    if (!mol.have) throw Err{ADMP_E_ARG, std::string("admp_md_mol_plan must precede ") + what};
+    ARG_CHECK(n >= 0 && n == mol.n_atoms, "n_atoms differs from the plan's");
+    ARG_CHECK(inv_mass && box, "bad argument");
+    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
+    double inv[9], vol;
+    return make_box(box, inv, &vol);
+  }
+  void md_mol_sums(int n, const void* pos, const void* vel, const void* grad_, const void* inv_mass, const double* box, uint64_t seed,
+                   uint64_t step, double* out_dev) override {
+    const Box<T> bx = md_mol_checked("admp_md_mol_sums", n, inv_mass, box);
+    ARG_CHECK(pos && vel && grad_ && out_dev, "bad argument");
+    TIMED("md_mol_sums");
+    HIP_TRY(hipMemsetAsync(out_dev, 0, 21 * sizeof(double), stream));
+    launch_md_mol_sums<T>(stream, mol.tiles, mol.threads, reinterpret_cast<const T*>(pos), reinterpret_cast<const T*>(vel),
+                          reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, seed, step, out_dev);
+    HIP_TRY(hipGetLastError());
+    mol.launches += 1;
+  }
+  void md_mol_scale(int n, void* pos, void* vel, const void* inv_mass, const double* box, double mu_minus_1,
+                    double inv_mu_minus_1) override {
+    const Box<T> bx = md_mol_checked("admp_md_mol_scale", n, inv_mass, box);
+    ARG_CHECK(pos && vel, "bad argument");
+    // mu > 0 and finite, and the two factors belong to one mu: (1 + (mu - 1)) (1 + (1/mu - 1)) = 1
+    ARG_CHECK(std::isfinite(mu_minus_1) && std::isfinite(inv_mu_minus_1) && mu_minus_1 > -1.0 && inv_mu_minus_1 > -1.0,
+              "the scale factor must be finite and positive");
+    ARG_CHECK(std::fabs((1.0 + mu_minus_1) * (1.0 + inv_mu_minus_1) - 1.0) <= 1e-12, "mu_minus_1 and inv_mu_minus_1 are not those of one factor");
+    TIMED("md_mol_scale");
+    launch_md_mol_scale<T>(stream, mol.tiles, mol.threads, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
+                           reinterpret_cast<const T*>(inv_mass), bx, mu_minus_1, inv_mu_minus_1);
+    HIP_TRY(hipGetLastError());
+    mol.launches += 1;
+  }
+  void md_mol_info(int64_t* out) override {
+    ARG_CHECK(out, "bad argument");
+    const int64_t v[8] = {mol.tiles.n_tiles, mol.tile_atoms, mol.max_group, mol.n_atoms, mol.n_groups, (int64_t)mol.lds_bytes,
+                          mol.threads, mol.launches};
+    for (int k = 0; k < 8; ++k) out[k] = mol.have || k == 7 ? v[k] : 0;
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3888,6 +3969,20 @@ int admp_md_con_project(admp_handle* h, int n_atoms, void* positions, const void
 }
 int admp_md_con_info(admp_handle* h, int64_t* out8) {
   return guarded(h, [&](EngineBase& e) { e.md_con_info(out8); });
+}
+int admp_md_mol_plan(admp_handle* h, int n_atoms, const int32_t* group_of, int tile_atoms) {
+  return guarded(h, [&](EngineBase& e) { e.md_mol_plan(n_atoms, group_of, tile_atoms); });
+}
+int admp_md_mol_sums(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, uint64_t seed, uint64_t step, double* out21_dev) {
+  return guarded(h, [&](EngineBase& e) { e.md_mol_sums(n_atoms, positions, velocities, grad, inv_mass, box, seed, step, out21_dev); });
+}
+int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* inv_mass, const double* box,
+                      double mu_minus_1, double inv_mu_minus_1) {
+  return guarded(h, [&](EngineBase& e) { e.md_mol_scale(n_atoms, positions, velocities, inv_mass, box, mu_minus_1, inv_mu_minus_1); });
+}
+int admp_md_mol_info(admp_handle* h, int64_t* out8) {
+  return guarded(h, [&](EngineBase& e) { e.md_mol_info(out8); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

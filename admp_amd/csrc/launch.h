@@ -10,6 +10,7 @@
 #include "frame_math.h"
 #include "brick_plan.h"
 #include "con_plan.h"
+#include "mol_plan.h"
 #include "mts_plan.h"
 #include "pfa_maps.h"
 #include "pme_math.h"
@@ -702,5 +703,21 @@ void launch_con_kick(hipStream_t st, const ConTiles<T>& P, int threads, const T*
 template <class T>
 void launch_con_project(hipStream_t st, const ConTiles<T>& P, int threads, T* pos, const T* ref, const T* inv_mass, const Box<T>& box,
                         double tol, int max_sweeps, int* counters);
+
+// ---- mol_kernels.hip: molecular (centre-of-mass) cell scaling, one workgroup per tile of whole groups.  MolTiles: the device
+// copy of a MolPlan (mol_plan.h).  threads = mts_threads(tile capacity); the launchers size the LDS themselves
+// (mol_lds_bytes).  out (21 doubles, device): the layout of launch_md_virial with the groups' kinetic tensor and the virial of
+// the centres' images; the caller zeroes the first 18 words.
+struct MolTiles {
+  int n_tiles;
+  MolDims dims;
+  const int *tile_atom0, *atom_id, *tile_grp0, *grp_atom0, *slot_grp;
+};
+template <class T>
+void launch_md_mol_sums(hipStream_t st, const MolTiles& P, int threads, const T* pos, const T* vel, const T* grad, const T* inv_mass,
+                        const Box<T>& box, uint64_t seed, uint64_t step, double* out);
+template <class T>
+void launch_md_mol_scale(hipStream_t st, const MolTiles& P, int threads, T* pos, T* vel, const T* inv_mass, const Box<T>& box,
+                         double mu_minus_1, double inv_mu_minus_1);
 
 }  // namespace admp

@@ -23,6 +23,11 @@ the calculators are called once per outer step.  Used by examples/md/mts_water.p
 onto them; `ConstrainedLangevin` is constrained BAOAB on them -- SHAKE on the displacement of the first half step, RATTLE on
 the velocities of the second, one kernel each with whole clusters resident in LDS (admp_md_con_plan / admp_md_con_step /
 admp_md_con_kick / admp_md_con_project).  Used by examples/md/rigid_water.py.
+
+`MolecularCRescaleBarostat` is the barostat for constrained (or any molecular) systems: groups of atoms are scaled as rigid
+bodies about their centres of mass and the pressure is the molecular one, so the constraints survive an application without a
+re-projection (admp_md_mol_plan / admp_md_mol_sums / admp_md_mol_scale); `groups_of` makes the group labels from the lists of
+a `HarmonicBonded` and / or a `Constraints`.  Used by examples/md/npt_water.py --molecular / --rigid.
 """
 import ctypes
 
@@ -600,6 +605,8 @@ class CRescaleBarostat:
         _checked(self._o, self.n_atoms, pos=pos, vel=vel)
         if not (isinstance(box, np.ndarray) and box.dtype == np.float64 and box.size == 9 and box.flags.writeable):
             raise ValueError('box must be a writeable float64 ndarray of 9 elements (it is scaled in place)')
+        # (d eps and mu: MolecularCRescaleBarostat.apply repeats these lines -- change both, or singleton groups no longer
+        # reduce to this class; tests/test_gpu_md_molecular_barostat.py holds the two to the same mu)
         _, vol = self._cell(box)
         kT_bar = KB * self.T * BAR_PER_KJ_MOL_A3 / vol                      # kB T / V in bar
         d_eps = self.beta_T / self.tau_p * (float(p_inst) - self.P0) * self.dt_p + \
@@ -613,3 +620,133 @@ class CRescaleBarostat:
         box *= mu
         self.step += 1
         return mu
+
+
+def groups_of(n_atoms, bonded=None, constraints=None):
+    """(n_atoms) int32 group labels: the connected components of the bond and angle lists of `bonded` (a HarmonicBonded) and / or
+    the pairs of `constraints` (a Constraints); an atom in no item is a group of its own.  The label of a group is its smallest
+    atom."""
+    n_atoms = int(n_atoms)
+    edges = []
+    if bonded is not None:
+        b, a = bonded._bidx.cpu().numpy().reshape(-1, 2), bonded._aidx.cpu().numpy().reshape(-1, 3)
+        edges += [b, a[:, :2], a[:, 1:]]
+    if constraints is not None:
+        edges.append(np.asarray(constraints._pairs).reshape(-1, 2))
+    for owner in (bonded, constraints):
+        if owner is not None and owner.n_atoms != n_atoms:
+            raise ValueError('%d atoms, but the lists are those of %d' % (n_atoms, owner.n_atoms))
+    label = np.arange(n_atoms, dtype=np.int64)
+    e = np.concatenate(edges).astype(np.int64) if edges else np.zeros((0, 2), dtype=np.int64)
+    while len(e):                                                     # label propagation to the smallest atom, with pointer jumping
+        lo = np.minimum(label[e[:, 0]], label[e[:, 1]])
+        new = label.copy()
+        np.minimum.at(new, e[:, 0], lo)
+        np.minimum.at(new, e[:, 1], lo)
+        new = new[new]
+        if np.array_equal(new, label):
+            break
+        label = new
+    return label.astype(np.int32)
+
+
+class MolecularCRescaleBarostat(CRescaleBarostat):
+    """`CRescaleBarostat` with molecular (centre-of-mass) scaling: what a system with constraints needs, since scaling every
+    atom would stretch every constrained distance by mu, and the atomic pressure counts the kinetic energy and the virial of
+    constrained degrees of freedom.  `groups` (n_atoms) assigns every atom to exactly one group by an integer label >= 0 (see
+    `groups_of`; a singleton is a group); an atom may be wrapped into the cell independently of its group, and groups are
+    assumed smaller than half the cell.  With the anchor a of a group its lowest-numbered atom,
+
+        d_i = min_image(r_i - r_a),  s_i = (r_i - r_a) - d_i  (the lattice translation the image applied; exactly zero if none)
+        R_c = r_a + sum m_i d_i / M,  V_c = sum m_i v_i / M,  R_c(i) = R_c + s_i  (the centre's image that belongs to atom i)
+
+    one application with factor mu (box -> mu box) is r_i += (mu - 1) R_c(i), v_i += (1/mu - 1) V_c: a group moves rigidly,
+    atoms of a group in the same image receive bitwise the same displacement dr and all its atoms the same dv, so distances and
+    relative velocities inside a group change by the one rounding of r + dr and v + dv only.
+    mu - 1 and 1/mu - 1 are formed on the host in double with expm1.  The pressure is the molecular one:
+
+        P = (2 K_com / 3 - dE/d eps) / V,  2 K_com = sum_c M_c |V_c|^2,
+        dE/d eps = (sum_ab box_ab (dE/dbox)_ab + sum_i R_c(i) . g_i) / 3
+
+    with dE/dbox what `get_box_gradient` of every calculator returns (fixed Cartesian positions).  d eps, the noise and `step`
+    are exactly those of `CRescaleBarostat`; with all-singleton groups everything reduces to it.  The groups are handled in
+    tiles of whole groups of at most `tile_atoms` atoms (None: the library's default; a larger group is refused with
+    ValueError); r and v do not depend on tile_atoms, bit for bit.  The plan has a slot of its own on the handle: a
+    `Constraints` can lend its handle to this class and to a `ConstrainedLangevin` at once."""
+    MAX_TILE_ATOMS = 256          # csrc/mol_plan.h kMolMaxTileAtoms
+
+    def __init__(self, handle_owner, masses, groups, dt_p_fs, temperature, pressure_bar, tau_p_fs, compressibility_per_bar, seed,
+                 tile_atoms=None):
+        super().__init__(handle_owner, masses, dt_p_fs, temperature, pressure_bar, tau_p_fs, compressibility_per_bar, seed)
+        if tile_atoms is not None and not (tile_atoms == int(tile_atoms) and 1 <= tile_atoms <= self.MAX_TILE_ATOMS):
+            raise ValueError('tile_atoms must be None or between 1 and %d' % self.MAX_TILE_ATOMS)
+        g = np.asarray(groups)
+        if g.ndim != 1 or len(g) != self.n_atoms:
+            raise ValueError('%s group labels for %d atoms' % (g.shape, self.n_atoms))
+        if not np.issubdtype(g.dtype, np.integer) or (g.size and (g.min() < -2 ** 31 or g.max() >= 2 ** 31)):
+            raise ValueError('the group labels must be 32-bit integers')
+        self._groups = np.ascontiguousarray(g, dtype=np.int32)
+        self._tile_atoms = 0 if tile_atoms is None else int(tile_atoms)
+        self._plan()
+
+    def _plan(self):
+        """the handle keeps one plan: made here, and again by sums / apply when another barostat on the same handle has replaced
+        it since"""
+        o = self._o
+        rc = o._L.admp_md_mol_plan(o._h, self.n_atoms, self._groups.ctypes.data, self._tile_atoms)
+        if rc == -1:                                                  # ADMP_E_ARG: the plan's refusal
+            msg = o._L.admp_last_error(o._h)
+            raise ValueError('admp_md_mol_plan: %s' % (msg.decode() if msg else ''))
+        _lib.check(o._h, rc, 'admp_md_mol_plan')
+        o._mol_planned_by = self
+
+    def _ready(self):
+        o = self._o
+        o._use_current_stream()
+        if getattr(o, '_mol_planned_by', None) is not self:
+            self._plan()
+        return o
+
+    def sums(self, pos, vel, grad, box):
+        """(kin, rg, xi): kin (3,3) = sum_c M_c V_c (x) V_c in kJ/mol (its trace is twice the kinetic energy of the centres), rg
+        (3,3) = sum_i R_c(i) (x) g_i with g = +dE/dr in kJ/mol, xi the normal of this application.  One launch and one host
+        read; sums in double."""
+        _checked(self._o, self.n_atoms, pos=pos, vel=vel, grad=grad)
+        o = self._ready()
+        boxa, _ = o._harr('box', box, 9)
+        P = o._ptr
+        _lib.check(o._h, o._L.admp_md_mol_sums(o._h, self.n_atoms, P(pos), P(vel), P(grad), P(self.inv_mass), boxa, self.seed,
+                                               int(self.step) & (2 ** 64 - 1), P(self._words)), 'admp_md_mol_sums')
+        w = self._words.cpu().numpy()
+        return w[0:9].reshape(3, 3) / self.ACC, w[9:18].reshape(3, 3).copy(), float(w[18])
+
+    def apply(self, pos, vel, box, p_inst, xi):
+        """one application: d eps on the host in double, mu - 1 and 1/mu - 1 by expm1, the groups moved by one kernel, `box` (a
+        float64 ndarray) multiplied IN PLACE by mu; then step += 1.  Returns mu."""
+        _checked(self._o, self.n_atoms, pos=pos, vel=vel)
+        if not (isinstance(box, np.ndarray) and box.dtype == np.float64 and box.size == 9 and box.flags.writeable):
+            raise ValueError('box must be a writeable float64 ndarray of 9 elements (it is scaled in place)')
+        # (d eps and mu: the lines of CRescaleBarostat.apply, repeated because that class stays as it is and this one needs
+        # d eps itself for expm1 -- change both)
+        _, vol = self._cell(box)
+        kT_bar = KB * self.T * BAR_PER_KJ_MOL_A3 / vol                      # kB T / V in bar
+        d_eps = self.beta_T / self.tau_p * (float(p_inst) - self.P0) * self.dt_p + \
+            np.sqrt(2.0 * kT_bar * self.beta_T * self.dt_p / self.tau_p) * float(xi)
+        mu = float(np.exp(d_eps / 3.0))
+        if not (np.isfinite(mu) and mu > 0.0):
+            raise ValueError('the scale factor is not finite (P_inst %r, xi %r)' % (p_inst, xi))
+        o = self._ready()
+        boxa, _ = o._harr('box', box, 9)
+        _lib.check(o._h, o._L.admp_md_mol_scale(o._h, self.n_atoms, o._ptr(pos), o._ptr(vel), o._ptr(self.inv_mass), boxa,
+                                                float(np.expm1(d_eps / 3.0)), float(np.expm1(-d_eps / 3.0))), 'admp_md_mol_scale')
+        box *= mu
+        self.step += 1
+        return mu
+
+    def plan_info(self):
+        """what the library planned: tiles, tile capacity, largest group, atoms, groups, LDS bytes per workgroup, lanes of a
+        workgroup, launches so far"""
+        out = (ctypes.c_int64 * 8)()
+        _lib.check(self._o._h, self._o._L.admp_md_mol_info(self._o._h, out), 'admp_md_mol_info')
+        keys = ('tiles', 'tile_atoms', 'largest_group', 'atoms', 'groups', 'lds_bytes', 'lanes', 'launches')
+        return dict(zip(keys, (int(x) for x in out)))

@@ -9,8 +9,15 @@ the thermostat's generator): a run restarted at any step repeats it.
 
     python examples/md/npt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1]
                                     [--pressure 1] [--tau-p 1000] [--compress 4.5e-5] [--nbaro 10] [--pol] [--single] [--mesh K]
+                                    [--molecular | --rigid [--bonds-only] [--tol T]]
 
-The other arguments are those of nve_water.py.  Isotropic scaling of the atoms only (no molecular scaling, one rank).
+The other arguments are those of nve_water.py.  Without --molecular or --rigid: isotropic scaling of the atoms only (one rank).
+--molecular: the same flexible water, but whole molecules are scaled about their centres of mass and the pressure is the
+molecular one (admp_amd.md.MolecularCRescaleBarostat: admp_md_mol_sums, admp_md_mol_scale).  --rigid: the rigid water of
+rigid_water.py (constrained BAOAB, admp_amd.md.Constraints / ConstrainedLangevin; --bonds-only and --tol as there) under the
+molecular barostat, default --dt 2 with the lists rebuilt every 5 steps: a molecule moves rigidly in an application, so the
+constraints survive it without a re-projection -- the largest constraint error right after the application is logged with
+every record.
 """
 import argparse
 import os
@@ -21,8 +28,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import MASS, add_arguments, setup, minimize      # noqa: E402
-from admp_amd import settings                                  # noqa: E402
+from water_md import MASS, add_arguments, setup, minimize, rigid_start      # noqa: E402
+from admp_amd import settings                                               # noqa: E402
 
 G_CM3_PER_AMU_A3 = 1.66053907      # 1 amu/A^3 in g/cm^3
 
@@ -36,24 +43,53 @@ def main():
     ap.add_argument('--tau-p', type=float, default=1000.0, help='relaxation time of the barostat, fs')
     ap.add_argument('--compress', type=float, default=4.5e-5, help='isothermal compressibility, 1/bar')
     ap.add_argument('--nbaro', type=int, default=10, help='steps between applications of the barostat')
+    ap.add_argument('--molecular', action='store_true', help='scale whole molecules about their centres of mass; molecular pressure')
+    ap.add_argument('--rigid', action='store_true', help='rigid water (constrained BAOAB) under the molecular barostat; default --dt 2')
+    ap.add_argument('--bonds-only', action='store_true', help='with --rigid: constrain the O-H bonds only; the angle stays harmonic')
+    ap.add_argument('--tol', type=float, default=0.0, help='with --rigid: relative tolerance of the constraints (0: 1e-8 in double, '
+                    '1e-6 in single)')
+    ap.set_defaults(dt=None, rebuild=None)      # resolved below: they depend on --rigid
     opt = ap.parse_args()
+    if opt.dt is None:
+        opt.dt = 2.0 if opt.rigid else 0.5
+    if opt.rebuild is None:
+        opt.rebuild = 5 if opt.rigid else 10      # as rigid_water.py: the lists are rebuilt every 10 fs
     if opt.nbaro < 1:
         ap.error('--nbaro must be at least 1')
+    if opt.molecular and opt.rigid:
+        ap.error('--rigid implies molecular scaling: give one of --molecular and --rigid')
+    if (opt.bonds_only or opt.tol) and not opt.rigid:
+        ap.error('--bonds-only and --tol belong to --rigid')
     w = setup(opt)
-    from admp_amd.md import CRescaleBarostat, Langevin, maxwell_boltzmann
+    from admp_amd.md import CRescaleBarostat, Langevin, MolecularCRescaleBarostat, groups_of, maxwell_boltzmann
     n_mol, pme, nbl, forces, epot_now, state, box = w.n_mol, w.pme, w.nbl, w.forces, w.epot_now, w.state, w.box
     masses = np.tile(MASS, n_mol)
     h = opt.dt
     # units: A, fs, amu, kJ/mol; pressures in bar
-    vel = maxwell_boltzmann(pme, masses, opt.temp, opt.seed)
-    lv = Langevin(pme, masses, h, opt.temp, opt.friction, opt.seed)
-    baro = CRescaleBarostat(pme, masses, opt.nbaro * h, opt.temp, opt.pressure, opt.tau_p, opt.compress, opt.seed)
-    pos, pairs, e123, grad = minimize(w, opt, w.pos)
+    con = angle = constraint_error = None
+    if opt.rigid:
+        rs = rigid_start(w, opt, masses)      # constraints, integrator, gradient closure; positions and velocities on the constraints
+        con, angle, lv, forces, epot_now, constraint_error = rs.con, rs.angle, rs.integ, rs.gradient, rs.epot_now, rs.constraint_error
+        pos, vel, pairs, e123, grad = rs.pos, rs.vel, rs.pairs, rs.e123, rs.grad
+        baro = MolecularCRescaleBarostat(con, masses, groups_of(3 * n_mol, constraints=con), opt.nbaro * h, opt.temp, opt.pressure,
+                                         opt.tau_p, opt.compress, opt.seed)
+    else:
+        vel = maxwell_boltzmann(pme, masses, opt.temp, opt.seed)
+        lv = Langevin(pme, masses, h, opt.temp, opt.friction, opt.seed)
+        if opt.molecular:
+            baro = MolecularCRescaleBarostat(pme, masses, groups_of(3 * n_mol, bonded=w.bond), opt.nbaro * h, opt.temp, opt.pressure,
+                                             opt.tau_p, opt.compress, opt.seed)
+        else:
+            baro = CRescaleBarostat(pme, masses, opt.nbaro * h, opt.temp, opt.pressure, opt.tau_p, opt.compress, opt.seed)
+        pos, pairs, e123, grad = minimize(w, opt, w.pos)
     log = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for step in range(opt.steps):
-        lv.kick_drift(pos, vel, grad)                                  # B, A, O, A: in place, one kernel
+        if con is not None:
+            lv.kick_drift(pos, vel, grad, box)                         # B, A-O-A, SHAKE: in place, one kernel
+        else:
+            lv.kick_drift(pos, vel, grad)                              # B, A, O, A: in place, one kernel
         if (step + 1) % opt.rebuild == 0:
             pairs = nbl.allocate(pos)
         if opt.prune and (step + 1) % opt.prune == 0:
@@ -61,26 +97,48 @@ def main():
         e123, grad = forces(pos, pairs)
         baro_now = (step + 1) % opt.nbaro == 0
         rec = baro_now and (step // opt.nbaro % max(opt.log // opt.nbaro, 1) == 0 or step + opt.nbaro >= opt.steps)
-        lv.kick(pos, vel, grad, want_ekin=rec)                         # B: v(t + h)
+        if con is not None:
+            lv.kick(pos, vel, grad, box, want_ekin=rec)                # B, RATTLE: v(t + h)
+        else:
+            lv.kick(pos, vel, grad, want_ekin=rec)                     # B: v(t + h)
         if baro_now:
-            dbox = w.box_gradient(pos, pairs)                          # four evaluations at the current positions and list
-            kin, rg, xi = baro.sums(pos, vel, grad)                    # one launch, one host read
+            if con is not None:                                        # the three calculators, and the angle of --bonds-only
+                dbox = w.box_gradient(pos, pairs, bonded=False)
+                if angle is not None:
+                    dbox = dbox + angle.get_box_gradient(pos, box)
+            else:
+                dbox = w.box_gradient(pos, pairs)                      # four evaluations at the current positions and list
+            if con is not None or opt.molecular:
+                kin, rg, xi = baro.sums(pos, vel, grad, box)           # one launch, one host read
+            else:
+                kin, rg, xi = baro.sums(pos, vel, grad)                # one launch, one host read
             p_inst = baro.pressure(box, dbox, kin, rg)
             if rec:
                 log.append((step, epot_now(e123), lv.temperature(), p_inst, abs(float(np.linalg.det(box)))))
             baro.apply(pos, vel, box, p_inst, xi)                      # r, v and the cell (in place: the closures hold `box`)
+            if rec and con is not None:                                # the constraints in the scaled cell, not re-projected
+                log[-1] += (constraint_error(pos),)
             pairs = nbl.allocate(pos)
             e123, grad = forces(pos, pairs)                            # the next kick takes the scaled configuration's gradients
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     m_tot = float(masses.sum())
-    for (s, ep, tk, p, v) in log:
+    for rec in log:
+        (s, ep, tk, p, v) = rec[:5]
         print('step %5d  Epot %14.4f  T_kin %8.2f  P_inst %12.2f  V %14.4f  density %7.4f'
-              % (s, ep, tk, p, v, m_tot / v * G_CM3_PER_AMU_A3))
+              % (s, ep, tk, p, v, m_tot / v * G_CM3_PER_AMU_A3) + ('  constraints %.2e' % rec[5] if con is not None else ''))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
         print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
+    if con is not None or opt.molecular:
+        info = baro.plan_info()
+        print('# molecular scaling: %d groups in %d tiles of at most %d atoms, %d B of LDS per workgroup'
+              % (info['groups'], info['tiles'], info['tile_atoms'], info['lds_bytes']))
+    if con is not None:
+        print('# constraints: largest constraint error %.3e at a record, %.3e at the end (tolerance %.1e, no re-projection in the '
+              'loop); most sweeps of a cluster %d; failures %d'
+              % (max(r[5] for r in log), constraint_error(pos), con.tolerance, con.max_sweeps_seen(), con.failures()))
     half = [r for r in log if r[0] >= opt.steps // 2]
     tk, pp, vv = (np.array([r[k] for r in half]) for k in (2, 3, 4))
     print('# %d waters, %s, %s, dt %.2f fs, Langevin %.1f K, friction %g /fs, seed %d, barostat %.1f bar, tau_p %g fs, every %d '

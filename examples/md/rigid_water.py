@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import KB, MASS, R0, K_ANG, TH0, add_arguments, setup, minimize      # noqa: E402
-from admp_amd import settings                                                      # noqa: E402
+from water_md import MASS, add_arguments, setup, rigid_start      # noqa: E402
+from admp_amd import settings                                     # noqa: E402
 
 
 def main():
@@ -34,63 +34,11 @@ def main():
     ap.add_argument('--tol', type=float, default=0.0, help='relative tolerance of the constraints (0: 1e-8 in double, 1e-6 in single)')
     opt = ap.parse_args()
     w = setup(opt)
-    from admp_amd.md import Constraints, ConstrainedLangevin, HarmonicBonded, maxwell_boltzmann
-    n_mol, pos, dt, box = w.n_mol, w.pos, w.dtype, w.box
-    nbl, forces, state, pme = w.nbl, w.forces, w.state, w.pme
-    tol = opt.tol or (1e-6 if opt.single else 1e-8)
-
-    o = 3 * np.arange(n_mol)
-    pairs = [np.stack([o, o + 1], axis=1), np.stack([o, o + 2], axis=1)]
-    lengths = [np.full(n_mol, R0), np.full(n_mol, R0)]
-    if not opt.bonds_only:
-        pairs.append(np.stack([o + 1, o + 2], axis=1))
-        lengths.append(np.full(n_mol, 2.0 * R0 * np.sin(0.5 * TH0)))
-    pairs = np.stack(pairs, axis=1).reshape(-1, 2)          # a molecule's constraints side by side
-    lengths = np.stack(lengths, axis=1).reshape(-1)
-    masses = np.tile(MASS, n_mol)
-    con = Constraints(3 * n_mol, pairs, lengths, masses, tolerance=tol)
-    angle = None
-    if opt.bonds_only:
-        angle = HarmonicBonded(3 * n_mol, np.zeros((0, 2)), np.zeros((0, 2)), np.stack([o + 1, o, o + 2], axis=1),
-                               np.tile([K_ANG, TH0], (n_mol, 1)))
-    integ = ConstrainedLangevin(con, opt.dt, opt.temp, opt.friction, opt.seed)
-    n_dof = 9 * n_mol - con.n_constraints
-    pi, pj = (torch.as_tensor(pairs[:, k], device='cuda') for k in (0, 1))
-    d_t = torch.as_tensor(lengths, dtype=torch.float64, device='cuda')
-
-    def gradient(p, prs):
-        """the calculators without the bonded terms, plus the harmonic angle of --bonds-only"""
-        e, g = forces(p, prs, bonded=False)
-        if angle is not None:
-            angle.reset_energy()
-            angle.add_forces(p, box, g)
-        return e, g
-
-    def epot_now(e):
-        return float(e) + (angle.energy() if angle is not None else 0.0)
-
-    def constraint_error(p):
-        """largest | |x_j - x_i| - d | / d, minimum image, in double on the device"""
-        h = torch.as_tensor(np.asarray(box, dtype=np.float64).reshape(3, 3), device='cuda')
-        s = (p[pj].double() - p[pi].double()) @ torch.linalg.inv(h)
-        d = ((s - torch.round(s)) @ h).norm(dim=1)
-        return float(((d - d_t).abs() / d_t).max())
-
-    pos, pairs_l, _, _ = minimize(w, opt, pos)                              # flexible, as the other drivers
-    print('# constraint error before the projection %.3e' % constraint_error(pos))
-    con.project_positions(pos, box)
-    pairs_l = nbl.allocate(pos)
-    e123, grad = gradient(pos, pairs_l)
-    vel = maxwell_boltzmann(con, masses, opt.temp, opt.seed)
-    con.project_velocities(pos, vel, box, opt.dt)
-    m_t = torch.as_tensor(masses, dtype=dt, device='cuda')[:, None]
-    t_now = float((m_t * vel * vel).sum()) / ConstrainedLangevin.ACC / (n_dof * KB)
-    if t_now > 0:
-        vel *= float(np.sqrt(opt.temp / t_now))
-    print('# %d constraints (%s), tolerance %.1e; start: constraint error %.3e, T %.1f K over %d degrees of freedom, failures %d'
-          % (con.n_constraints, 'O-H bonds, harmonic angle' if opt.bonds_only else 'rigid water', tol, constraint_error(pos),
-             opt.temp if t_now > 0 else 0.0, n_dof, con.failures()))
-    con.reset_failures()
+    n_mol, box = w.n_mol, w.box
+    nbl, state, pme = w.nbl, w.state, w.pme
+    rs = rigid_start(w, opt, np.tile(MASS, n_mol))      # constraints, integrator, gradient closure; the start on the constraints
+    con, integ, tol, gradient, epot_now, constraint_error = rs.con, rs.integ, rs.tol, rs.gradient, rs.epot_now, rs.constraint_error
+    pos, vel, pairs_l, e123, grad = rs.pos, rs.vel, rs.pairs, rs.e123, rs.grad
     h = opt.dt
     log = []
     torch.cuda.synchronize()

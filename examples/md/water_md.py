@@ -1,6 +1,7 @@
 """What the MD drivers of this directory share (nve_water.py, nvt_water.py, npt_water.py, mts_water.py): the water force field's bonded
 constants, the command-line arguments, the calculators with their Verlet lists, the `forces` closure and the `box_gradient`
-closure of the NPT driver, and the capped steepest descent that relaxes the synthetic box before a run."""
+closure of the NPT driver, the capped steepest descent that relaxes the synthetic box before a run, and the start of the
+rigid-water drivers (rigid_water.py, npt_water.py --rigid)."""
 import os
 import sys
 import types
@@ -143,16 +144,17 @@ def setup(opt):
     def epot_now(e123):
         return float(e123) + bond.energy()
 
-    def box_gradient(p, pairs):
+    def box_gradient(p, pairs, bonded=True):
         """dE/dbox (3,3) at fixed Cartesian positions summed over the four calculators, at the list and (--pol) from the
-        dipoles of the last forces() call; four evaluations, used every --nbaro steps by npt_water.py"""
+        dipoles of the last forces() call; four evaluations, used every --nbaro steps by npt_water.py.  bonded=False: the
+        three calculators alone (npt_water.py --rigid has no bonded terms, or an angle term of its own)"""
         if opt.pol:
             d = pme.get_energy_and_box_gradient(p, box, pairs, Q, pol, thole, mS, pS, dS, U_init=state['U'])[1]
         else:
             d = pme.get_energy_and_box_gradient(p, box, pairs, Q, mS)[1]
         d = d + disp.get_energy_and_box_gradient(p, box, pairs, cl, mS)[1]
         d = d + tt_obj.get_energy_and_box_gradient(p, box, pairs, mS, a_, b_, q_, c6)[1]
-        return d + bond.get_energy_and_box_gradient(p, box)[1]
+        return d + bond.get_energy_and_box_gradient(p, box)[1] if bonded else d
 
     par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
@@ -174,3 +176,67 @@ def minimize(w, opt, pos):
     pairs = nbl.allocate(pos)
     e123, grad = forces(pos, pairs)
     return pos.contiguous(), pairs, e123, grad
+
+
+def rigid_start(w, opt, masses):
+    """what rigid_water.py and npt_water.py --rigid share: the constraints of rigid water (O-H, O-H and H-H; opt.bonds_only: the
+    O-H bonds, with the harmonic angle as a HarmonicBonded of its own), the constrained integrator, the gradient closure
+    without the bonded terms, and the start -- the flexible minimisation, the positions projected onto the constraints,
+    Maxwell-Boltzmann velocities projected likewise and rescaled to opt.temp over the constrained degrees of freedom.  Returns
+    a namespace: con, angle, integ, tol, n_dof, gradient, epot_now, constraint_error, pos, vel, pairs, e123, grad."""
+    from admp_amd.md import Constraints, ConstrainedLangevin, HarmonicBonded, maxwell_boltzmann
+    n_mol, box, nbl = w.n_mol, w.box, w.nbl
+    tol = opt.tol or (1e-6 if opt.single else 1e-8)
+    o = 3 * np.arange(n_mol)
+    pairs = [np.stack([o, o + 1], axis=1), np.stack([o, o + 2], axis=1)]
+    lengths = [np.full(n_mol, R0), np.full(n_mol, R0)]
+    if not opt.bonds_only:
+        pairs.append(np.stack([o + 1, o + 2], axis=1))
+        lengths.append(np.full(n_mol, 2.0 * R0 * np.sin(0.5 * TH0)))
+    pairs = np.stack(pairs, axis=1).reshape(-1, 2)          # a molecule's constraints side by side
+    lengths = np.stack(lengths, axis=1).reshape(-1)
+    con = Constraints(3 * n_mol, pairs, lengths, masses, tolerance=tol)
+    angle = None
+    if opt.bonds_only:
+        angle = HarmonicBonded(3 * n_mol, np.zeros((0, 2)), np.zeros((0, 2)), np.stack([o + 1, o, o + 2], axis=1),
+                               np.tile([K_ANG, TH0], (n_mol, 1)))
+    integ = ConstrainedLangevin(con, opt.dt, opt.temp, opt.friction, opt.seed)
+    pi, pj = (torch.as_tensor(pairs[:, k], device='cuda') for k in (0, 1))
+    d_t = torch.as_tensor(lengths, dtype=torch.float64, device='cuda')
+
+    def gradient(p, prs):
+        """the calculators without the bonded terms, plus the harmonic angle of --bonds-only"""
+        e, g = w.forces(p, prs, bonded=False)
+        if angle is not None:
+            angle.reset_energy()
+            angle.add_forces(p, box, g)
+        return e, g
+
+    def epot_now(e):
+        return float(e) + (angle.energy() if angle is not None else 0.0)
+
+    def constraint_error(p):
+        """largest | |x_j - x_i| - d | / d, minimum image, in double on the device"""
+        h = torch.as_tensor(np.asarray(box, dtype=np.float64).reshape(3, 3), device='cuda')
+        s = (p[pj].double() - p[pi].double()) @ torch.linalg.inv(h)
+        d = ((s - torch.round(s)) @ h).norm(dim=1)
+        return float(((d - d_t).abs() / d_t).max())
+
+    pos, _, _, _ = minimize(w, opt, w.pos)                                 # flexible, as the other drivers
+    print('# constraint error before the projection %.3e' % constraint_error(pos))
+    con.project_positions(pos, box)
+    pairs_l = nbl.allocate(pos)
+    e123, grad = gradient(pos, pairs_l)
+    vel = maxwell_boltzmann(con, masses, opt.temp, opt.seed)
+    con.project_velocities(pos, vel, box, opt.dt)
+    n_dof = 9 * n_mol - con.n_constraints
+    m_t = torch.as_tensor(masses, dtype=w.dtype, device='cuda')[:, None]
+    t_now = float((m_t * vel * vel).sum()) / ConstrainedLangevin.ACC / (n_dof * KB)
+    if t_now > 0:
+        vel *= float(np.sqrt(opt.temp / t_now))
+    print('# %d constraints (%s), tolerance %.1e; start: constraint error %.3e, T %.1f K over %d degrees of freedom, failures %d'
+          % (con.n_constraints, 'O-H bonds, harmonic angle' if opt.bonds_only else 'rigid water', tol, constraint_error(pos),
+             opt.temp if t_now > 0 else 0.0, n_dof, con.failures()))
+    con.reset_failures()
+    return types.SimpleNamespace(con=con, angle=angle, integ=integ, tol=tol, n_dof=n_dof, gradient=gradient, epot_now=epot_now,
+                                 constraint_error=constraint_error, pos=pos, vel=vel, pairs=pairs_l, e123=e123, grad=grad)

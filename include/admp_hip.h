@@ -351,6 +351,30 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       n_atoms other than the plan's, tolerance < 0, max_sweeps < 1 or dt <= 0.
  *   admp_md_con_info    out8: tiles, tile capacity, largest cluster, atoms, constraints, clusters, LDS bytes per workgroup (of
  *                       the projection, the largest), launches so far (zeros but for the launches without a plan)
+ *   admp_md_mol_plan    the plan of the molecular (centre-of-mass) cell scaling (csrc/mol_plan.h) from a HOST array:
+ *                       group_of (n_atoms) int32 labels >= 0, every atom in exactly one group ("molecule"; a singleton is a
+ *                       group); the labels need not be dense or ordered.  Groups are taken in the order of their smallest
+ *                       atom -- the group's anchor a -- and packed whole into tiles of at most tile_atoms atoms, one workgroup
+ *                       each; tile_atoms 0 selects the library's default, which is also the maximum: 256.  The plan has a slot
+ *                       of its own on the handle, next to those of admp_md_mts_plan and admp_md_con_plan, and replaces an
+ *                       earlier one (the call waits for the handle's stream).  ADMP_E_ARG, with admp_last_error naming the
+ *                       offender, for a negative label, a group larger than tile_atoms (size and smallest atom named) or
+ *                       tile_atoms outside 0..256.
+ *                       With d_i = minimum image of r_i - r_a and s_i = (r_i - r_a) - d_i (the lattice translation the image
+ *                       applied, exactly zero when none was; groups are smaller than half the cell, atoms may be wrapped one
+ *                       by one): R_c = r_a + sum m_i d_i / M, V_c = sum m_i v_i / M, R_c(i) = R_c + s_i.  M, sum m d and
+ *                       sum m v are summed in double by one lane per group in the plan's order, without float atomics.
+ *   admp_md_mol_sums    what the molecular pressure needs, in the layout and units of admp_md_virial: out21_dev (21 doubles,
+ *                       zeroed by the call): [0..8] = sum over groups M_c V_c (x) V_c, [9..17] = sum_i R_c(i) (x) grad_i,
+ *                       [18..20] = the three normals of (seed, step, stream 2, atom 0).  box: host, 9 doubles.
+ *   admp_md_mol_scale   one application with factor mu (the caller scales its box): r_i += (mu - 1) R_c(i), v_i += (1/mu - 1)
+ *                       V_c in place -- a group moves rigidly.  mu_minus_1 and inv_mu_minus_1 from the host in double (expm1);
+ *                       the products are rounded to the handle's precision once, so atoms of a group in the same image receive
+ *                       bitwise the same displacement.  No atomics: r and v are bit-identical from run to run and for every
+ *                       tile_atoms.  ADMP_E_ARG unless both are finite and > -1 and belong to one mu.
+ *                       Both: ADMP_E_ARG for a call without a plan, n_atoms other than the plan's, a singular or non-finite box.
+ *   admp_md_mol_info    out8: tiles, tile capacity, largest group, atoms, groups, LDS bytes per workgroup, lanes of a
+ *                       workgroup, launches so far (zeros but for the launches without a plan)
  * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE);
  * admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is launched. */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
@@ -384,6 +408,12 @@ int admp_md_con_kick(admp_handle* h, int n_atoms, const void* positions, void* v
 int admp_md_con_project(admp_handle* h, int n_atoms, void* positions, const void* reference, const void* inv_mass, const double* box,
                         double tolerance, int max_sweeps, int32_t* counters_dev);
 int admp_md_con_info(admp_handle* h, int64_t* out8);
+int admp_md_mol_plan(admp_handle* h, int n_atoms, const int32_t* group_of, int tile_atoms);
+int admp_md_mol_sums(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad, const void* inv_mass,
+                     const double* box, uint64_t seed, uint64_t step, double* out21_dev);
+int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* inv_mass, const double* box,
+                      double mu_minus_1, double inv_mu_minus_1);
+int admp_md_mol_info(admp_handle* h, int64_t* out8);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
