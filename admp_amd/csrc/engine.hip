@@ -28,6 +28,7 @@
 #include "../../include/admp_hip.h"
 #include "dft_math.h"
 #include "launch.h"
+#include "md_fire_math.h"
 #include "rccl_comm.h"
 #include "scf_policy.h"
 
@@ -365,6 +366,8 @@ struct EngineBase {
   virtual void md_mol_scale(int n, void* pos, void* vel, const void* inv_mass, const double* box, double mu_minus_1,
                             double inv_mu_minus_1) = 0;
   virtual void md_mol_info(int64_t* out) = 0;
+  virtual void md_fire_step(int n, void* pos, void* vel, const void* grad, const void* inv_mass, const double* par9, double ftol,
+                            uint64_t call, double* state16_dev) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -665,6 +668,7 @@ struct Engine : EngineBase {
     mts.reals.release();
     con.ints.release();
     con.reals.release();
+    fire_rows.release();
     free_programs();
     if (Eh) (void)hipHostFree(Eh);
     prof.destroy();
@@ -2798,6 +2802,29 @@ struct Engine : EngineBase {
                           mol.threads, mol.launches};
     for (int k = 0; k < 8; ++k) out[k] = mol.have || k == 7 ? v[k] : 0;
   }
+  // the FIRE minimiser (fire_kernels.hip, md_fire_math.h; admp_amd/md.py FireMinimizer): the handle owns the rows of partial
+  // sums, the caller the state; every argument is checked before the first launch
+  DevBuf fire_rows;
+  void md_fire_step(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, const double* par9, double ftol,
+                    uint64_t call, double* state16_dev) override {
+    HIP_TRY(hipSetDevice(device));
+    ARG_CHECK(snranks == 1, "the MD helpers serve single-rank handles only (slab-decomposed handle)");
+    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && par9 && state16_dev && (n == 0 || (pos && vel && grad_ && inv_mass)), "bad argument");
+    const double dt_max = par9[FIRE_P_DT_MAX], dt_min = par9[FIRE_P_DT_MIN], max_step = par9[FIRE_P_MAX_STEP];
+    ARG_CHECK(std::isfinite(dt_max) && std::isfinite(dt_min) && std::isfinite(max_step) && dt_max > 0.0 && dt_min > 0.0 &&
+              max_step > 0.0 && dt_min <= dt_max, "dt_min, dt_max and max_step must be finite and positive, dt_min <= dt_max");
+    ARG_CHECK(par9[FIRE_P_N_DELAY] >= 0.0, "n_delay must not be negative");
+    ARG_CHECK(std::isfinite(par9[FIRE_P_F_INC]) && par9[FIRE_P_F_INC] >= 1.0, "f_inc must be finite and at least 1");
+    for (int w : {(int)FIRE_P_F_DEC, (int)FIRE_P_ALPHA_START, (int)FIRE_P_F_ALPHA})
+      ARG_CHECK(par9[w] > 0.0 && par9[w] <= 1.0, "f_dec, alpha_start and f_alpha must lie in (0, 1]");
+    ARG_CHECK(std::isfinite(ftol) && ftol >= 0.0, "ftol must be finite and not negative");
+    fire_rows.need(kFireRowsBytes);
+    TIMED("md_fire");
+    const int rc = launch_md_fire<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
+                                     reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), par9, ftol, call,
+                                     fire_rows.as<double>(), state16_dev);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("FIRE step: ") + hipGetErrorString((hipError_t)rc)};
+  }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
@@ -3983,6 +4010,10 @@ int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* veloci
 }
 int admp_md_mol_info(admp_handle* h, int64_t* out8) {
   return guarded(h, [&](EngineBase& e) { e.md_mol_info(out8); });
+}
+int admp_md_fire_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                      const double* params9, double ftol, uint64_t call, double* state16_dev) {
+  return guarded(h, [&](EngineBase& e) { e.md_fire_step(n_atoms, positions, velocities, grad, inv_mass, params9, ftol, call, state16_dev); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {

@@ -720,4 +720,12 @@ template <class T>
 void launch_md_mol_scale(hipStream_t st, const MolTiles& P, int threads, T* pos, T* vel, const T* inv_mass, const Box<T>& box,
                          double mu_minus_1, double inv_mu_minus_1);
 
+// ---- fire_kernels.hip: one iteration of the FIRE minimiser (md_fire_math.h): the six reduced words as one row per workgroup in
+// `rows` (>= kFireRowsBytes), then fold + control + update.  state16 (device): two slots of 8 doubles, slot call & 1 is read, the
+// other written; n = 0 copies the slot forward.  par9 is read on the host.  Returns hipError_t as int.
+constexpr size_t kFireRowsBytes = 256 * 6 * sizeof(double);
+template <class T>
+int launch_md_fire(hipStream_t st, int n, T* pos, T* vel, const T* grad, const T* inv_mass, const double* par9, double ftol,
+                   uint64_t call, double* rows, double* state16);
+
 }  // namespace admp

@@ -28,6 +28,12 @@ admp_md_con_kick / admp_md_con_project).  Used by examples/md/rigid_water.py.
 bodies about their centres of mass and the pressure is the molecular one, so the constraints survive an application without a
 re-projection (admp_md_mol_plan / admp_md_mol_sums / admp_md_mol_scale); `groups_of` makes the group labels from the lists of
 a `HarmonicBonded` and / or a `Constraints`.  Used by examples/md/npt_water.py --molecular / --rigid.
+
+`FireMinimizer` is the energy minimiser that prepares a start: FIRE (Bitzek et al. 2006) with the half step back of FIRE 2.0
+(Guenole et al. 2020) and a hard cap on every atom's move.  One iteration is one C call (admp_md_fire_step) of two kernels: six
+sums and maxima in double without atomics, then the decision -- downhill or uphill, the new time step, converged, failed -- taken
+on the device from a double-buffered state (csrc/md_fire_math.h), so an iteration reads nothing back and is bit-repeatable; with
+a `Constraints` it minimises on them.  Used by examples/md/minimize_water.py and by every driver with --minimizer fire.
 """
 import ctypes
 
@@ -750,3 +756,127 @@ class MolecularCRescaleBarostat(CRescaleBarostat):
         _lib.check(self._o._h, self._o._L.admp_md_mol_info(self._o._h, out), 'admp_md_mol_info')
         keys = ('tiles', 'tile_atoms', 'largest_group', 'atoms', 'groups', 'lds_bytes', 'lanes', 'launches')
         return dict(zip(keys, (int(x) for x in out)))
+
+
+class FireMinimizer:
+    """FIRE energy minimiser (Bitzek et al., PRL 97, 170201, 2006) with the half step back of FIRE 2.0 (Guenole et al., Comput.
+    Mater. Sci. 175, 109584, 2020), semi-implicit Euler and a hard displacement cap; units as in VelocityVerlet (the rule is
+    csrc/md_fire_math.h, the entry admp_md_fire_step).  `masses` (amu; None: 1 for every atom) weigh the force step, w_i = 1e-4 /
+    m_i.  Per iteration, with F = -grad, P = sum F.v:
+
+        P > 0:      v <- (1 - alpha) v + alpha |v| F / |F| (norms over all atoms); after `n_delay` such steps in a row
+                    dt <- min(dt f_inc, dt_max), alpha <- alpha f_alpha
+        otherwise:  x <- x - (last step / 2) v;  v <- 0;  dt <- dt f_dec (not below dt_min);  alpha <- alpha_start
+        then        v <- v + s w F;  x <- x + s v,   s the largest value <= dt for which no atom moves more than `max_step` (A)
+
+    The minimiser owns the velocities `vel` and the state (2 x 8 doubles on the device: dt, alpha, n_pos, dtv_last, fmax,
+    iterations, uphill steps, flags); `step` is one C call that reads nothing back, `info()` is one host read.  With
+    `constraints` (a Constraints of the same atoms) every step is followed by the projection of positions and velocities onto
+    them, so the minimum found is the one ON the constraints.  For a given number of atoms the result is a function of the
+    inputs alone, bit for bit."""
+    ACC = VelocityVerlet.ACC
+    STATE_WORDS = ('dt', 'alpha', 'n_pos', 'dtv_last', 'fmax', 'iterations', 'uphill_steps')      # and the flags word
+    DONE, FAILED = 1, 2
+
+    def __init__(self, handle_owner, n_atoms, masses=None, *, dt_start_fs=0.5, dt_max_fs=5.0, dt_min_fs=0.01, max_step=0.1,
+                 n_delay=20, f_inc=1.1, f_dec=0.5, alpha_start=0.25, f_alpha=0.99, constraints=None):
+        self._o = handle_owner
+        self.n_atoms = int(n_atoms)
+        if self.n_atoms < 0 or self.n_atoms != n_atoms:
+            raise ValueError('n_atoms must be an integer that is not negative')
+        m = np.ones(self.n_atoms) if masses is None else np.asarray(masses, dtype=np.float64).reshape(-1)
+        if len(m) != self.n_atoms:
+            raise ValueError('%d masses for %d atoms' % (len(m), self.n_atoms))
+        if not (np.all(m > 0) and np.all(np.isfinite(m))):
+            raise ValueError('masses must be positive and finite')
+        self.dt_start, self.dt_max, self.dt_min, self.max_step = float(dt_start_fs), float(dt_max_fs), float(dt_min_fs), float(max_step)
+        self.n_delay, self.f_inc, self.f_dec = n_delay, float(f_inc), float(f_dec)
+        self.alpha_start, self.f_alpha = float(alpha_start), float(f_alpha)
+        for name in ('dt_start', 'dt_max', 'dt_min', 'max_step'):
+            if not (np.isfinite(getattr(self, name)) and getattr(self, name) > 0):
+                raise ValueError('%s must be positive and finite' % name)
+        if not self.dt_min <= self.dt_start <= self.dt_max:
+            raise ValueError('dt_min <= dt_start <= dt_max is required')
+        if n_delay != int(n_delay) or n_delay < 0:
+            raise ValueError('n_delay must be an integer that is not negative')
+        if not (np.isfinite(self.f_inc) and self.f_inc >= 1):
+            raise ValueError('f_inc must be finite and at least 1')
+        for name in ('f_dec', 'alpha_start', 'f_alpha'):
+            if not 0 < getattr(self, name) <= 1:
+                raise ValueError('%s must lie in (0, 1]' % name)
+        if constraints is not None and not (isinstance(constraints, Constraints) and constraints.n_atoms == self.n_atoms):
+            raise ValueError('constraints must be a Constraints of the same %d atoms' % self.n_atoms)
+        self.constraints = constraints
+        self.inv_mass = handle_owner._real(1.0 / m)
+        self._params = _lib.darr([self.dt_start, self.dt_max, self.dt_min, self.max_step, float(int(n_delay)), self.f_inc, self.f_dec,
+                                  self.alpha_start, self.f_alpha])
+        self.vel = torch.zeros((self.n_atoms, 3), dtype=handle_owner._dtype, device=handle_owner._device)
+        self.state = torch.zeros((2, 8), dtype=torch.float64, device=handle_owner._device)
+        self.reset()
+
+    def reset(self):
+        """velocities zero, a fresh state in both slots, call = 0: also what clears `failed`"""
+        self.vel.zero_()
+        fresh = torch.tensor([self.dt_start, self.alpha_start, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float64)
+        self.state.copy_(fresh.expand(2, 8))
+        self.call = 0
+
+    def step(self, pos, grad, ftol=0.0, box=None):
+        """one iteration in place on pos and self.vel with grad = +dE/dpos at pos; nothing is read back.  Frozen (nothing moves)
+        once max |F_i| <= ftol (`done`; a later call with a larger force resumes) or after a non-finite word (`failed`, until
+        reset()).  box: the cell of the constraints, required with them."""
+        o = self._o
+        _checked(o, self.n_atoms, pos=pos, grad=grad)
+        ftol = float(ftol)
+        if not (np.isfinite(ftol) and ftol >= 0):
+            raise ValueError('ftol must be finite and not negative')
+        if self.constraints is not None and box is None:
+            raise ValueError('box is required with constraints')
+        o._use_current_stream()
+        P = o._ptr
+        rc = o._L.admp_md_fire_step(o._h, self.n_atoms, P(pos), P(self.vel), P(grad), P(self.inv_mass), self._params, ftol,
+                                    self.call & (2 ** 64 - 1), P(self.state))
+        if rc == -1:                                                  # ADMP_E_ARG
+            msg = o._L.admp_last_error(o._h)
+            raise ValueError('admp_md_fire_step: %s' % (msg.decode() if msg else ''))
+        _lib.check(o._h, rc, 'admp_md_fire_step')
+        self.call += 1
+        if self.constraints is not None:
+            self.constraints.project_positions(pos, box)
+            self.constraints.project_velocities(pos, self.vel, box, dt_fs=self.dt_max)
+
+    def info(self):
+        """(host read) the state after the last step: dt, alpha, n_pos, dtv_last, fmax (the largest |F_i| the last step saw),
+        iterations, uphill_steps, and the flags as the bools done and failed"""
+        w = self.state[self.call & 1].cpu().numpy()
+        out = dict(zip(self.STATE_WORDS, (float(x) for x in w[:7])))
+        for k in ('n_pos', 'iterations', 'uphill_steps'):
+            out[k] = int(out[k])
+        out['done'], out['failed'] = int(w[7]) == self.DONE, int(w[7]) == self.FAILED
+        return out
+
+    def fmax(self):
+        """(host read) the largest |F_i| the last step saw"""
+        return self.info()['fmax']
+
+    def converged(self):
+        """(host read) whether the last step found max |F_i| <= ftol"""
+        return self.info()['done']
+
+    def minimize(self, pos, gradient_fn, ftol, max_iter, check_every=10, box=None):
+        """at most max_iter iterations of grad = gradient_fn(pos); step(pos, grad, ftol, box), with one host read every
+        `check_every` of them: stops on done, raises FloatingPointError on failed.  Returns info()."""
+        if check_every != int(check_every) or check_every < 1:
+            raise ValueError('check_every must be an integer of at least 1')
+        for it in range(int(max_iter)):
+            self.step(pos, gradient_fn(pos), ftol, box)
+            if (it + 1) % check_every == 0:
+                info = self.info()
+                if info['failed']:
+                    raise FloatingPointError('FIRE: a force or a velocity is not finite (iteration %d)' % info['iterations'])
+                if info['done']:
+                    return info
+        info = self.info()
+        if info['failed']:
+            raise FloatingPointError('FIRE: a force or a velocity is not finite (iteration %d)' % info['iterations'])
+        return info

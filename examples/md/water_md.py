@@ -1,7 +1,8 @@
 """What the MD drivers of this directory share (nve_water.py, nvt_water.py, npt_water.py, mts_water.py): the water force field's bonded
 constants, the command-line arguments, the calculators with their Verlet lists, the `forces` closure and the `box_gradient`
-closure of the NPT driver, the capped steepest descent that relaxes the synthetic box before a run, and the start of the
-rigid-water drivers (rigid_water.py, npt_water.py --rigid)."""
+closure of the NPT driver, the minimisation that relaxes the synthetic box before a run (capped steepest descent, or
+--minimizer fire: admp_amd.md.FireMinimizer; minimize_water.py runs the two side by side), and the start of the rigid-water
+drivers (rigid_water.py, npt_water.py --rigid)."""
 import os
 import sys
 import types
@@ -42,6 +43,9 @@ def add_arguments(ap):
     ap.add_argument('--cut', action='store_true', help='set_cutoff(rc) on the three calculators: every term is then the one of the '
                     'exact-rc list whatever the age of the skin list (default off: every listed pair counts, as in the reference)')
     ap.add_argument('--minimize', type=int, default=200)
+    ap.add_argument('--minimizer', choices=('sd', 'fire'), default='sd', help='sd: capped steepest descent (0.02 A per evaluation, one host '
+                    'read each); fire: admp_amd.md.FireMinimizer (one C call per iteration, the control loop on the device); the '
+                    'rigid-water drivers then minimise a second time ON the constraints')
     ap.add_argument('--temp', type=float, default=300.0)
     ap.add_argument('--mesh', type=int, default=0, help='PME mesh size per dimension (0: the reference rule)')
     ap.add_argument('--log', type=int, default=10, help='steps between energy records (each costs two host reads)')
@@ -161,8 +165,38 @@ def setup(opt):
                                  forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient)
 
 
+def minimize_fire(w, opt, pos, gradient=None, epot=None, constraints=None, label='minimize'):
+    """opt.minimize iterations of admp_amd.md.FireMinimizer on a copy of pos, the list rebuilt every opt.rebuild iterations;
+    gradient (default: w.forces, everything) -> (e, grad) and epot (default: w.epot_now) -> the energy of e for a printed line;
+    constraints: a Constraints to minimise on.  Returns (pos, pairs, e, grad) at the end, like minimize()."""
+    from admp_amd.md import FireMinimizer
+    nbl = w.nbl
+    gradient, epot = gradient or w.forces, epot or w.epot_now
+    pos = pos.clone().contiguous()
+    fm = FireMinimizer(w.pme, 3 * w.n_mol, np.tile(MASS, w.n_mol), constraints=constraints)
+    pairs = nbl.allocate(pos)
+    for it in range(opt.minimize):
+        e, grad = gradient(pos, pairs)
+        if it % 50 == 0 or it == opt.minimize - 1:
+            print('%s %4d  Epot %14.4f' % (label, it, epot(e)))
+        fm.step(pos, grad, 0.0, w.box if constraints is not None else None)
+        if (it + 1) % opt.rebuild == 0:
+            pairs = nbl.allocate(pos)
+    info = fm.info()
+    if info['failed']:
+        raise FloatingPointError('FIRE: a force or a velocity is not finite')
+    print('# FIRE: %d iterations, %d uphill, dt %.3f fs, largest |F_i| before the last step %.3f kJ/mol/A'
+          % (info['iterations'], info['uphill_steps'], info['dt'], info['fmax']))
+    pairs = nbl.allocate(pos)
+    e, grad = gradient(pos, pairs)
+    return pos, pairs, e, grad
+
+
 def minimize(w, opt, pos):
-    """the synthetic box is not equilibrated: capped steepest descent first; returns (pos, pairs, e123, grad) at the end"""
+    """the synthetic box is not equilibrated: it is relaxed first, by capped steepest descent or (--minimizer fire) by FIRE;
+    returns (pos, pairs, e123, grad) at the end"""
+    if getattr(opt, 'minimizer', 'sd') == 'fire':
+        return minimize_fire(w, opt, pos)
     nbl, forces, epot_now = w.nbl, w.forces, w.epot_now
     pairs = nbl.allocate(pos)
     e123, grad = forces(pos, pairs)
@@ -225,6 +259,9 @@ def rigid_start(w, opt, masses):
     pos, _, _, _ = minimize(w, opt, w.pos)                                 # flexible, as the other drivers
     print('# constraint error before the projection %.3e' % constraint_error(pos))
     con.project_positions(pos, box)
+    if getattr(opt, 'minimizer', 'sd') == 'fire':      # a second stage ON the constraints, without the bonded terms they replace
+        pos, _, _, _ = minimize_fire(w, opt, pos, gradient=gradient, epot=epot_now, constraints=con, label='minimize (rigid)')
+        print('# constraint error after the constrained minimisation %.3e' % constraint_error(pos))
     pairs_l = nbl.allocate(pos)
     e123, grad = gradient(pos, pairs_l)
     vel = maxwell_boltzmann(con, masses, opt.temp, opt.seed)

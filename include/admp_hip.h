@@ -375,8 +375,31 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       Both: ADMP_E_ARG for a call without a plan, n_atoms other than the plan's, a singular or non-finite box.
  *   admp_md_mol_info    out8: tiles, tile capacity, largest group, atoms, groups, LDS bytes per workgroup, lanes of a
  *                       workgroup, launches so far (zeros but for the launches without a plan)
- * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE);
- * admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is launched. */
+ *   admp_md_fire_step   one iteration of the FIRE energy minimiser (Bitzek et al. 2006, with the half step back of FIRE 2.0,
+ *                       Guenole et al. 2020; semi-implicit Euler; hard displacement cap; the rule is csrc/md_fire_math.h) in two
+ *                       launches, its decision logic on the device, nothing read back.  With F = -grad and w_i = 1e-4 inv_mass_i
+ *                       six words are reduced in double on both precisions, without atomics (one row per workgroup, folded in a
+ *                       fixed order): Fv = sum F.v, FF = sum |F|^2, vv = sum |v|^2, vmax = max |v|, fmax = max |F|, amax =
+ *                       max w |F|.  A word that is not finite sets flag 2 (failed): nothing moves, in this call or any later one,
+ *                       until the caller writes a fresh state.  fmax <= ftol sets flag 1 (done): nothing moves; a later call with
+ *                       a larger fmax resumes.  Fv > 0: a = 1 - alpha, b = alpha sqrt(vv / FF), back = 0, n_pos += 1, and if
+ *                       n_pos > n_delay: dt = min(dt f_inc, dt_max), alpha *= f_alpha (a and b keep the old alpha); vb = a vmax +
+ *                       b fmax.  Otherwise: a = b = 0, back = dtv_last / 2, n_pos = 0, dt *= f_dec if that stays >= dt_min, alpha
+ *                       = alpha_start, vb = 0, uphill steps += 1.  dtv = min(dt, 2 max_step / (vb + sqrt(vb^2 + 4 amax
+ *                       max_step))), the largest step with dtv vb + dtv^2 amax <= max_step; dtv_last = dtv; iterations += 1.
+ *                       Per atom, the four coefficients rounded to the handle's precision once: x -= back v; v = a v + b F;
+ *                       v += dtv w F; x += dtv v -- no atom's forward move exceeds max_step.
+ *                       params9 (HOST) = dt_start (not read by the step), dt_max, dt_min, max_step, n_delay, f_inc, f_dec,
+ *                       alpha_start, f_alpha.  state16_dev (DEVICE, the caller's): two slots of 8 doubles = dt, alpha, n_pos,
+ *                       dtv_last, fmax, iterations, uphill steps, flags; the call reads slot call & 1 and writes slot
+ *                       (call + 1) & 1 in full (a frozen call copies it forward), `call` being the caller's call counter.  For a
+ *                       given n positions, velocities and state are functions of the inputs alone, bit for bit.  n_atoms = 0
+ *                       launches nothing and copies the slot forward on the stream.  ADMP_E_ARG for a null pointer, n_atoms < 0,
+ *                       dt_min, dt_max or max_step not finite and positive, dt_min > dt_max, f_inc < 1, f_dec, alpha_start or
+ *                       f_alpha outside (0, 1], n_delay < 0, ftol negative or not finite -- and for a slab-decomposed handle.
+ * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE;
+ * admp_md_fire_step: ADMP_E_ARG); admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is
+ * launched. */
 int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
                    const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
                    void* grad_inout);
@@ -414,6 +437,8 @@ int admp_md_mol_sums(admp_handle* h, int n_atoms, const void* positions, const v
 int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* inv_mass, const double* box,
                       double mu_minus_1, double inv_mu_minus_1);
 int admp_md_mol_info(admp_handle* h, int64_t* out8);
+int admp_md_fire_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
+                      const double* params9, double ftol, uint64_t call, double* state16_dev);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
