@@ -26,9 +26,10 @@
 #include <vector>
 
 #include "../../include/admp_hip.h"
+#include "dev_buf.h"
 #include "dft_math.h"
+#include "handle.h"
 #include "launch.h"
-#include "md_fire_math.h"
 #include "rccl_comm.h"
 #include "scf_policy.h"
 
@@ -36,133 +37,23 @@ using namespace admp;
 
 namespace {
 
-struct Err {
-  int code;
-  std::string msg;
-};
-
-#define HIP_TRY(x)                                                                                       \
-  do {                                                                                                   \
-    hipError_t e_ = (x);                                                                                 \
-    if (e_ != hipSuccess) throw Err{ADMP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)};          \
-  } while (0)
 #define FFT_TRY(x)                                                                                       \
   do {                                                                                                   \
     rocfft_status s_ = (x);                                                                              \
     if (s_ != rocfft_status_success) throw Err{ADMP_E_FFT, std::string(#x) + ": rocfft status " + std::to_string((int)s_)}; \
   } while (0)
-#define ARG_CHECK(c, m) \
-  do { if (!(c)) throw Err{ADMP_E_ARG, m}; } while (0)
 
 std::once_flag g_fft_once;
 
-// growable device buffer
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  void need(size_t n) {
-    if (n <= bytes) return;
-    if (p) HIP_TRY(hipFree(p));
-    p = nullptr;
-    bytes = 0;
-    HIP_TRY(hipMalloc(&p, n));
-    bytes = n;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class U> U* as() const { return reinterpret_cast<U*>(p); }
-};
-
-// per-label launch timing with HIP events on the engine's stream
-struct Profiler {
-  bool on = false;
-  std::string only;   // when non-empty, only sections with exactly this label are bracketed
-  struct Rec { int label; hipEvent_t a, b; };
-  std::vector<std::string> labels;
-  std::map<std::string, int> index;
-  std::vector<double> total_ms;
-  std::vector<int64_t> count;
-  std::vector<Rec> pending;
-  std::vector<hipEvent_t> pool;
-  hipEvent_t get() {
-    if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-    hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));
-    return e;
-  }
-  int id(const char* name) {
-    auto it = index.find(name);
-    if (it != index.end()) return it->second;
-    int k = (int)labels.size();
-    labels.push_back(name); index[name] = k; total_ms.push_back(0.0); count.push_back(0);
-    return k;
-  }
-  void begin(const char* name, hipStream_t st, Rec& r) {
-    r.label = id(name); r.a = get(); r.b = get();
-    HIP_TRY(hipEventRecord(r.a, st));
-  }
-  void end(hipStream_t st, Rec& r) {
-    HIP_TRY(hipEventRecord(r.b, st));
-    pending.push_back(r);
-  }
-  void collect(hipStream_t st) {
-    if (pending.empty()) return;
-    HIP_TRY(hipStreamSynchronize(st));
-    for (auto& r : pending) {
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, r.a, r.b));
-      total_ms[r.label] += ms; count[r.label] += 1;
-      pool.push_back(r.a); pool.push_back(r.b);
-    }
-    pending.clear();
-  }
-  void reset(hipStream_t st) {
-    collect(st);
-    for (auto& v : total_ms) v = 0.0;
-    for (auto& v : count) v = 0;
-  }
-  void destroy() {
-    for (auto& r : pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto e : pool) (void)hipEventDestroy(e);
-    pending.clear(); pool.clear();
-  }
-};
-
-struct Scoped {
-  Profiler& p; hipStream_t st; Profiler::Rec r; bool active;
-  Scoped(Profiler& p_, const char* name, hipStream_t st_) : p(p_), st(st_), active(p_.on && (p_.only.empty() || p_.only == name)) {
-    if (active) p.begin(name, st, r);
-  }
-  ~Scoped() { if (active) p.end(st, r); }
-};
-#define TIMED(name) Scoped scoped_timer_(prof, name, stream)
-
-void invert3(const double* h, double* inv, double* det) {
-  double d = h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]);
-  inv[0] = (h[4] * h[8] - h[5] * h[7]) / d; inv[1] = (h[2] * h[7] - h[1] * h[8]) / d; inv[2] = (h[1] * h[5] - h[2] * h[4]) / d;
-  inv[3] = (h[5] * h[6] - h[3] * h[8]) / d; inv[4] = (h[0] * h[8] - h[2] * h[6]) / d; inv[5] = (h[2] * h[3] - h[0] * h[5]) / d;
-  inv[6] = (h[3] * h[7] - h[4] * h[6]) / d; inv[7] = (h[1] * h[6] - h[0] * h[7]) / d; inv[8] = (h[0] * h[4] - h[1] * h[3]) / d;
-  *det = d;
-}
-
-struct EngineBase {
+struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, srank, snranks, md (handle.h)
   virtual ~EngineBase() {}
-  int device = 0;
-  int prec = 8;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  Profiler prof;
   Topology top;
   NbrTable nbr;
   bool have_top = false, have_ewald = false, have_pairs = false;
   double kappa = 0;
   int K[3] = {0, 0, 0};
   int lmax = 2, lpol = 0;
-  int srank = 0, snranks = 1;   // x-slab decomposition (admp_slab_configure)
-  admp_comm comm{};             // ... and the caller's communicator (admp_set_comm); unused with one rank
+  admp_comm comm{};             // the caller's communicator of the x-slab decomposition (admp_set_comm); unused with one rank
   bool have_comm = false;
   // collectives of a decomposed evaluation: every rank makes the same calls in the same order
   admp_rccl* rccl = nullptr;    // native communicator (admp_set_comm_rccl): the collectives go straight to RCCL on `stream`
@@ -333,41 +224,6 @@ struct EngineBase {
                            int32_t* info) = 0;
   virtual void mscale_grad(int kind, const void* pos, const double* box, const void* par, int pmax, int ns, double* out,
                            int on_device) = 0;
-  virtual void md_bonded(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na,
-                         const int32_t* aidx, const void* apar, double* E_dev, void* grad) = 0;
-  virtual void md_kick_drift(int n, void* pos, void* vel, const void* grad, const void* inv_mass, double half_dt_acc, double dt,
-                             double* ekin_dev) = 0;
-  virtual void md_langevin(int n, void* pos, void* vel, const void* grad, const void* inv_mass, double half_dt_acc, double dt,
-                           double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin_dev) = 0;
-  virtual void md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) = 0;
-  virtual void md_bonded_box(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na,
-                             const int32_t* aidx, const void* apar, double* E_dev, double* S_dev) = 0;
-  virtual void md_virial(int n, const void* pos, const void* vel, const void* grad, const void* inv_mass, uint64_t seed,
-                         uint64_t step, double* out_dev) = 0;
-  virtual void md_scale(int n, void* pos, void* vel, double mu) = 0;
-  virtual void md_mts_plan(int n_atoms, int nb, const int32_t* bidx, const double* bpar, int na, const int32_t* aidx,
-                           const double* apar, int tile_atoms) = 0;
-  virtual void md_mts_step(int n, void* pos, void* vel, const void* grad_slow, const void* inv_mass, const double* box,
-                           double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc, uint64_t seed,
-                           uint64_t outer_step, double* E_dev, void* grad_fast) = 0;
-  virtual void md_mts_info(int64_t* out) = 0;
-  virtual void md_con_plan(int n_atoms, int n_cons, const int32_t* pairs, const double* lengths, int tile_atoms) = 0;
-  virtual void md_con_step(int n, void* pos, void* vel, const void* grad, const void* inv_mass, const double* box, double half_dt_acc,
-                           double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double tol, int max_sweeps,
-                           int32_t* counters_dev) = 0;
-  virtual void md_con_kick(int n, const void* pos, void* vel, const void* grad, const void* inv_mass, const double* box,
-                           double half_dt_acc, double dt, double tol, int max_sweeps, double* ekin_dev, int32_t* counters_dev) = 0;
-  virtual void md_con_project(int n, void* pos, const void* ref, const void* inv_mass, const double* box, double tol, int max_sweeps,
-                              int32_t* counters_dev) = 0;
-  virtual void md_con_info(int64_t* out) = 0;
-  virtual void md_mol_plan(int n_atoms, const int32_t* group_of, int tile_atoms) = 0;
-  virtual void md_mol_sums(int n, const void* pos, const void* vel, const void* grad, const void* inv_mass, const double* box,
-                           uint64_t seed, uint64_t step, double* out_dev) = 0;
-  virtual void md_mol_scale(int n, void* pos, void* vel, const void* inv_mass, const double* box, double mu_minus_1,
-                            double inv_mu_minus_1) = 0;
-  virtual void md_mol_info(int64_t* out) = 0;
-  virtual void md_fire_step(int n, void* pos, void* vel, const void* grad, const void* inv_mass, const double* par9, double ftol,
-                            uint64_t call, double* state16_dev) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
   virtual void nbr_fill(int32_t* pairs) = 0;
   virtual void nbr_table(const void* pos, const double* box, double rc) = 0;
@@ -559,8 +415,7 @@ struct EngineBase {
       apply_classes();
       order_rows();
     }
-    HIP_TRY(hipStreamSynchronize(stream));
-    staged.release();
+    HIP_TRY(hipStreamSynchronize(stream));      // `staged` is freed on the way out, and on the way out of a throw above
     have_pairs = true;
     ++nbr_gen;
   }
@@ -578,10 +433,6 @@ struct SlabState {
   const int* home = nullptr;    // home atoms, ascending
   const int* rows = nullptr;    // home rows in the pair kernels' order (the table's class-grouped order, filtered)
   const int* act = nullptr;     // polarizable home atoms, ascending
-  void release() {
-    for (DevBuf* b : {&owner, &owner_prev, &mig, &bits, &counts, &totals, &lists, &imp, &exp, &mig_in, &mig_out, &sendb, &recvb,
-                      &ghost, &pack, &tbuf}) b->release();
-  }
 };
 
 template <class T>
@@ -651,24 +502,14 @@ struct Engine : EngineBase {
   ScfHistory scf;             // residual history of the polarizable calls of this handle: picks the form of the next one
   bool mono_ok = false;       // this evaluation may use the charge-only pair forms (no dE/dQ_local requested)
 
+  // Every DevBuf member frees itself after this body, so after the stream is gone: hipFree needs no stream, and admp_destroy
+  // has set the device and synchronised the stream before it deletes the handle.
   ~Engine() override {
     destroy_plans();
-    for (DevBuf* b : {&sites, &grad, &pot, &fld_pair, &fld_recip, &field, &energies_d, &s_pos, &s_Q, &s_pol,
-                      &s_thole, &s_U, &s_out, &s_dQ, &s_par, &mesh, &spec, &gtabs[0], &gtabs[1], &gtabs[2], &gtabs[3], &fft_work, &binv_d, &scan_scratch, &bin_cells,
-                      &bin_sorted, &bin_scan, &home_list, &dft_tw, &bases_d, &vir_d, &act_d, &isites, &mesh2, &act_tmp,
-                      &rq_d, &pfa_tw, &pfa_fmap, &pfa_ptab, &gtab_nat, &fx_tw, &bin_cells_ind, &bin_sorted_ind, &srow_d, &onehot_d, &tcount_d, &prune_rowptr, &prune_cnt, &prune_col,
-                      &cut_end, &cut_col, &cut_iend, &cut_icol, &xctab, &xctab_flag})
-      b->release();
     free_topology();
     if (ind.end) (void)hipFree(ind.end);
     if (ind.col) (void)hipFree(ind.col);
     cells.release();
-    sl.release();
-    mts.ints.release();
-    mts.reals.release();
-    con.ints.release();
-    con.reals.release();
-    fire_rows.release();
     free_programs();
     if (Eh) (void)hipHostFree(Eh);
     prof.destroy();
@@ -1233,13 +1074,7 @@ struct Engine : EngineBase {
   void fft_inverse(T* spec_p, T* mesh_p) { run_plan("rocfft_c2r", plan_b, spec_p, mesh_p); }
   void fft_x(T* buf, int inverse) { run_plan(inverse ? "rocfft_x_inv" : "rocfft_x_fwd", inverse ? plan_xb : plan_xf, buf, buf); }
 
-  Box<T> make_box(const double* h, double* inv, double* vol) {
-    Box<T> b;
-    invert3(h, inv, vol);
-    ARG_CHECK(std::fabs(*vol) > 1e-12, "singular box");
-    for (int k = 0; k < 9; ++k) { b.h[k] = (T)h[k]; b.hinv[k] = (T)inv[k]; }
-    return b;
-  }
+  Box<T> make_box(const double* h, double* inv, double* vol) { return admp::make_box<T>(h, inv, vol); }
 
   RecipGeom<T> make_geom(const double* inv) {
     // every spread and gather comes through here; only admp_mesh_convolve, which has no splines, takes shorter meshes
@@ -2490,342 +2325,6 @@ struct Engine : EngineBase {
     vir_assemble(inv, 0.0, dbox);      // only the xw sums are non-zero here
   }
 
-  // ---- MD-driver helpers (md_kernels.hip): device pointers, nothing read back -----------------------------
-  void md_bonded(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na, const int32_t* aidx,
-                 const void* apar, double* E_dev, void* grad_) override {
-    ARG_CHECK(pos && box && E_dev && grad_ && nb >= 0 && na >= 0, "bad argument");
-    ARG_CHECK((nb == 0 || (bidx && bpar)) && (na == 0 || (aidx && apar)), "bond / angle lists missing");
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    TIMED("md_bonded");
-    launch_md_bonded<T>(stream, nb, bidx, reinterpret_cast<const T*>(bpar), na, aidx, reinterpret_cast<const T*>(apar),
-                        reinterpret_cast<const T*>(pos), bx, reinterpret_cast<T*>(grad_), E_dev);
-  }
-  void md_kick_drift(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, double half_dt_acc, double dt,
-                     double* ekin_dev) override {
-    ARG_CHECK(n >= 0 && vel && grad_ && inv_mass && (dt == 0.0 || pos), "bad argument");
-    TIMED("md_kick_drift");
-    launch_md_kick_drift<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), reinterpret_cast<const T*>(grad_),
-                            reinterpret_cast<const T*>(inv_mass), half_dt_acc, dt, ekin_dev);
-  }
-  void md_langevin(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, double half_dt_acc, double dt, double c1,
-                   double c2sq_kT_acc, uint64_t seed, uint64_t step, double* ekin_dev) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && pos && vel && grad_ && inv_mass, "bad argument");
-    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
-    TIMED("md_langevin");
-    launch_md_langevin<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), reinterpret_cast<const T*>(grad_),
-                          reinterpret_cast<const T*>(inv_mass), half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, ekin_dev);
-    HIP_TRY(hipGetLastError());
-  }
-  void md_random(int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream_id, void* out) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(kind == 0 || kind == 1, "kind must be 0 (words) or 1 (normals)");
-    ARG_CHECK(n >= 0 && n <= (int64_t)1 << 32 && (n == 0 || out), "bad argument (the atom index is a 32-bit counter word)");
-    TIMED("md_random");
-    launch_md_random<T>(stream, kind, n, seed, step, stream_id, out);
-    HIP_TRY(hipGetLastError());
-  }
-  // the isotropic barostat's three (admp_amd/md.py CRescaleBarostat): every argument is checked before the first launch
-  void md_bonded_box(const void* pos, const double* box, int nb, const int32_t* bidx, const void* bpar, int na, const int32_t* aidx,
-                     const void* apar, double* E_dev, double* S_dev) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(box && E_dev && S_dev && nb >= 0 && na >= 0 && nb <= INT_MAX / 4 - na, "bad argument");
-    ARG_CHECK(nb + na == 0 || pos, "positions missing");
-    ARG_CHECK((nb == 0 || (bidx && bpar)) && (na == 0 || (aidx && apar)), "bond / angle lists missing");
-    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    TIMED("md_bonded_box");
-    launch_md_bonded_box<T>(stream, nb, bidx, reinterpret_cast<const T*>(bpar), na, aidx, reinterpret_cast<const T*>(apar),
-                            reinterpret_cast<const T*>(pos), bx, E_dev, S_dev);
-    HIP_TRY(hipGetLastError());
-  }
-  void md_virial(int n, const void* pos, const void* vel, const void* grad_, const void* inv_mass, uint64_t seed, uint64_t step,
-                 double* out_dev) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && out_dev && (n == 0 || (pos && vel && grad_ && inv_mass)), "bad argument");
-    TIMED("md_virial");
-    HIP_TRY(hipMemsetAsync(out_dev, 0, 21 * sizeof(double), stream));
-    launch_md_virial<T>(stream, n, reinterpret_cast<const T*>(pos), reinterpret_cast<const T*>(vel),
-                        reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), seed, step, out_dev);
-    HIP_TRY(hipGetLastError());
-  }
-  void md_scale(int n, void* pos, void* vel, double mu) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && (n == 0 || (pos && vel)), "bad argument");
-    ARG_CHECK(std::isfinite(mu) && mu > 0.0 && std::isfinite(1.0 / mu), "the scale factor must be finite and positive");
-    TIMED("md_scale");
-    launch_md_scale<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel), mu, 1.0 / mu);
-    HIP_TRY(hipGetLastError());
-  }
-  // the multiple-time-step integrator (mts_kernels.hip; admp_amd/md.py MTSLangevin): the plan of the bonded lists is made on
-  // the host (mts_plan.h) and kept on the handle until the next one replaces it
-  struct MtsState {
-    bool have = false;
-    int n_atoms = 0, tile_atoms = 0, max_component = 0, n_bonds = 0, n_angles = 0, threads = 0;
-    size_t lds_bytes = 0;
-    int64_t launches = 0;
-    MtsTiles<T> tiles{};
-    DevBuf ints, reals;
-  } mts;
-  void md_mts_plan(int n_atoms, int nb, const int32_t* bidx, const double* bpar, int na, const int32_t* aidx, const double* apar,
-                   int tile_atoms) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && nb >= 0 && na >= 0, "bad argument");
-    ARG_CHECK((nb == 0 || (bidx && bpar)) && (na == 0 || (aidx && apar)), "bond / angle lists missing");
-    const MtsPlan p = mts_make_plan(n_atoms, nb, bidx, bpar, na, aidx, apar, tile_atoms == 0 ? kMtsDefaultTileAtoms : tile_atoms);
-    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
-    // one block of ints and one of reals (the parameters rounded to the handle's precision once)
-    const std::vector<int>* iv[8] = {&p.tile_atom0, &p.atom_id, &p.tile_bond0, &p.bond_slot, &p.tile_angle0, &p.angle_slot, &p.ref0, &p.ref};
-    std::vector<int> hi;
-    size_t off[8];
-    for (int k = 0; k < 8; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
-    std::vector<T> hr(p.bond_par.begin(), p.bond_par.end());
-    hr.insert(hr.end(), p.angle_par.begin(), p.angle_par.end());
-    HIP_TRY(hipStreamSynchronize(stream));      // a step of the plan being replaced may still read the old arrays
-    mts.have = false;
-    mts.ints.need(hi.size() * sizeof(int));
-    mts.reals.need((hr.size() + 1) * sizeof(T));
-    HIP_TRY(hipMemcpy(mts.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (!hr.empty()) HIP_TRY(hipMemcpy(mts.reals.p, hr.data(), hr.size() * sizeof(T), hipMemcpyHostToDevice));
-    const int* di = mts.ints.template as<int>();
-    MtsTiles<T>& m = mts.tiles;
-    m.n_tiles = p.n_tiles; m.dims = p.dims;
-    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_bond0 = di + off[2]; m.bond_slot = di + off[3];
-    m.tile_angle0 = di + off[4]; m.angle_slot = di + off[5]; m.ref0 = di + off[6]; m.ref = di + off[7];
-    m.bond_par = mts.reals.template as<T>(); m.angle_par = m.bond_par + p.bond_par.size();
-    mts.n_atoms = n_atoms; mts.tile_atoms = p.tile_atoms; mts.max_component = p.max_component; mts.n_bonds = nb; mts.n_angles = na;
-    mts.threads = mts_threads(p.tile_atoms);
-    mts.lds_bytes = mts_lds_bytes(p.dims, sizeof(T));
-    mts.have = true;
-  }
-  void md_mts_step(int n, void* pos, void* vel, const void* grad_slow, const void* inv_mass, const double* box,
-                   double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc, uint64_t seed,
-                   uint64_t outer_step, double* E_dev, void* grad_fast) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(mts.have, "admp_md_mts_plan must precede admp_md_mts_step");
-    ARG_CHECK(n == mts.n_atoms, "n_atoms differs from the plan's");
-    ARG_CHECK(n_inner >= 1, "n_inner must be at least 1");
-    ARG_CHECK(pos && vel && grad_slow && inv_mass && box, "bad argument");
-    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
-    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    TIMED("md_mts");
-    launch_md_mts<T>(stream, mts.tiles, mts.threads, mts.lds_bytes, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
-                     reinterpret_cast<const T*>(grad_slow), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc_outer, dt_outer,
-                     n_inner, c1, c2sq_kT_acc, seed, outer_step, E_dev, reinterpret_cast<T*>(grad_fast));
-    HIP_TRY(hipGetLastError());
-    mts.launches += 1;
-  }
-  void md_mts_info(int64_t* out) override {
-    ARG_CHECK(out, "bad argument");
-    const int64_t v[8] = {mts.have ? mts.tiles.n_tiles : 0, mts.tile_atoms, mts.max_component, mts.n_atoms, mts.n_bonds, mts.n_angles,
-                          (int64_t)mts.lds_bytes, mts.launches};
-    for (int k = 0; k < 8; ++k) out[k] = mts.have || k == 7 ? v[k] : 0;
-  }
-  // distance constraints (con_kernels.hip; admp_amd/md.py Constraints, ConstrainedLangevin): the plan of the constraint list is
-  // made on the host (con_plan.h) and kept on the handle until the next one replaces it
-  struct ConState {
-    bool have = false;
-    int n_atoms = 0, tile_atoms = 0, max_cluster = 0, n_cons = 0, n_clusters = 0, threads = 0;
-    size_t lds_bytes = 0;      // of k_con_project, the largest of the three
-    int64_t launches = 0;
-    ConTiles<T> tiles{};
-    DevBuf ints, reals;
-  } con;
-  void md_con_plan(int n_atoms, int n_cons, const int32_t* pairs, const double* lengths, int tile_atoms) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && n_cons >= 0, "bad argument");
-    ARG_CHECK(n_cons == 0 || (pairs && lengths), "constraint lists missing");
-    const ConPlan p = con_make_plan(n_atoms, n_cons, pairs, lengths, tile_atoms == 0 ? kConDefaultTileAtoms : tile_atoms);
-    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
-    const std::vector<int>* iv[5] = {&p.tile_atom0, &p.atom_id, &p.tile_clu0, &p.clu_con0, &p.con_slot};
-    std::vector<int> hi;
-    size_t off[5];
-    for (int k = 0; k < 5; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
-    const std::vector<T> hr(p.con_d2.begin(), p.con_d2.end());      // d^2 rounded to the handle's precision once
-    HIP_TRY(hipStreamSynchronize(stream));      // a launch of the plan being replaced may still read the old arrays
-    con.have = false;
-    con.ints.need(hi.size() * sizeof(int));
-    con.reals.need((hr.size() + 1) * sizeof(T));
-    HIP_TRY(hipMemcpy(con.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (!hr.empty()) HIP_TRY(hipMemcpy(con.reals.p, hr.data(), hr.size() * sizeof(T), hipMemcpyHostToDevice));
-    const int* di = con.ints.template as<int>();
-    ConTiles<T>& m = con.tiles;
-    m.n_tiles = p.n_tiles; m.dims = p.dims;
-    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_clu0 = di + off[2]; m.clu_con0 = di + off[3]; m.con_slot = di + off[4];
-    m.con_d2 = con.reals.template as<T>();
-    con.n_atoms = n_atoms; con.tile_atoms = p.tile_atoms; con.max_cluster = p.max_cluster; con.n_cons = n_cons;
-    con.n_clusters = p.n_clusters;
-    con.threads = mts_threads(p.tile_atoms);
-    con.lds_bytes = con_lds_bytes(p.dims, sizeof(T), true);
-    con.have = true;
-  }
-  // what the three launches share: every argument is checked before anything is launched
-  Box<T> md_con_checked(const char* what, int n, const void* inv_mass, const double* box, double tol, int max_sweeps) {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    if (!con.have) throw Err{ADMP_E_ARG, std::string("admp_md_con_plan must precede ") + what};
-    ARG_CHECK(n >= 0 && n == con.n_atoms, "n_atoms differs from the plan's");
-    ARG_CHECK(inv_mass && box, "bad argument");
-    ARG_CHECK(tol >= 0.0 && std::isfinite(tol), "the tolerance must be finite and not negative");
-    ARG_CHECK(max_sweeps >= 1, "max_sweeps must be at least 1");
-    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
-    double inv[9], vol;
-    return make_box(box, inv, &vol);
-  }
-  void md_con_step(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, const double* box, double half_dt_acc,
-                   double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step, double tol, int max_sweeps,
-                   int32_t* counters_dev) override {
-    const Box<T> bx = md_con_checked("admp_md_con_step", n, inv_mass, box, tol, max_sweeps);
-    ARG_CHECK(pos && vel && grad_, "bad argument");
-    ARG_CHECK(dt > 0.0 && std::isfinite(dt) && std::isfinite(half_dt_acc), "dt must be positive and finite");
-    ARG_CHECK(c1 >= 0.0 && c1 <= 1.0 && c2sq_kT_acc >= 0.0, "c1 must lie in [0, 1] and c2sq_kT_acc must not be negative");
-    TIMED("md_con_step");
-    launch_con_step<T>(stream, con.tiles, con.threads, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
-                       reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc, dt, c1, c2sq_kT_acc, seed,
-                       step, tol, max_sweeps, counters_dev);
-    HIP_TRY(hipGetLastError());
-    con.launches += 1;
-  }
-  void md_con_kick(int n, const void* pos, void* vel, const void* grad_, const void* inv_mass, const double* box, double half_dt_acc,
-                   double dt, double tol, int max_sweeps, double* ekin_dev, int32_t* counters_dev) override {
-    const Box<T> bx = md_con_checked("admp_md_con_kick", n, inv_mass, box, tol, max_sweeps);
-    ARG_CHECK(pos && vel, "bad argument");
-    ARG_CHECK(grad_ || half_dt_acc == 0.0, "a kick needs a gradient (half_dt_acc 0 with a NULL gradient is a pure projection)");
-    ARG_CHECK(dt > 0.0 && std::isfinite(dt) && std::isfinite(half_dt_acc), "dt must be positive and finite");
-    TIMED("md_con_kick");
-    launch_con_kick<T>(stream, con.tiles, con.threads, reinterpret_cast<const T*>(pos), reinterpret_cast<T*>(vel),
-                       reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, half_dt_acc, dt, tol, max_sweeps,
-                       ekin_dev, counters_dev);
-    HIP_TRY(hipGetLastError());
-    con.launches += 1;
-  }
-  void md_con_project(int n, void* pos, const void* ref, const void* inv_mass, const double* box, double tol, int max_sweeps,
-                      int32_t* counters_dev) override {
-    const Box<T> bx = md_con_checked("admp_md_con_project", n, inv_mass, box, tol, max_sweeps);
-    ARG_CHECK(pos && ref, "bad argument");
-    TIMED("md_con_project");
-    launch_con_project<T>(stream, con.tiles, con.threads, reinterpret_cast<T*>(pos), reinterpret_cast<const T*>(ref),
-                          reinterpret_cast<const T*>(inv_mass), bx, tol, max_sweeps, counters_dev);
-    HIP_TRY(hipGetLastError());
-    con.launches += 1;
-  }
-  void md_con_info(int64_t* out) override {
-    ARG_CHECK(out, "bad argument");
-    const int64_t v[8] = {con.tiles.n_tiles, con.tile_atoms, con.max_cluster, con.n_atoms, con.n_cons, con.n_clusters,
-                          (int64_t)con.lds_bytes, con.launches};
-    for (int k = 0; k < 8; ++k) out[k] = con.have || k == 7 ? v[k] : 0;
-  }
-  // molecular cell scaling (mol_kernels.hip; admp_amd/md.py MolecularCRescaleBarostat): the plan of the group partition is made
-  // on the host (mol_plan.h) and kept on the handle, in a slot of its own next to the two above, until the next one replaces it
-  struct MolState {
-    bool have = false;
-    int n_atoms = 0, tile_atoms = 0, max_group = 0, n_groups = 0, threads = 0;
-    size_t lds_bytes = 0;
-    int64_t launches = 0;
-    MolTiles tiles{};
-    DevBuf ints;
-  } mol;
-  void md_mol_plan(int n_atoms, const int32_t* group_of, int tile_atoms) override {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    ARG_CHECK(n_atoms > 0 && n_atoms <= INT_MAX / 4 && group_of, "bad argument");
-    const MolPlan p = mol_make_plan(n_atoms, group_of, tile_atoms == 0 ? kMolDefaultTileAtoms : tile_atoms);
-    if (!p.error.empty()) throw Err{ADMP_E_ARG, p.error};
-    const std::vector<int>* iv[5] = {&p.tile_atom0, &p.atom_id, &p.tile_grp0, &p.grp_atom0, &p.slot_grp};
-    std::vector<int> hi;
-    size_t off[5];
-    for (int k = 0; k < 5; ++k) { off[k] = hi.size(); hi.insert(hi.end(), iv[k]->begin(), iv[k]->end()); }
-    HIP_TRY(hipStreamSynchronize(stream));      // a launch of the plan being replaced may still read the old arrays
-    mol.have = false;
-    mol.ints.need(hi.size() * sizeof(int));
-    HIP_TRY(hipMemcpy(mol.ints.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
-    const int* di = mol.ints.template as<int>();
-    MolTiles& m = mol.tiles;
-    m.n_tiles = p.n_tiles; m.dims = p.dims;
-    m.tile_atom0 = di + off[0]; m.atom_id = di + off[1]; m.tile_grp0 = di + off[2]; m.grp_atom0 = di + off[3]; m.slot_grp = di + off[4];
-    mol.n_atoms = n_atoms; mol.tile_atoms = p.tile_atoms; mol.max_group = p.max_group; mol.n_groups = p.n_groups;
-    mol.threads = mts_threads(p.tile_atoms);
-    mol.lds_bytes = mol_lds_bytes(p.dims, sizeof(T));
-    mol.have = true;
-  }
-  // what the two launches share: every argument is checked before anything is launched
-  Box<T> md_mol_checked(const char* what, int n, const void* inv_mass, const double* box) {
-    HIP_TRY(hipSetDevice(device));
-    if (snranks > 1) throw Err{ADMP_E_STATE, "the MD helpers serve single-rank handles only"};
-    if (!mol.have) throw Err{ADMP_E_ARG, std::string("admp_md_mol_plan must precede ") + what};
-    ARG_CHECK(n >= 0 && n == mol.n_atoms, "n_atoms differs from the plan's");
-    ARG_CHECK(inv_mass && box, "bad argument");
-    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box must be finite");
-    double inv[9], vol;
-    return make_box(box, inv, &vol);
-  }
-  void md_mol_sums(int n, const void* pos, const void* vel, const void* grad_, const void* inv_mass, const double* box, uint64_t seed,
-                   uint64_t step, double* out_dev) override {
-    const Box<T> bx = md_mol_checked("admp_md_mol_sums", n, inv_mass, box);
-    ARG_CHECK(pos && vel && grad_ && out_dev, "bad argument");
-    TIMED("md_mol_sums");
-    HIP_TRY(hipMemsetAsync(out_dev, 0, 21 * sizeof(double), stream));
-    launch_md_mol_sums<T>(stream, mol.tiles, mol.threads, reinterpret_cast<const T*>(pos), reinterpret_cast<const T*>(vel),
-                          reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), bx, seed, step, out_dev);
-    HIP_TRY(hipGetLastError());
-    mol.launches += 1;
-  }
-  void md_mol_scale(int n, void* pos, void* vel, const void* inv_mass, const double* box, double mu_minus_1,
-                    double inv_mu_minus_1) override {
-    const Box<T> bx = md_mol_checked("admp_md_mol_scale", n, inv_mass, box);
-    ARG_CHECK(pos && vel, "bad argument");
-    // mu > 0 and finite, and the two factors belong to one mu: (1 + (mu - 1)) (1 + (1/mu - 1)) = 1
-    ARG_CHECK(std::isfinite(mu_minus_1) && std::isfinite(inv_mu_minus_1) && mu_minus_1 > -1.0 && inv_mu_minus_1 > -1.0,
-              "the scale factor must be finite and positive");
-    ARG_CHECK(std::fabs((1.0 + mu_minus_1) * (1.0 + inv_mu_minus_1) - 1.0) <= 1e-12, "mu_minus_1 and inv_mu_minus_1 are not those of one factor");
-    TIMED("md_mol_scale");
-    launch_md_mol_scale<T>(stream, mol.tiles, mol.threads, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
-                           reinterpret_cast<const T*>(inv_mass), bx, mu_minus_1, inv_mu_minus_1);
-    HIP_TRY(hipGetLastError());
-    mol.launches += 1;
-  }
-  void md_mol_info(int64_t* out) override {
-    ARG_CHECK(out, "bad argument");
-    const int64_t v[8] = {mol.tiles.n_tiles, mol.tile_atoms, mol.max_group, mol.n_atoms, mol.n_groups, (int64_t)mol.lds_bytes,
-                          mol.threads, mol.launches};
-    for (int k = 0; k < 8; ++k) out[k] = mol.have || k == 7 ? v[k] : 0;
-  }
-  // the FIRE minimiser (fire_kernels.hip, md_fire_math.h; admp_amd/md.py FireMinimizer): the handle owns the rows of partial
-  // sums, the caller the state; every argument is checked before the first launch
-  DevBuf fire_rows;
-  void md_fire_step(int n, void* pos, void* vel, const void* grad_, const void* inv_mass, const double* par9, double ftol,
-                    uint64_t call, double* state16_dev) override {
-    HIP_TRY(hipSetDevice(device));
-    ARG_CHECK(snranks == 1, "the MD helpers serve single-rank handles only (slab-decomposed handle)");
-    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && par9 && state16_dev && (n == 0 || (pos && vel && grad_ && inv_mass)), "bad argument");
-    const double dt_max = par9[FIRE_P_DT_MAX], dt_min = par9[FIRE_P_DT_MIN], max_step = par9[FIRE_P_MAX_STEP];
-    ARG_CHECK(std::isfinite(dt_max) && std::isfinite(dt_min) && std::isfinite(max_step) && dt_max > 0.0 && dt_min > 0.0 &&
-              max_step > 0.0 && dt_min <= dt_max, "dt_min, dt_max and max_step must be finite and positive, dt_min <= dt_max");
-    ARG_CHECK(par9[FIRE_P_N_DELAY] >= 0.0, "n_delay must not be negative");
-    ARG_CHECK(std::isfinite(par9[FIRE_P_F_INC]) && par9[FIRE_P_F_INC] >= 1.0, "f_inc must be finite and at least 1");
-    for (int w : {(int)FIRE_P_F_DEC, (int)FIRE_P_ALPHA_START, (int)FIRE_P_F_ALPHA})
-      ARG_CHECK(par9[w] > 0.0 && par9[w] <= 1.0, "f_dec, alpha_start and f_alpha must lie in (0, 1]");
-    ARG_CHECK(std::isfinite(ftol) && ftol >= 0.0, "ftol must be finite and not negative");
-    fire_rows.need(kFireRowsBytes);
-    TIMED("md_fire");
-    const int rc = launch_md_fire<T>(stream, n, reinterpret_cast<T*>(pos), reinterpret_cast<T*>(vel),
-                                     reinterpret_cast<const T*>(grad_), reinterpret_cast<const T*>(inv_mass), par9, ftol, call,
-                                     fire_rows.as<double>(), state16_dev);
-    if (rc != 0) throw Err{ADMP_E_HIP, std::string("FIRE step: ") + hipGetErrorString((hipError_t)rc)};
-  }
-
   // ---- neighbour search (cell list) ------------------------------------------------------------------
   CellScratch cells;
   int nb_na = 0; const T* nb_pos = nullptr; Box<T> nb_box; double nb_rc = 0;
@@ -3726,6 +3225,11 @@ static int guarded(admp_handle* h, F&& f) {
   }
 }
 
+// the same for a translation unit that knows only handle.h (md_driver.hip)
+int admp::handle_call(admp_handle* h, void (*fn)(HandleCtx&, void*), void* arg) {
+  return guarded(h, [&](EngineBase& e) { fn(e, arg); });
+}
+
 extern "C" {
 
 const char* admp_version(void) { return "admp_hip 0.1 (gfx950)"; }
@@ -3920,100 +3424,6 @@ int admp_thole_sums(admp_handle* h, const void* positions, const double* box, co
                     const void* tholes, int n_scales, const double* mScales, const double* pScales, const void* U,
                     void* sumX, void* sumXw) {
   return guarded(h, [&](EngineBase& e) { e.thole_sums(positions, box, Q_local, pol, tholes, n_scales, mScales, pScales, U, sumX, sumXw); });
-}
-
-int admp_md_bonded(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
-                   const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
-                   void* grad_inout) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_bonded(positions, box, n_bonds, bond_idx, bond_par, n_angles, angle_idx, angle_par, E_dev, grad_inout);
-  });
-}
-int admp_md_kick_drift(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
-                       double half_dt_acc, double dt, double* ekin_dev) {
-  return guarded(h, [&](EngineBase& e) { e.md_kick_drift(n_atoms, positions, velocities, grad, inv_mass, half_dt_acc, dt, ekin_dev); });
-}
-int admp_md_langevin(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
-                     double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
-                     double* ekin_dev) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_langevin(n_atoms, positions, velocities, grad, inv_mass, half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, ekin_dev);
-  });
-}
-int admp_md_random(admp_handle* h, int kind, int64_t n, uint64_t seed, uint64_t step, uint32_t stream, void* out) {
-  return guarded(h, [&](EngineBase& e) { e.md_random(kind, n, seed, step, stream, out); });
-}
-int admp_md_bonded_box(admp_handle* h, const void* positions, const double* box, int n_bonds, const int32_t* bond_idx,
-                       const void* bond_par, int n_angles, const int32_t* angle_idx, const void* angle_par, double* E_dev,
-                       double* S_dev) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_bonded_box(positions, box, n_bonds, bond_idx, bond_par, n_angles, angle_idx, angle_par, E_dev, S_dev);
-  });
-}
-int admp_md_virial(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad,
-                   const void* inv_mass, uint64_t seed, uint64_t step, double* out_dev) {
-  return guarded(h, [&](EngineBase& e) { e.md_virial(n_atoms, positions, velocities, grad, inv_mass, seed, step, out_dev); });
-}
-int admp_md_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, double mu) {
-  return guarded(h, [&](EngineBase& e) { e.md_scale(n_atoms, positions, velocities, mu); });
-}
-int admp_md_mts_plan(admp_handle* h, int n_atoms, int n_bonds, const int32_t* bond_idx, const double* bond_par, int n_angles,
-                     const int32_t* angle_idx, const double* angle_par, int tile_atoms) {
-  return guarded(h, [&](EngineBase& e) { e.md_mts_plan(n_atoms, n_bonds, bond_idx, bond_par, n_angles, angle_idx, angle_par, tile_atoms); });
-}
-int admp_md_mts_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad_slow, const void* inv_mass,
-                     const double* box, double half_dt_acc_outer, double dt_outer, int n_inner, double c1, double c2sq_kT_acc,
-                     uint64_t seed, uint64_t outer_step, double* E_dev, void* grad_fast_out) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_mts_step(n_atoms, positions, velocities, grad_slow, inv_mass, box, half_dt_acc_outer, dt_outer, n_inner, c1, c2sq_kT_acc,
-                  seed, outer_step, E_dev, grad_fast_out);
-  });
-}
-int admp_md_mts_info(admp_handle* h, int64_t* out8) {
-  return guarded(h, [&](EngineBase& e) { e.md_mts_info(out8); });
-}
-int admp_md_con_plan(admp_handle* h, int n_atoms, int n_constraints, const int32_t* pairs, const double* lengths, int tile_atoms) {
-  return guarded(h, [&](EngineBase& e) { e.md_con_plan(n_atoms, n_constraints, pairs, lengths, tile_atoms); });
-}
-int admp_md_con_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
-                     const double* box, double half_dt_acc, double dt, double c1, double c2sq_kT_acc, uint64_t seed, uint64_t step,
-                     double tolerance, int max_sweeps, int32_t* counters_dev) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_con_step(n_atoms, positions, velocities, grad, inv_mass, box, half_dt_acc, dt, c1, c2sq_kT_acc, seed, step, tolerance,
-                  max_sweeps, counters_dev);
-  });
-}
-int admp_md_con_kick(admp_handle* h, int n_atoms, const void* positions, void* velocities, const void* grad, const void* inv_mass,
-                     const double* box, double half_dt_acc, double dt, double tolerance, int max_sweeps, double* ekin_dev,
-                     int32_t* counters_dev) {
-  return guarded(h, [&](EngineBase& e) {
-    e.md_con_kick(n_atoms, positions, velocities, grad, inv_mass, box, half_dt_acc, dt, tolerance, max_sweeps, ekin_dev, counters_dev);
-  });
-}
-int admp_md_con_project(admp_handle* h, int n_atoms, void* positions, const void* reference, const void* inv_mass, const double* box,
-                        double tolerance, int max_sweeps, int32_t* counters_dev) {
-  return guarded(h, [&](EngineBase& e) { e.md_con_project(n_atoms, positions, reference, inv_mass, box, tolerance, max_sweeps, counters_dev); });
-}
-int admp_md_con_info(admp_handle* h, int64_t* out8) {
-  return guarded(h, [&](EngineBase& e) { e.md_con_info(out8); });
-}
-int admp_md_mol_plan(admp_handle* h, int n_atoms, const int32_t* group_of, int tile_atoms) {
-  return guarded(h, [&](EngineBase& e) { e.md_mol_plan(n_atoms, group_of, tile_atoms); });
-}
-int admp_md_mol_sums(admp_handle* h, int n_atoms, const void* positions, const void* velocities, const void* grad, const void* inv_mass,
-                     const double* box, uint64_t seed, uint64_t step, double* out21_dev) {
-  return guarded(h, [&](EngineBase& e) { e.md_mol_sums(n_atoms, positions, velocities, grad, inv_mass, box, seed, step, out21_dev); });
-}
-int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* inv_mass, const double* box,
-                      double mu_minus_1, double inv_mu_minus_1) {
-  return guarded(h, [&](EngineBase& e) { e.md_mol_scale(n_atoms, positions, velocities, inv_mass, box, mu_minus_1, inv_mu_minus_1); });
-}
-int admp_md_mol_info(admp_handle* h, int64_t* out8) {
-  return guarded(h, [&](EngineBase& e) { e.md_mol_info(out8); });
-}
-int admp_md_fire_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
-                      const double* params9, double ftol, uint64_t call, double* state16_dev) {
-  return guarded(h, [&](EngineBase& e) { e.md_fire_step(n_atoms, positions, velocities, grad, inv_mass, params9, ftol, call, state16_dev); });
 }
 
 int admp_neighbor_count(admp_handle* h, int n_atoms, const void* positions, const double* box, double rc, int64_t* n_pairs) {
