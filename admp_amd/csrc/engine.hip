@@ -14,6 +14,7 @@
 #include <rocfft/rocfft.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include "../../include/admp_hip.h"
 #include "dev_buf.h"
 #include "dft_math.h"
+#include "disp_plan.h"
 #include "handle.h"
 #include "launch.h"
 #include "rccl_comm.h"
@@ -726,6 +728,38 @@ struct Engine : EngineBase {
   int nxown() const { return snranks > 1 ? (X1 - X0) : K[0]; }
   int nyown() const { return snranks > 1 ? (Y1 - Y0) : K[1]; }
 
+  // batched 2-D r2c / c2r plans over `batch` y-z planes stored back to back: real rows of K2 words, spectrum rows padded to
+  // fx_khp complex numbers (ensure_mesh: whole 128-byte lines on the fused-x path and on a slab rank, K2/2+1 otherwise)
+  void make_yz_plans(size_t batch, rocfft_plan* fwd, rocfft_plan* bwd) {
+    const rocfft_precision pr = sizeof(T) == 4 ? rocfft_precision_single : rocfft_precision_double;
+    const size_t len2[2] = {(size_t)K[2], (size_t)K[1]};
+    const size_t rs[2] = {1, (size_t)K[2]}, cs[2] = {1, (size_t)fx_khp};
+    const size_t rdist = (size_t)K[1] * K[2], cdist = (size_t)K[1] * fx_khp;
+    rocfft_plan_description df = nullptr, db = nullptr;
+    FFT_TRY(rocfft_plan_description_create(&df));
+    FFT_TRY(rocfft_plan_description_set_data_layout(df, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
+                                                    nullptr, 2, rs, rdist, 2, cs, cdist));
+    FFT_TRY(rocfft_plan_description_create(&db));
+    FFT_TRY(rocfft_plan_description_set_data_layout(db, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
+                                                    nullptr, 2, cs, cdist, 2, rs, rdist));
+    FFT_TRY(rocfft_plan_create(fwd, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 2, len2, batch, df));
+    FFT_TRY(rocfft_plan_create(bwd, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 2, len2, batch, db));
+    rocfft_plan_description_destroy(df);
+    rocfft_plan_description_destroy(db);
+  }
+  // twiddles of the fused x pass (fftx_kernels.hip): cos, sin of 2 pi m / K0 for the first half turn
+  void upload_fx_twiddles() {
+    std::vector<T> tw((size_t)K[0]);
+    for (int m = 0; m < K[0] / 2; ++m) {
+      const double th = 2.0 * M_PI * (double)m / (double)K[0];
+      tw[2 * m] = (T)std::cos(th);
+      tw[2 * m + 1] = (T)std::sin(th);
+    }
+    fx_tw.need(tw.size() * sizeof(T));
+    HIP_TRY(hipMemcpy(fx_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
+    use_fx = true;
+  }
+
   void ensure_mesh() {
     update_slab();
     const size_t K2h = (size_t)(K[2] / 2 + 1);
@@ -756,51 +790,15 @@ struct Engine : EngineBase {
       FFT_TRY(rocfft_plan_create(&plan_f, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 3, len, 1, nullptr));
       FFT_TRY(rocfft_plan_create(&plan_b, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 3, len, 1, nullptr));
       if (want_fx) {
-        const size_t len2[2] = {(size_t)K[2], (size_t)K[1]};
-        const size_t rs[2] = {1, (size_t)K[2]}, cs[2] = {1, (size_t)khp};
-        const size_t rdist = (size_t)K[1] * K[2], cdist = (size_t)K[1] * khp;
-        rocfft_plan_description df = nullptr, db = nullptr;
-        FFT_TRY(rocfft_plan_description_create(&df));
-        FFT_TRY(rocfft_plan_description_set_data_layout(df, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                        nullptr, 2, rs, rdist, 2, cs, cdist));
-        FFT_TRY(rocfft_plan_description_create(&db));
-        FFT_TRY(rocfft_plan_description_set_data_layout(db, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                        nullptr, 2, cs, cdist, 2, rs, rdist));
-        FFT_TRY(rocfft_plan_create(&plan2_f, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 2, len2, (size_t)K[0], df));
-        FFT_TRY(rocfft_plan_create(&plan2_b, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 2, len2, (size_t)K[0], db));
-        rocfft_plan_description_destroy(df);
-        rocfft_plan_description_destroy(db);
+        make_yz_plans((size_t)K[0], &plan2_f, &plan2_b);
         FFT_TRY(rocfft_plan_get_work_buffer_size(plan2_f, &w)); if (w > wmax) wmax = w;
         FFT_TRY(rocfft_plan_get_work_buffer_size(plan2_b, &w)); if (w > wmax) wmax = w;
-        std::vector<T> tw((size_t)K[0]);
-        for (int m = 0; m < K[0] / 2; ++m) {
-          const double th = 2.0 * M_PI * (double)m / (double)K[0];
-          tw[2 * m] = (T)std::cos(th);
-          tw[2 * m + 1] = (T)std::sin(th);
-        }
-        fx_tw.need(tw.size() * sizeof(T));
-        HIP_TRY(hipMemcpy(fx_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
-        use_fx = true;
+        upload_fx_twiddles();
       }
     } else {
       // distributed transform = batched 2-D r2c over the owned planes, all-to-all transpose (done by the caller over
       // RCCL), batched strided 1-D c2c along x
-      const size_t len2[2] = {(size_t)K[2], (size_t)K[1]};
-      {
-        const size_t rs[2] = {1, (size_t)K[2]}, cs[2] = {1, (size_t)khp};
-        const size_t rdist = (size_t)K[1] * K[2], cdist = (size_t)K[1] * khp;
-        rocfft_plan_description df = nullptr, db = nullptr;
-        FFT_TRY(rocfft_plan_description_create(&df));
-        FFT_TRY(rocfft_plan_description_set_data_layout(df, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                        nullptr, 2, rs, rdist, 2, cs, cdist));
-        FFT_TRY(rocfft_plan_description_create(&db));
-        FFT_TRY(rocfft_plan_description_set_data_layout(db, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                        nullptr, 2, cs, cdist, 2, rs, rdist));
-        FFT_TRY(rocfft_plan_create(&plan_f, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 2, len2, (size_t)nxown(), df));
-        FFT_TRY(rocfft_plan_create(&plan_b, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 2, len2, (size_t)nxown(), db));
-        rocfft_plan_description_destroy(df);
-        rocfft_plan_description_destroy(db);
-      }
+      make_yz_plans((size_t)nxown(), &plan_f, &plan_b);
       const size_t len1[1] = {(size_t)K[0]};
       const size_t stride[1] = {(size_t)nyown() * K2h};
       const size_t batch = (size_t)nyown() * K2h;
@@ -817,17 +815,7 @@ struct Engine : EngineBase {
       }
       FFT_TRY(rocfft_plan_get_work_buffer_size(plan_xf, &w)); if (w > wmax) wmax = w;
       FFT_TRY(rocfft_plan_get_work_buffer_size(plan_xb, &w)); if (w > wmax) wmax = w;
-      if (!fx_off && fftx_usable(K[0])) {   // the fused x pass works on the transposed layout [K0][ny][K2/2+1] as well
-        std::vector<T> tw((size_t)K[0]);
-        for (int m = 0; m < K[0] / 2; ++m) {
-          const double th = 2.0 * M_PI * (double)m / (double)K[0];
-          tw[2 * m] = (T)std::cos(th);
-          tw[2 * m + 1] = (T)std::sin(th);
-        }
-        fx_tw.need(tw.size() * sizeof(T));
-        HIP_TRY(hipMemcpy(fx_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
-        use_fx = true;
-      }
+      if (!fx_off && fftx_usable(K[0])) upload_fx_twiddles();   // the fused x pass works on the transposed layout [K0][ny][K2/2+1] as well
     }
     FFT_TRY(rocfft_plan_get_work_buffer_size(plan_f, &w)); if (w > wmax) wmax = w;
     FFT_TRY(rocfft_plan_get_work_buffer_size(plan_b, &w)); if (w > wmax) wmax = w;
@@ -929,6 +917,30 @@ struct Engine : EngineBase {
   bool pair_rider_ok() const {
     return lpol && side_stream_on && rider_ok() && env_flag("ADMP_PAIR_RIDER", true);
   }
+  // The distributed convolution of an x-slab rank around its x pass.  The stencils of the home atoms overhang into kGhost
+  // planes of the next rank (added there before the transform), the 3-D transform is batched 2-D r2c on the owned planes ->
+  // transpose (all-to-all over the ranks: every GPU exchanges a block with each of the others) -> xpass(tbuf, ny, nh): the x
+  // lines forward * G * inverse on the ny y rows this rank owns, nh complex numbers each -> transpose back -> 2-D c2r into
+  // mesh_o, and the gather needs the next rank's first planes of phi as its ghost planes.  Every rank makes the same
+  // collective calls in the same order.
+  template <class XPass>
+  void slab_convolve(T* mesh_p, T* spec_p, T* mesh_o, XPass&& xpass) {
+    const size_t plane = (size_t)K[1] * K[2];
+    const int nx = nxown(), ny = nyown(), nh = K[2] / 2 + 1;
+    sl.ghost.need(kGhost * plane * sizeof(T));
+    sl.pack.need((size_t)nx * K[1] * nh * 2 * sizeof(T));
+    sl.tbuf.need((size_t)K[0] * ny * nh * 2 * sizeof(T));
+    { TIMED("comm_ghost"); c_shift(mesh_p + (size_t)nx * plane, sl.ghost.p, (int64_t)(kGhost * plane), real_dtype(), 1, ADMP_TAG_GHOST); }
+    { TIMED("mesh_add"); launch_mesh_add<T>(stream, (long)(kGhost * plane), mesh_p, sl.ghost.as<T>()); }
+    fft_forward(mesh_p, spec_p);
+    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 0, spec_p, sl.pack.as<T>()); }
+    { TIMED("comm_transpose"); c_all_to_all_v(sl.pack.p, sl.tr_send, sl.tbuf.p, sl.tr_recv, real_dtype(), ADMP_TAG_TRANSPOSE); }
+    xpass(sl.tbuf.as<T>(), ny, nh);
+    { TIMED("comm_transpose"); c_all_to_all_v(sl.tbuf.p, sl.tr_recv, sl.pack.p, sl.tr_send, real_dtype(), ADMP_TAG_TRANSPOSE); }
+    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 1, spec_p, sl.pack.as<T>()); }
+    fft_inverse(spec_p, mesh_o);
+    { TIMED("comm_ghost"); c_shift(mesh_o, mesh_o + (size_t)nx * plane, (int64_t)(kGhost * plane), real_dtype(), 0, ADMP_TAG_GHOST); }
+  }
   bool convolve(T* mesh_p, T* spec_p, const T* gtab, int slot, T* accum = nullptr, T* out = nullptr,
                 const PlaneSpread<T>* sp = nullptr, const PairFieldArgs<T>* rider = nullptr, const PairFullArgs<T>* prider = nullptr) {
     double* Ed = Ed_cur();
@@ -938,32 +950,16 @@ struct Engine : EngineBase {
     ARG_CHECK(!(prider && prider->on) || (use_dft && !use_pfa && snranks == 1 && !(rider && rider->kind == 1)),
               "internal: pair rider on a transform path without it");
     if (snranks > 1) {
-      // x-slab ranks: the stencils of the home atoms overhang into kGhost planes of the next rank (added there before the
-      // transform), the 3-D transform is batched 2-D r2c on the owned planes -> transpose (all-to-all over the ranks: every
-      // GPU exchanges a block with each of the others) -> x lines forward * G * inverse on the y rows this rank owns ->
-      // transpose back -> 2-D c2r, and the gather needs the next rank's first planes of phi as its ghost planes
-      const size_t plane = (size_t)K[1] * K[2];
-      const int nx = nxown(), ny = nyown(), nh = K[2] / 2 + 1;
-      sl.ghost.need(kGhost * plane * sizeof(T));
-      sl.pack.need((size_t)nx * K[1] * nh * 2 * sizeof(T));
-      sl.tbuf.need((size_t)K[0] * ny * nh * 2 * sizeof(T));
-      { TIMED("comm_ghost"); c_shift(mesh_p + (size_t)nx * plane, sl.ghost.p, (int64_t)(kGhost * plane), real_dtype(), 1, ADMP_TAG_GHOST); }
-      { TIMED("mesh_add"); launch_mesh_add<T>(stream, (long)(kGhost * plane), mesh_p, sl.ghost.as<T>()); }
-      fft_forward(mesh_p, spec_p);
-      { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 0, spec_p, sl.pack.as<T>()); }
-      { TIMED("comm_transpose"); c_all_to_all_v(sl.pack.p, sl.tr_send, sl.tbuf.p, sl.tr_recv, real_dtype(), ADMP_TAG_TRANSPOSE); }
-      if (use_fx) {
-        TIMED("fftx_kspace");
-        launch_fftx_conv<T>(stream, K, fx_tw.as<T>(), sl.tbuf.as<T>(), gtab, Ed, slot, nh, ny);
-      } else {
-        fft_x(sl.tbuf.as<T>(), 0);
-        { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, sl.tbuf.as<T>(), Ed, slot); }
-        fft_x(sl.tbuf.as<T>(), 1);
-      }
-      { TIMED("comm_transpose"); c_all_to_all_v(sl.tbuf.p, sl.tr_recv, sl.pack.p, sl.tr_send, real_dtype(), ADMP_TAG_TRANSPOSE); }
-      { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 1, spec_p, sl.pack.as<T>()); }
-      fft_inverse(spec_p, mesh_o);
-      { TIMED("comm_ghost"); c_shift(mesh_o, mesh_o + (size_t)nx * plane, (int64_t)(kGhost * plane), real_dtype(), 0, ADMP_TAG_GHOST); }
+      slab_convolve(mesh_p, spec_p, mesh_o, [&](T* tbuf, int ny, int nh) {
+        if (use_fx) {
+          TIMED("fftx_kspace");
+          launch_fftx_conv<T>(stream, K, fx_tw.as<T>(), tbuf, gtab, Ed, slot, nh, ny);
+        } else {
+          fft_x(tbuf, 0);
+          { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, tbuf, Ed, slot); }
+          fft_x(tbuf, 1);
+        }
+      });
       (void)accum;
       return false;
     }
@@ -1026,23 +1022,7 @@ struct Engine : EngineBase {
   void ensure_batched_plans(int nb) {
     ARG_CHECK(nb >= 2 && nb <= 3 && use_fx && snranks == 1, "internal: batched y-z plans");
     if (plan2n_f[nb]) return;
-    const rocfft_precision pr = sizeof(T) == 4 ? rocfft_precision_single : rocfft_precision_double;
-    const size_t len2[2] = {(size_t)K[2], (size_t)K[1]};
-    const size_t rs[2] = {1, (size_t)K[2]}, cs[2] = {1, (size_t)fx_khp};
-    const size_t rdist = (size_t)K[1] * K[2], cdist = (size_t)K[1] * fx_khp;
-    rocfft_plan_description df = nullptr, db = nullptr;
-    FFT_TRY(rocfft_plan_description_create(&df));
-    FFT_TRY(rocfft_plan_description_set_data_layout(df, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                    nullptr, 2, rs, rdist, 2, cs, cdist));
-    FFT_TRY(rocfft_plan_description_create(&db));
-    FFT_TRY(rocfft_plan_description_set_data_layout(db, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                    nullptr, 2, cs, cdist, 2, rs, rdist));
-    FFT_TRY(rocfft_plan_create(&plan2n_f[nb], rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 2, len2,
-                               (size_t)nb * K[0], df));
-    FFT_TRY(rocfft_plan_create(&plan2n_b[nb], rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 2, len2,
-                               (size_t)nb * K[0], db));
-    rocfft_plan_description_destroy(df);
-    rocfft_plan_description_destroy(db);
+    make_yz_plans((size_t)nb * K[0], &plan2n_f[nb], &plan2n_b[nb]);
     size_t w = 0, wmax = 0;
     FFT_TRY(rocfft_plan_get_work_buffer_size(plan2n_f[nb], &w)); if (w > wmax) wmax = w;
     FFT_TRY(rocfft_plan_get_work_buffer_size(plan2n_b[nb], &w)); if (w > wmax) wmax = w;
@@ -1060,6 +1040,29 @@ struct Engine : EngineBase {
       launch_fftx_conv_batch<T>(stream, K, fx_tw.as<T>(), spec_p, tabs, nb, (long)nspec, Ed_cur(), slot, fx_khp); }
     run_plan("rocfft_c2r_yz", plan2n_b[nb], spec_p, mesh_p);
     (void)nreal;
+  }
+  // The same on a direct-DFT mesh (plain or two-level lines): five launches for the batch instead of five per mesh.  mix
+  // (plain lines only): the nb meshes are type meshes, the x pass forms the powers from them at every k (k_dft_x_mix).
+  void convolve_dft_batch(T* mesh_p, T* spec_p, const DftTabs<T>& tabs, int nb, size_t nreal, size_t nspec, int slot,
+                          const MixTab* mix = nullptr) {
+    double* Ed = Ed_cur();
+    if (use_pfa) {
+      const T* tw = pfa_tw.as<T>();
+      { TIMED("dft_z_r2c"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 0, nb, (long)nreal, (long)nspec); }
+      { TIMED("dft_y_fwd"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 0, nb, (long)nspec); }
+      { TIMED("dft_x_kspace"); launch_pfa_x_conv<T>(stream, pfa, tw, spec_p, tabs, Ed, slot, nb, (long)nspec); }
+      { TIMED("dft_y_inv"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 1, nb, (long)nspec); }
+      { TIMED("dft_z_c2r"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 1, nb, (long)nreal, (long)nspec); }
+      return;
+    }
+    const T* tw = dft_tw.as<T>();
+    { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 0, nb, (long)nreal, (long)nspec); }
+    { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec_p, 0, nb, (long)nspec); }
+    { TIMED("dft_x_kspace");
+      if (mix) launch_dft_x_mix<T>(stream, K, tw, spec_p, tabs, *mix, (long)nspec, Ed, slot);
+      else launch_dft_x_conv<T>(stream, K, tw, spec_p, tabs, Ed, slot, nb, (long)nspec); }
+    { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec_p, 1, nb, (long)nspec); }
+    { TIMED("dft_z_c2r"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 1, nb, (long)nreal, (long)nspec); }
   }
 
   void run_plan(const char* label, rocfft_plan plan, void* in, void* out) {
@@ -1201,6 +1204,13 @@ struct Engine : EngineBase {
     b.sorted = sorted.as<int>();
     b.scan_tmp = bin_scan.p;
     b.scan_bytes = bin_scan.bytes;
+  }
+
+  // launch_spread on the site-row bins of this handle; a failed launch is an error of the call
+  void spread_sites(int n, const Site<T>* rows, int lp, const RecipGeom<T>& g, T* mesh_p, const int4* bases = nullptr, int nb = 1,
+                    int reuse_bins = 0) {
+    const int rc = launch_spread<T>(stream, n, rows, lp, g, bins, mesh_p, nullptr, bases, nb, reuse_bins);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
   }
 
   // ---- one evaluation, step by step --------------------------------------------------------------------------
@@ -2110,12 +2120,7 @@ struct Engine : EngineBase {
   // never holds the bare spectrum)
   void recip_pass_virial(int slot, int which, double vol, double* acc, int reuse_bins = 0, int lpol_sites = -1) {
     need_eval_or_disp();
-    {
-      TIMED("spread");
-      int rc = launch_spread<T>(stream, vs_n, vs_sites, lpol_sites < 0 ? lpol : lpol_sites, vs_g, bins, mesh.as<T>(), nullptr,
-                                nullptr, 1, reuse_bins);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
-    }
+    { TIMED("spread"); spread_sites(vs_n, vs_sites, lpol_sites < 0 ? lpol : lpol_sites, vs_g, mesh.as<T>(), nullptr, 1, reuse_bins); }
     fft_forward(mesh.as<T>(), spec.as<T>());
     launch_kspace_virial<T>(stream, K, binv_d.as<double>(), std::fabs(vol), kappa, which, ref_korder, spec.as<T>(), acc + V_TK);
     const T* gt = gtab_cur;
@@ -2140,25 +2145,12 @@ struct Engine : EngineBase {
   // them -- every rank returns the full dE/dbox.
   void convolve_slab_virial(T* mesh_p, T* spec_p, const T* gtab, int slot, int which, double vol, double* acc) {
     double* Ed = Ed_cur();
-    const size_t plane = (size_t)K[1] * K[2];
-    const int nx = nxown(), ny = nyown(), nh = K[2] / 2 + 1;
-    sl.ghost.need(kGhost * plane * sizeof(T));
-    sl.pack.need((size_t)nx * K[1] * nh * 2 * sizeof(T));
-    sl.tbuf.need((size_t)K[0] * ny * nh * 2 * sizeof(T));
-    { TIMED("comm_ghost"); c_shift(mesh_p + (size_t)nx * plane, sl.ghost.p, (int64_t)(kGhost * plane), real_dtype(), 1, ADMP_TAG_GHOST); }
-    { TIMED("mesh_add"); launch_mesh_add<T>(stream, (long)(kGhost * plane), mesh_p, sl.ghost.as<T>()); }
-    fft_forward(mesh_p, spec_p);
-    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 0, spec_p, sl.pack.as<T>()); }
-    { TIMED("comm_transpose"); c_all_to_all_v(sl.pack.p, sl.tr_send, sl.tbuf.p, sl.tr_recv, real_dtype(), ADMP_TAG_TRANSPOSE); }
-    fft_x(sl.tbuf.as<T>(), 0);
-    launch_kspace_virial<T>(stream, K, binv_d.as<double>(), std::fabs(vol), kappa, which, ref_korder, sl.tbuf.as<T>(), acc + V_TK,
-                            Y0, ny);
-    { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, sl.tbuf.as<T>(), Ed, slot); }
-    fft_x(sl.tbuf.as<T>(), 1);
-    { TIMED("comm_transpose"); c_all_to_all_v(sl.tbuf.p, sl.tr_recv, sl.pack.p, sl.tr_send, real_dtype(), ADMP_TAG_TRANSPOSE); }
-    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 1, spec_p, sl.pack.as<T>()); }
-    fft_inverse(spec_p, mesh_p);
-    { TIMED("comm_ghost"); c_shift(mesh_p, mesh_p + (size_t)nx * plane, (int64_t)(kGhost * plane), real_dtype(), 0, ADMP_TAG_GHOST); }
+    slab_convolve(mesh_p, spec_p, mesh_p, [&](T* tbuf, int ny, int) {
+      fft_x(tbuf, 0);
+      launch_kspace_virial<T>(stream, K, binv_d.as<double>(), std::fabs(vol), kappa, which, ref_korder, tbuf, acc + V_TK, Y0, ny);
+      { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, tbuf, Ed, slot); }
+      fft_x(tbuf, 1);
+    });
   }
   void pme_box_grad(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
                     const double* mS, const double* pS, const void* U_, double* E, double* dbox) override {
@@ -2201,49 +2193,37 @@ struct Engine : EngineBase {
   // dispersion PME box gradient on a slab rank (round 4): the pair sums over its home rows, the channels spread / gathered on
   // its home atoms through the distributed convolution with the k-tensor sums between the x transforms, the self term over
   // its home atoms; the 24 device sums are added over the ranks
-  void disp_box_grad_slab(const T* pos, const double* box, const T* cl, int pmax, int ns, const double* mS, double* E,
+  void disp_box_grad_slab(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
                           double* dbox) {
     const int na = top.na;
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    ensure_mesh();
-    RecipGeom<T> g = make_geom(inv);
-    ScaleTab<T> tab = make_tab(ns, mS, nullptr);
+    RecipGeom<T> g;
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, clist_, 3, nullptr, 1, 2 * E_WORDS, &g);
+    const T* pos = sc.pos; const T* cl = sc.par;
+    double* Ed = sc.Ed;
     ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
-    grad.need(3 * (size_t)na * sizeof(T));
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, 2 * E_WORDS * sizeof(double), stream));
     double* acc = vir_begin();
     cls_sites_na = slab_sites_na = -1;
     const ScalarRows sr = scalar_rows(pos, g, K[0], X0, X1, true);
-    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), bx, tab, (T)kappa, pmax, grad.as<T>(), Ed, sr.rows, sr.n, cutoff);
-    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, acc + V_XW, cutoff, sr.rows, sr.n);
-    const double kp[3] = {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
+    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, sr.rows, sr.n, cutoff);
+    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff, sr.rows, sr.n);
     const int nch = (pmax - 4) / 2;
     const size_t nreal = nreal_local();
     mesh.need(nch * nreal * sizeof(T));
     sites.need(sizeof(Site<T>) * (size_t)na);
     ensure_bins(std::max(sr.n, 1));
-    {
-      int rc = launch_bin_bricks<T>(stream, sr.n, (const Site<T>*)nullptr, g, bins, sr.home, bases_d.as<int4>());
-      if (rc == 0) rc = launch_spread_scalar<T>(stream, nch, pos, cl, 3, g, bins, mesh.as<T>(), (long)nreal);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("dispersion spread: ") + hipGetErrorString((hipError_t)rc)};
-      bins.counters_zero = true;
-    }
+    spread_bricks(sr, g, nch, pos, cl, nullptr);
     double* scratchE = Ed + E_WORDS;              // (the all-atom self sums of launch_scalar_sites are not this rank's: discarded)
     for (int c = 0; c < nch; ++c) {
-      ensure_gtab(box, inv, vol, 6 + 2 * c);
-      upload_binv(inv);
-      convolve_slab_virial(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP, 6 + 2 * c, vol, acc);
+      ensure_gtab(box, sc.inv, sc.vol, 6 + 2 * c);
+      upload_binv(sc.inv);
+      convolve_slab_virial(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP, 6 + 2 * c, sc.vol, acc);
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, 0.0, sites.as<Site<T>>(), scratchE);
       launch_gather_virial<T>(stream, sr.n, sites.as<Site<T>>(), 0, g, mesh.as<T>() + c * nreal, acc + V_XW, acc + V_Y, sr.home);
     }
-    launch_scalar_self<T>(stream, nch, sr.n, cl, 3, sr.home, kp, Ed);
+    launch_scalar_self<T>(stream, nch, sr.n, cl, 3, sr.home, disp_kp().data(), Ed);
     read_scalar_energies(Ed, E, 3);
     { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
-    vir_assemble(inv, E[1], dbox);
+    vir_assemble(sc.inv, E[1], dbox);
   }
 
   void disp_box_grad(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
@@ -2252,36 +2232,28 @@ struct Engine : EngineBase {
     ARG_CHECK(pos_ && box && clist_ && E && dbox, "null argument");
     ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
     if (snranks > 1) {
-      disp_box_grad_slab(reinterpret_cast<const T*>(pos_), box, reinterpret_cast<const T*>(clist_), pmax, ns, mS, E, dbox);
+      disp_box_grad_slab(pos_, box, clist_, pmax, ns, mS, E, dbox);
       return;
     }
     const int na = top.na;
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    RecipGeom<T> g = make_geom(inv);
-    ScaleTab<T> tab = make_tab(ns, mS, nullptr);
-    ensure_mesh();
-    const T* pos = reinterpret_cast<const T*>(pos_);
-    const T* cl = reinterpret_cast<const T*>(clist_);
-    grad.need(3 * (size_t)na * sizeof(T));
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, E_SLOTS * sizeof(double), stream));
+    RecipGeom<T> g;
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, clist_, 3, nullptr, 1, E_SLOTS, &g);
+    const T* pos = sc.pos; const T* cl = sc.par;
+    double* Ed = sc.Ed;
     double* acc = vir_begin();
-    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), bx, tab, (T)kappa, pmax, grad.as<T>(), Ed, nullptr, 0, cutoff);
-    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, acc + V_XW, cutoff);
+    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, nullptr, 0, cutoff);
+    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff);
     cls_sites_na = slab_sites_na = -1;   // other rows than an electrostatics evaluation's
     sites.need(sizeof(Site<T>) * (size_t)na);
     ensure_bins(na);
-    const double kp[3] = {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
+    const std::array<double, 3> kp = disp_kp();
     const int nch = (pmax - 4) / 2;
     vs_n = na; vs_sites = sites.as<Site<T>>(); vs_g = g;
     for (int c = 0; c < nch; ++c) {
-      ensure_gtab(box, inv, vol, 6 + 2 * c);
-      upload_binv(inv);
+      ensure_gtab(box, sc.inv, sc.vol, 6 + 2 * c);
+      upload_binv(sc.inv);
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed);
-      recip_pass_virial(E_RECIP, 6 + 2 * c, vol, acc, c > 0, 0);
+      recip_pass_virial(E_RECIP, 6 + 2 * c, sc.vol, acc, c > 0, 0);
       launch_gather_virial<T>(stream, na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), acc + V_XW, acc + V_Y);
     }
     vs_sites = nullptr;
@@ -2289,7 +2261,7 @@ struct Engine : EngineBase {
     HIP_TRY(hipMemcpyAsync(Eh2, Ed, sizeof(Eh2), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     E[0] = Eh2[E_REAL]; E[1] = Eh2[E_RECIP]; E[2] = Eh2[E_SELF];
-    vir_assemble(inv, E[1], dbox);
+    vir_assemble(sc.inv, E[1], dbox);
   }
 
   void tt_box_grad(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, double* E,
@@ -2297,32 +2269,15 @@ struct Engine : EngineBase {
     ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
     ARG_CHECK(pos_ && box && abqc_ && E && dbox, "null argument");
     const int na = top.na;
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    ScaleTab<T> tab = make_tab(ns, mS, nullptr);
-    const T* pos = reinterpret_cast<const T*>(pos_);
-    const T* par = reinterpret_cast<const T*>(abqc_);
-    grad.need(3 * (size_t)na * sizeof(T));
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, E_WORDS * sizeof(double), stream));
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, abqc_, 4, nullptr, 1, E_WORDS);
     double* acc = vir_begin();
     ScalarRows sr{nullptr, na, nullptr};
-    if (snranks > 1) {     // ownership by x-slabs of a virtual mesh, as in tt(); the sums are added over the ranks
-      ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      RecipGeom<T> g;
-      const int Kv = 64 * snranks;
-      g.K[0] = Kv; g.K[1] = g.K[2] = 32;
-      for (int k = 0; k < 9; ++k) { g.hinv[k] = (T)inv[k]; g.Aop[k] = g.Jac[k] = T(0); }
-      g.xoff = 64 * srank; g.nloc0 = 64 + kGhost; g.wrap0 = 1 << 30;
-      sr = scalar_rows(pos, g, Kv, 64 * srank, 64 * (srank + 1), true);
-    }
-    launch_tt_pair<T>(stream, na, nbr, pack_srows(pos, par, 4), bx, tab, grad.as<T>(), Ed, sr.rows, sr.n, cutoff);
-    launch_scalar_pair_virial<T>(stream, 1, na, nbr, pos, par, bx, tab, T(0), 0, acc + V_XW, cutoff, sr.rows, sr.n);
-    read_scalar_energies(Ed, E, 1);
+    if (snranks > 1) sr = virtual_slab_rows(sc.pos, sc.inv);     // as in tt(); the sums are added over the ranks
+    launch_tt_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff);
+    launch_scalar_pair_virial<T>(stream, 1, na, nbr, sc.pos, sc.par, sc.bx, sc.tab, T(0), 0, acc + V_XW, cutoff, sr.rows, sr.n);
+    read_scalar_energies(sc.Ed, E, 1);
     if (snranks > 1) { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
-    vir_assemble(inv, 0.0, dbox);      // only the xw sums are non-zero here
+    vir_assemble(sc.inv, 0.0, dbox);      // only the xw sums are non-zero here
   }
 
   // ---- neighbour search (cell list) ------------------------------------------------------------------
@@ -2462,6 +2417,87 @@ struct Engine : EngineBase {
     decompose(K0v, X0v, X1v, order);
     return {sl.rows, sl.n_home, sl.home};
   }
+  // ... of a pair potential on a slab rank: it has no mesh, so ownership goes by x-slabs of a virtual one of 64 planes per rank
+  ScalarRows virtual_slab_rows(const T* pos, const double* inv) {
+    ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
+    RecipGeom<T> g;
+    const int Kv = 64 * snranks;
+    g.K[0] = Kv; g.K[1] = g.K[2] = 32;
+    for (int k = 0; k < 9; ++k) { g.hinv[k] = (T)inv[k]; g.Aop[k] = g.Jac[k] = T(0); }
+    g.xoff = 64 * srank; g.nloc0 = 64 + kGhost; g.wrap0 = 1 << 30;
+    return scalar_rows(pos, g, Kv, 64 * srank, 64 * (srank + 1), true);
+  }
+
+  // ---- the opening and the closing of a scalar call (dispersion PME, Tang-Toennies, traced pair programs) ----------------
+  // Filled on the stack by scalar_begin: the cell, the scale table, the inputs on the device, where the gradient goes (the
+  // caller's device array, or `grad` for a host caller, a caller without one and the box gradients) and the energy words.
+  struct ScalarCall {
+    const double* h; Box<T> bx; double inv[9], vol;      // the caller's cell, its device form, inverse and volume
+    ScaleTab<T> tab;
+    const T* pos; const T* par;
+    T* dpos;
+    double* Ed;
+  };
+  // par_: npar words per atom; zero_words: how many of the energy words the call starts from zero -- E_SLOTS: the energies
+  // (and the word the type check counts into, E_FMAX), enough for a call that reads them back itself; E_WORDS: the whole
+  // half, as read_scalar_energies copies it (with the words packed for the sum over the ranks); 2 * E_WORDS: the second half
+  // too, where the slab box gradient leaves the self sums it discards.  g: the call works on the mesh -- plans and buffers
+  // first, then its geometry (with its refusal of meshes shorter than the splines).
+  ScalarCall scalar_begin(const double* box, int ns, const double* mS, const void* pos_, const void* par_, size_t npar,
+                          void* dpos_, int on_device, size_t zero_words, RecipGeom<T>* g = nullptr) {
+    const size_t na = (size_t)top.na;
+    ScalarCall sc;
+    sc.h = box;
+    sc.bx = make_box(box, sc.inv, &sc.vol);
+    if (g) { ensure_mesh(); *g = make_geom(sc.inv); }
+    sc.tab = make_tab(ns, mS, nullptr);
+    sc.pos = stage_in(s_pos, pos_, 3 * na, on_device);
+    sc.par = stage_in(s_par, par_, npar * na, on_device);
+    grad.need(3 * na * sizeof(T));
+    sc.dpos = (dpos_ && on_device) ? reinterpret_cast<T*>(dpos_) : grad.as<T>();
+    energies_d.need(2 * E_WORDS * sizeof(double));
+    ehalf = 0; other_clean = false;
+    sc.Ed = energies_d.as<double>();
+    HIP_TRY(hipMemsetAsync(sc.Ed, 0, zero_words * sizeof(double), stream));
+    return sc;
+  }
+  // the gradient of a host caller goes back; sync = false: the caller has more to copy and synchronises itself
+  void scalar_return_grad(const ScalarCall& sc, void* dpos_, int on_device, bool sync = true) {
+    if (!dpos_ || on_device) return;
+    HIP_TRY(hipMemcpyAsync(dpos_, sc.dpos, 3 * (size_t)top.na * sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (sync) HIP_TRY(hipStreamSynchronize(stream));
+  }
+
+  // ---- tables of a dispersion call ------------------------------------------------------------------------------------------
+  // self / gamma-point factors of the powers 6, 8, 10 (admp/disp_pme.py:254-279)
+  std::array<double, 3> disp_kp() const {
+    return {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
+  }
+  // coefficients of the type table by (power, type), for the x passes that mix type meshes into powers
+  MixTab disp_mix(int nch) const {
+    MixTab mix;
+    mix.nch = nch; mix.nt = disp_nt;
+    for (int c = 0; c < 3; ++c)
+      for (int t = 0; t < 4; ++t) mix.c[c][t] = (c < nch && t < disp_nt) ? disp_ctab[t][c] : 0.0;
+    return mix;
+  }
+  // the G tables of the first nch powers
+  DftTabs<T> disp_tabs(const double* box, const double* inv, double vol, int nch) {
+    DftTabs<T> tabs;
+    for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = gtab_cur; }
+    return tabs;
+  }
+  // ONE binning and ONE spread of nmesh meshes straight from the caller's arrays (disp_kernels.hip): one mesh per power from
+  // the coefficient rows cl, or -- types given -- one per type
+  void spread_bricks(const ScalarRows& sr, const RecipGeom<T>& g, int nmesh, const T* pos, const T* cl, const int* types) {
+    int rc = launch_bin_bricks<T>(stream, sr.n, (const Site<T>*)nullptr, g, bins, sr.home, bases_d.as<int4>());
+    if (rc == 0)
+      rc = types ? launch_spread_typed<T>(stream, nmesh, pos, types, g, bins, mesh.as<T>(), (long)nreal_local())
+                 : launch_spread_scalar<T>(stream, nmesh, pos, cl, 3, g, bins, mesh.as<T>(), (long)nreal_local());
+    if (rc != 0)
+      throw Err{ADMP_E_HIP, std::string(types ? "dispersion spread (typed): " : "dispersion spread: ") + hipGetErrorString((hipError_t)rc)};
+    bins.counters_zero = true;
+  }
 
   // admp_disp_set_types: the atoms' coefficient rows take nt <= 3 distinct values; types (device int32[Na], the caller's) picks
   // the row ctab[type][3] of every atom.  Used by the single-rank fused-x path in single precision (typed meshes: one spread
@@ -2502,7 +2538,140 @@ struct Engine : EngineBase {
   // ADMP_DISP_TYPES=0 / ADMP_DISP_BATCH=0: no typed meshes / the per-channel loop (A/B, tests)
   static bool disp_types_on() { static const bool on = env_flag("ADMP_DISP_TYPES", true); return on; }
   static bool disp_batch_on() { static const bool on = env_flag("ADMP_DISP_BATCH", true); return on; }
-  // dispersion PME (admp/disp_pme.py:80-123): real-space pairs + one scalar reciprocal pass per power
+  // ---- dispersion PME (admp/disp_pme.py:80-123): real-space pairs + the reciprocal space of every power, by one of the paths
+  // of disp_plan.h.  A path function holds the launches between the pair kernel and the energy read of its path.
+  // Brick regime, typed meshes (disp_kernels.hip): nt type meshes through the batched y-z plans, combined per k in the x pass,
+  // ONE gather per atom
+  void disp_bricks_typed(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
+    const int nt = disp_nt;
+    const size_t nreal = nreal_local(), nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
+    ensure_bins(std::max(sr.n, 1));
+    const MixTab mix = disp_mix(nch);
+    launch_types_check<T>(stream, top.na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
+    mesh.need((size_t)std::max(nt, nch) * nreal * sizeof(T));
+    spec.need((size_t)nt * nspec * sizeof(T));
+    { TIMED("spread"); spread_bricks(sr, g, nt, sc.pos, nullptr, disp_types); }
+    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+    if (nt >= 2) ensure_batched_plans(nt);
+    run_plan("rocfft_r2c_yz", nt >= 2 ? plan2n_f[nt] : plan2_f, mesh.p, spec.p);
+    { TIMED("fftx_kspace");
+      launch_fftx_mix<T>(stream, K, fx_tw.as<T>(), spec.as<T>(), tabs, mix, (long)nspec, sc.Ed, E_RECIP, fx_khp); }
+    run_plan("rocfft_c2r_yz", nt >= 2 ? plan2n_b[nt] : plan2_b, spec.p, mesh.p);
+    { TIMED("gather_field");
+      launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par, 3, g, mesh.as<T>(), (long)nreal, sc.dpos, sr.home, 0, disp_types); }
+  }
+  // Brick regime (at scale, and every slab rank): ONE binning and ONE spread of the nch meshes straight from the caller's
+  // arrays, no site rows and no scale-add pass.  batched (one rank on a fused-x mesh, round 4): the meshes go through ONE
+  // batched r2c, ONE x pass (a G table per power) and ONE batched c2r; then the powers of every mesh point are laid side by
+  // side (one streaming pass) and ONE gather fetches them with a single load per stencil point -- the gather is bound by its
+  // load instructions (36 per lane and mesh), not by the bytes they return.  Otherwise every power is gathered right after
+  // its transform: that gather is bound by the cache-line rate of its 36 mesh loads per lane, whatever it sums (0.175 ms per
+  // power at 1M atoms in every form tried: one pass over the three meshes 0.52-0.61 ms; one pass per power from its own or
+  // from a shared, cache-resident phi buffer 0.525; round 2's k_gather_field_staged on site rows 0.525).
+  void disp_bricks(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch, bool batched) {
+    const size_t nreal = nreal_local();
+    mesh.need(nch * nreal * sizeof(T));
+    ensure_bins(std::max(sr.n, 1));
+    { TIMED("spread"); spread_bricks(sr, g, nch, sc.pos, sc.par, nullptr); }
+    if (batched) {
+      const size_t nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
+      spec.need(nch * nspec * sizeof(T));
+      mesh2.need(nch * nreal * sizeof(T));
+      const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+      convolve_batch(mesh.as<T>(), spec.as<T>(), tabs, nch, nreal, nspec, E_RECIP);
+      { TIMED("interleave"); launch_interleave<T>(stream, nch, (long)nreal, mesh.as<T>(), (long)nreal, mesh2.as<T>()); }
+      { TIMED("gather_field");
+        launch_gather_scalar<T>(stream, nch, sr.n, sc.pos, sc.par, 3, g, mesh2.as<T>(), (long)nreal, sc.dpos, sr.home, 1); }
+    } else
+    for (int c = 0; c < nch; ++c) {
+      ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
+      convolve(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP);
+      TIMED("gather_field");
+      launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par + c, 3, g, mesh.as<T>() + c * nreal, (long)nreal, sc.dpos, sr.home);
+    }
+    { TIMED("scalar_self"); launch_scalar_self<T>(stream, nch, sr.n, sc.par, 3, sr.home, disp_kp().data(), sc.Ed); }
+  }
+  // The other paths go through the spread / gather kernels of the electrostatics: nb batches of charge-only site rows (which
+  // also accumulate the self term, disp_pme.py:254-279), their fields, the bins; returns the geometry of their gather
+  RecipGeom<T> disp_site_rows(const RecipGeom<T>& g, int nb) {
+    const size_t na = (size_t)top.na;
+    sites.need(sizeof(Site<T>) * na * nb);
+    fld_recip.need(3 * na * sizeof(T) * nb);
+    ensure_bins(top.na);
+    RecipGeom<T> gj = g;                       // scalar sites: dE/dr = c * Jac . F1 (gather_field applies g.Aop)
+    for (int k = 0; k < 9; ++k) gj.Aop[k] = g.Jac[k];
+    return gj;
+  }
+  // Typed meshes on a direct-DFT mesh (small systems; see admp_disp_set_types): the types take the place of the powers in the
+  // batch -- one-hot weights through the same site / spread / gather kernels, the x pass combines (dft_kernels.hip k_dft_x_mix)
+  void disp_dft_typed(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
+    const int na = top.na, nt = disp_nt;
+    const RecipGeom<T> gj = disp_site_rows(g, nt);
+    const MixTab mix = disp_mix(nch);
+    launch_types_check<T>(stream, na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
+    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (K[2] / 2 + 1);
+    mesh.need(nt * nreal * sizeof(T));
+    spec.need(nt * nspec * sizeof(T));
+    onehot_d.need((size_t)na * nt * sizeof(T));
+    bases_d.need(sizeof(int4) * (size_t)na);
+    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+    const double no_self[3] = {0.0, 0.0, 0.0};
+    { TIMED("scalar_sites");
+      if (!disp_onehot_ok || onehot_for != onehot_d.p) {
+        launch_onehot<T>(stream, na, nt, disp_types, onehot_d.as<T>());
+        disp_onehot_ok = true; onehot_for = onehot_d.p;
+      }
+      launch_scalar_sites_batch<T>(stream, na, sc.pos, onehot_d.as<T>(), nt, nt, no_self, sites.as<Site<T>>(), sc.Ed, &g,
+                                   bases_d.as<int4>()); }
+    { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), nt); }
+    convolve_dft_batch(mesh.as<T>(), spec.as<T>(), tabs, nt, nreal, nspec, E_RECIP, &mix);
+    { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nt); }
+    { TIMED("scale_add"); launch_scale_add<T>(stream, na, onehot_d.as<T>(), nt, 0, fld_recip.as<T>(), sc.dpos, nt); }
+  }
+  // direct-DFT meshes are small and dispatch bound: the powers are spread into separate meshes and transformed as ONE batch
+  // (5 launches instead of 5 per power), then one gather over the batch of meshes
+  void disp_dft_batched(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
+    const int na = top.na;
+    const std::array<double, 3> kp = disp_kp();
+    const RecipGeom<T> gj = disp_site_rows(g, nch);
+    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (use_pfa ? pfa.Khp : K[2] / 2 + 1);
+    mesh.need(nch * nreal * sizeof(T));
+    spec.need(nch * nspec * sizeof(T));
+    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+    if (!spread_uses_bricks(na, g)) {        // the scan-spread regime takes the powers as a batch
+      // the stencil records ride along: every (brick, power) workgroup of the scan spread reads them instead of
+      // redoing three grid_ref per atom (3072 atoms x 1029 workgroups at 97^3)
+      bases_d.need(sizeof(int4) * (size_t)na);
+      { TIMED("scalar_sites"); launch_scalar_sites_batch<T>(stream, na, sc.pos, sc.par, 3, nch, kp.data(), sites.as<Site<T>>(), sc.Ed,
+                                                            &g, bases_d.as<int4>()); }
+      TIMED("spread");
+      spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), nch);
+    } else {
+      for (int c = 0; c < nch; ++c) {
+        { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, sc.pos, sc.par, 3, c, kp[c], sites.as<Site<T>>(), sc.Ed); }
+        TIMED("spread");
+        spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>() + c * nreal, nullptr, 1, c > 0);
+      }
+    }
+    convolve_dft_batch(mesh.as<T>(), spec.as<T>(), tabs, nch, nreal, nspec, E_RECIP);
+    // the site rows hold the positions (only the charge slot differs per power): one gather over the batch of meshes
+    { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nch); }
+    { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, 0, fld_recip.as<T>(), sc.dpos, nch); }
+  }
+  // one scalar reciprocal pass per power: the power is packed into site rows, spread, convolved, gathered, scaled
+  void disp_per_power(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
+    const int na = top.na;
+    const std::array<double, 3> kp = disp_kp();
+    const RecipGeom<T> gj = disp_site_rows(g, 1);
+    for (int c = 0; c < nch; ++c) {
+      ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
+      { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, sc.pos, sc.par, 3, c, kp[c], sites.as<Site<T>>(), sc.Ed); }
+      { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0); }
+      convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP);
+      { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr); }
+      { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, c, fld_recip.as<T>(), sc.dpos); }
+    }
+  }
   void disp(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
             void* dpos_, int on_device) override {
     ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
@@ -2511,232 +2680,44 @@ struct Engine : EngineBase {
     ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
     const int na = top.na;
     HIP_TRY(hipSetDevice(device));
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    ensure_mesh();
-    RecipGeom<T> g = make_geom(inv);
-    ScaleTab<T> tab = make_tab(ns, mS, nullptr);
-    const T* pos = stage_in(s_pos, pos_, 3 * (size_t)na, on_device);
-    const T* cl = stage_in(s_par, clist_, 3 * (size_t)na, on_device);
-    T* dpos = nullptr;
-    grad.need(3 * (size_t)na * sizeof(T));
-    if (dpos_ && on_device) dpos = reinterpret_cast<T*>(dpos_);
-    else dpos = grad.as<T>();
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, E_WORDS * sizeof(double), stream));
-    const double kp[3] = {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
+    RecipGeom<T> g;
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, clist_, 3, dpos_, on_device, E_WORDS, &g);
     const int nch = (pmax - 4) / 2;
     cls_sites_na = slab_sites_na = -1;   // other rows than an electrostatics evaluation's
-    // At scale (brick regime) and on every slab rank the channels go through ONE binning, ONE spread and ONE gather straight
-    // from the caller's position / coefficient arrays (disp_kernels.hip); small single-GPU systems keep the batched
-    // scan-spread / direct-DFT path below (dispatch-bound: nine launches for the three powers).
-    const bool fused = !(use_dft || use_pfa) && (snranks > 1 || spread_uses_bricks(na, g));
+    DispPathIn in;
+    in.snranks = snranks; in.use_dft = use_dft; in.use_pfa = use_pfa; in.use_fx = use_fx;
+    in.bricks = spread_uses_bricks(na, g);
+    in.single_precision = sizeof(T) == 4;
+    in.nch = nch; in.disp_nt = disp_nt; in.have_types = disp_types != nullptr;
+    in.types_on = disp_types_on(); in.batch_on = disp_batch_on();
+    const DispPath path = disp_path(in);
+    const bool bricks = path == DispPath::BricksTyped || path == DispPath::BricksBatched || path == DispPath::BricksPerPower;
+    const bool typed = path == DispPath::BricksTyped || path == DispPath::DftTyped;
     if (snranks > 1) ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
-    const ScalarRows sr = scalar_rows(pos, g, K[0], X0, X1, fused);
-    { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), bx, tab, (T)kappa, pmax, dpos, Ed, sr.rows, sr.n, cutoff); }
-    if (fused) {
-      const size_t nreal = nreal_local();
-      mesh.need(nch * nreal * sizeof(T));
-      ensure_bins(std::max(sr.n, 1));
-      // (more types than powers would mean more transforms than the per-power form: pmax 6 with two types keeps its one mesh)
-      const bool typed = disp_types_on() && disp_batch_on() && snranks == 1 && use_fx && sizeof(T) == 4 && disp_nt >= 1 && disp_nt <= nch &&
-                         disp_types;
-      if (typed) {
-        // Typed meshes (disp_kernels.hip): nt type meshes through the transforms, combined per k in the x pass
-        const int nt = disp_nt;
-        MixTab mix;
-        mix.nch = nch; mix.nt = nt;
-        for (int c = 0; c < 3; ++c)
-          for (int t = 0; t < 4; ++t) mix.c[c][t] = (c < nch && t < nt) ? disp_ctab[t][c] : 0.0;
-        launch_types_check<T>(stream, na, cl, 3, disp_types, mix, Ed + E_FMAX);
-        const size_t nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
-        mesh.need((size_t)std::max(nt, nch) * nreal * sizeof(T));
-        spec.need((size_t)nt * nspec * sizeof(T));
-        { TIMED("spread");
-          int rc = launch_bin_bricks<T>(stream, sr.n, (const Site<T>*)nullptr, g, bins, sr.home, bases_d.as<int4>());
-          if (rc == 0) rc = launch_spread_typed<T>(stream, nt, pos, disp_types, g, bins, mesh.as<T>(), (long)nreal);
-          if (rc != 0) throw Err{ADMP_E_HIP, std::string("dispersion spread (typed): ") + hipGetErrorString((hipError_t)rc)};
-          bins.counters_zero = true; }
-        DftTabs<T> tabs;
-        for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = gtab_cur; }
-        if (nt >= 2) ensure_batched_plans(nt);
-        run_plan("rocfft_r2c_yz", nt >= 2 ? plan2n_f[nt] : plan2_f, mesh.p, spec.p);
-        { TIMED("fftx_kspace");
-          launch_fftx_mix<T>(stream, K, fx_tw.as<T>(), spec.as<T>(), tabs, mix, (long)nspec, Ed, E_RECIP, fx_khp); }
-        run_plan("rocfft_c2r_yz", nt >= 2 ? plan2n_b[nt] : plan2_b, spec.p, mesh.p);
-        { TIMED("gather_field");
-          launch_gather_scalar<T>(stream, 1, sr.n, pos, cl, 3, g, mesh.as<T>(), (long)nreal, dpos, sr.home, 0, disp_types); }
-        const double e_self = typed_self_energy(na, nch, kp);
-        read_scalar_energies(Ed, E, 3, true);
-        E[2] = e_self;
-        if (dpos_ && !on_device) {
-          HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-          HIP_TRY(hipStreamSynchronize(stream));
-        }
-        return;
-      }
-      { TIMED("spread");
-        int rc = launch_bin_bricks<T>(stream, sr.n, (const Site<T>*)nullptr, g, bins, sr.home, bases_d.as<int4>());
-        if (rc == 0) rc = launch_spread_scalar<T>(stream, nch, pos, cl, 3, g, bins, mesh.as<T>(), (long)nreal);
-        if (rc != 0) throw Err{ADMP_E_HIP, std::string("dispersion spread: ") + hipGetErrorString((hipError_t)rc)};
-        bins.counters_zero = true; }
-      // every channel is gathered right after its transform.  The gather is bound by the cache-line rate of its 36 mesh loads
-      // per lane, whatever it sums: 0.175 ms per channel at 1M atoms in every form tried (one pass over the three meshes
-      // 0.52-0.61 ms; one pass per channel from its own or from a shared, cache-resident phi buffer 0.525; round 2's
-      // k_gather_field_staged on site rows 0.525) -- what the fused path saves is the site rows and the scale-add pass.
-      // Round 4, one rank on a fused-x mesh: the nch meshes go through ONE batched r2c, ONE x pass (a G table per channel)
-      // and ONE batched c2r; then the channels of every mesh point are laid side by side (one streaming pass) and ONE gather
-      // fetches them with a single load per stencil point -- the gather is bound by its load instructions (36 per lane and
-      // mesh), not by the bytes they return.  ADMP_DISP_BATCH=0: the per-channel loop (A/B, tests).
-      if (disp_batch_on() && snranks == 1 && use_fx && nch >= 2) {
-        const size_t nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
-        spec.need(nch * nspec * sizeof(T));
-        mesh2.need(nch * nreal * sizeof(T));
-        DftTabs<T> tabs;
-        for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = gtab_cur; }
-        convolve_batch(mesh.as<T>(), spec.as<T>(), tabs, nch, nreal, nspec, E_RECIP);
-        { TIMED("interleave"); launch_interleave<T>(stream, nch, (long)nreal, mesh.as<T>(), (long)nreal, mesh2.as<T>()); }
-        { TIMED("gather_field");
-          launch_gather_scalar<T>(stream, nch, sr.n, pos, cl, 3, g, mesh2.as<T>(), (long)nreal, dpos, sr.home, 1); }
-      } else
-      for (int c = 0; c < nch; ++c) {
-        ensure_gtab(box, inv, vol, 6 + 2 * c);
-        convolve(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP);
-        TIMED("gather_field");
-        launch_gather_scalar<T>(stream, 1, sr.n, pos, cl + c, 3, g, mesh.as<T>() + c * nreal, (long)nreal, dpos, sr.home);
-      }
-      { TIMED("scalar_self"); launch_scalar_self<T>(stream, nch, sr.n, cl, 3, sr.home, kp, Ed); }
-      read_scalar_energies(Ed, E, 3);
-      if (dpos_ && !on_device) {
-        HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-      }
-      return;
+    const ScalarRows sr = scalar_rows(sc.pos, g, K[0], X0, X1, bricks);
+    { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
+    switch (path) {
+      case DispPath::BricksTyped: disp_bricks_typed(sc, g, sr, nch); break;
+      case DispPath::BricksBatched: disp_bricks(sc, g, sr, nch, true); break;
+      case DispPath::BricksPerPower: disp_bricks(sc, g, sr, nch, false); break;
+      case DispPath::DftTyped: disp_dft_typed(sc, g, nch); break;
+      case DispPath::DftBatched: disp_dft_batched(sc, g, nch); break;
+      case DispPath::PerPower: disp_per_power(sc, g, nch); break;
     }
-    // one scalar reciprocal pass per power through the same spread / gather kernels as the electrostatics:
-    // the channel is packed into charge-only site rows (which also accumulates the self term, disp_pme.py:254-279)
-    sites.need(sizeof(Site<T>) * (size_t)na);
-    fld_recip.need(3 * (size_t)na * sizeof(T));
-    ensure_bins(na);
-    RecipGeom<T> gj = g;                       // scalar sites: dE/dr = c * Jac . F1 (gather_field applies g.Aop)
-    for (int k = 0; k < 9; ++k) gj.Aop[k] = g.Jac[k];
-    // Typed meshes on a direct-DFT mesh (small systems; see admp_disp_set_types): the types take the place of the powers in the
-    // batch -- one-hot weights through the same site / spread / gather kernels, the x pass combines (dft_kernels.hip k_dft_x_mix)
-    if (disp_types_on() && disp_nt >= 1 && disp_nt < nch && disp_types && use_dft && !use_pfa && snranks == 1 &&
-        !spread_uses_bricks(na, g)) {
-      const int nt = disp_nt;
-      MixTab mix;
-      mix.nch = nch; mix.nt = nt;
-      for (int c = 0; c < 3; ++c)
-        for (int t = 0; t < 4; ++t) mix.c[c][t] = (c < nch && t < nt) ? disp_ctab[t][c] : 0.0;
-      launch_types_check<T>(stream, na, cl, 3, disp_types, mix, Ed + E_FMAX);
-      const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (K[2] / 2 + 1);
-      mesh.need(nt * nreal * sizeof(T));
-      spec.need(nt * nspec * sizeof(T));
-      sites.need(sizeof(Site<T>) * (size_t)na * nt);
-      fld_recip.need(3 * (size_t)na * sizeof(T) * nt);
-      onehot_d.need((size_t)na * nt * sizeof(T));
-      bases_d.need(sizeof(int4) * (size_t)na);
-      DftTabs<T> tabs;
-      for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = gtab_cur; }
-      const double no_self[3] = {0.0, 0.0, 0.0};
-      { TIMED("scalar_sites");
-        if (!disp_onehot_ok || onehot_for != onehot_d.p) {
-          launch_onehot<T>(stream, na, nt, disp_types, onehot_d.as<T>());
-          disp_onehot_ok = true; onehot_for = onehot_d.p;
-        }
-        launch_scalar_sites_batch<T>(stream, na, pos, onehot_d.as<T>(), nt, nt, no_self, sites.as<Site<T>>(), Ed, &g,
-                                     bases_d.as<int4>()); }
-      { TIMED("spread");
-        int rc = launch_spread<T>(stream, na, sites.as<Site<T>>(), 0, g, bins, mesh.as<T>(), nullptr, bases_d.as<int4>(), nt);
-        if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)}; }
-      const T* tw = dft_tw.as<T>();
-      { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh.as<T>(), spec.as<T>(), 0, nt, (long)nreal, (long)nspec); }
-      { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec.as<T>(), 0, nt, (long)nspec); }
-      { TIMED("dft_x_kspace"); launch_dft_x_mix<T>(stream, K, tw, spec.as<T>(), tabs, mix, (long)nspec, Ed, E_RECIP); }
-      { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec.as<T>(), 1, nt, (long)nspec); }
-      { TIMED("dft_z_c2r"); launch_dft_z<T>(stream, K, tw, mesh.as<T>(), spec.as<T>(), 1, nt, (long)nreal, (long)nspec); }
-      { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nt); }
-      { TIMED("scale_add"); launch_scale_add<T>(stream, na, onehot_d.as<T>(), nt, 0, fld_recip.as<T>(), dpos, nt); }
-      const double e_self = typed_self_energy(na, nch, kp);
-      read_scalar_energies(Ed, E, 3, true);
-      E[2] = e_self;
-      if (dpos_ && !on_device) {
-        HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-      }
-      return;
+    // the energies: a typed path takes its self term from the type table, and its read refuses a table that does not describe
+    // c_list; the brick paths and the typed ones read through the sum over the ranks
+    if (bricks || typed) {
+      const double e_self = typed ? typed_self_energy(na, nch, disp_kp().data()) : 0.0;
+      read_scalar_energies(sc.Ed, E, 3, typed);
+      if (typed) E[2] = e_self;
+      scalar_return_grad(sc, dpos_, on_device);
+    } else {
+      double Eh[E_SLOTS];
+      HIP_TRY(hipMemcpyAsync(Eh, sc.Ed, sizeof(Eh), hipMemcpyDeviceToHost, stream));
+      scalar_return_grad(sc, dpos_, on_device, false);
+      HIP_TRY(hipStreamSynchronize(stream));
+      E[0] = Eh[E_REAL]; E[1] = Eh[E_RECIP]; E[2] = Eh[E_SELF];
     }
-    if ((use_dft || use_pfa) && nch > 1) {
-      // direct-DFT meshes are small and dispatch bound: the powers are spread into separate meshes and transformed
-      // as ONE batch (5 launches instead of 5 per power); gather per power from its own mesh
-      const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (use_pfa ? pfa.Khp : K[2] / 2 + 1);
-      mesh.need(nch * nreal * sizeof(T));
-      spec.need(nch * nspec * sizeof(T));
-      DftTabs<T> tabs;
-      for (int c = 0; c < nch; ++c) {
-        ensure_gtab(box, inv, vol, 6 + 2 * c);
-        tabs.p[c] = gtab_cur;
-      }
-      sites.need(sizeof(Site<T>) * (size_t)na * nch);
-      fld_recip.need(3 * (size_t)na * sizeof(T) * nch);
-      const bool batch_spread = !spread_uses_bricks(na, g);        // the scan-spread regime takes the channels as a batch
-      if (batch_spread) {
-        // the stencil records ride along: every (brick, channel) workgroup of the scan spread reads them instead of
-        // redoing three grid_ref per atom (3072 atoms x 1029 workgroups at 97^3)
-        bases_d.need(sizeof(int4) * (size_t)na);
-        { TIMED("scalar_sites"); launch_scalar_sites_batch<T>(stream, na, pos, cl, 3, nch, kp, sites.as<Site<T>>(), Ed, &g,
-                                                              bases_d.as<int4>()); }
-        TIMED("spread");
-        int rc = launch_spread<T>(stream, na, sites.as<Site<T>>(), 0, g, bins, mesh.as<T>(), nullptr, bases_d.as<int4>(), nch);
-        if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
-      } else {
-        for (int c = 0; c < nch; ++c) {
-          { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed); }
-          TIMED("spread");
-          int rc = launch_spread<T>(stream, na, sites.as<Site<T>>(), 0, g, bins, mesh.as<T>() + c * nreal, nullptr, nullptr, 1,
-                                    c > 0);
-          if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
-        }
-      }
-      if (use_pfa) {
-        const T* tw = pfa_tw.as<T>();
-        { TIMED("dft_z_r2c"); launch_pfa_z<T>(stream, pfa, tw, mesh.as<T>(), spec.as<T>(), 0, nch, (long)nreal, (long)nspec); }
-        { TIMED("dft_y_fwd"); launch_pfa_y<T>(stream, pfa, tw, spec.as<T>(), 0, nch, (long)nspec); }
-        { TIMED("dft_x_kspace"); launch_pfa_x_conv<T>(stream, pfa, tw, spec.as<T>(), tabs, Ed, E_RECIP, nch, (long)nspec); }
-        { TIMED("dft_y_inv"); launch_pfa_y<T>(stream, pfa, tw, spec.as<T>(), 1, nch, (long)nspec); }
-        { TIMED("dft_z_c2r"); launch_pfa_z<T>(stream, pfa, tw, mesh.as<T>(), spec.as<T>(), 1, nch, (long)nreal, (long)nspec); }
-      } else {
-        const T* tw = dft_tw.as<T>();
-        { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh.as<T>(), spec.as<T>(), 0, nch, (long)nreal, (long)nspec); }
-        { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec.as<T>(), 0, nch, (long)nspec); }
-        { TIMED("dft_x_kspace"); launch_dft_x_conv<T>(stream, K, tw, spec.as<T>(), tabs, Ed, E_RECIP, nch, (long)nspec); }
-        { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec.as<T>(), 1, nch, (long)nspec); }
-        { TIMED("dft_z_c2r"); launch_dft_z<T>(stream, K, tw, mesh.as<T>(), spec.as<T>(), 1, nch, (long)nreal, (long)nspec); }
-      }
-      // the site rows hold the positions (only the charge slot differs per power): one gather over the batch of meshes
-      { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nch); }
-      { TIMED("scale_add"); launch_scale_add<T>(stream, na, cl, 3, 0, fld_recip.as<T>(), dpos, nch); }
-    } else
-    for (int c = 0; c < nch; ++c) {
-      ensure_gtab(box, inv, vol, 6 + 2 * c);
-      { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed); }
-      {
-        TIMED("spread");
-        int rc = launch_spread<T>(stream, na, sites.as<Site<T>>(), 0, g, bins, mesh.as<T>(), nullptr, nullptr, 1, c > 0);
-        if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
-      }
-      convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP);
-      { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr); }
-      { TIMED("scale_add"); launch_scale_add<T>(stream, na, cl, 3, c, fld_recip.as<T>(), dpos); }
-    }
-    double Eh[E_SLOTS];
-    HIP_TRY(hipMemcpyAsync(Eh, Ed, sizeof(Eh), hipMemcpyDeviceToHost, stream));
-    if (dpos_ && !on_device) HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    E[0] = Eh[E_REAL]; E[1] = Eh[E_RECIP]; E[2] = Eh[E_SELF];
   }
 
   void tt(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, double* E, void* dpos_,
@@ -2746,33 +2727,12 @@ struct Engine : EngineBase {
     ARG_CHECK(pos_ && box && abqc_ && E, "null argument");
     const int na = top.na;
     HIP_TRY(hipSetDevice(device));
-    double inv[9], vol;
-    Box<T> bx = make_box(box, inv, &vol);
-    ScaleTab<T> tab = make_tab(ns, mS, nullptr);
-    const T* pos = stage_in(s_pos, pos_, 3 * (size_t)na, on_device);
-    const T* par = stage_in(s_par, abqc_, 4 * (size_t)na, on_device);
-    grad.need(3 * (size_t)na * sizeof(T));
-    T* dpos = (dpos_ && on_device) ? reinterpret_cast<T*>(dpos_) : grad.as<T>();
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, E_WORDS * sizeof(double), stream));
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, abqc_, 4, dpos_, on_device, E_WORDS);
     ScalarRows sr{nullptr, na, nullptr};
-    if (snranks > 1) {     // no mesh on a pair potential: ownership by x-slabs of a virtual mesh of 64 planes per rank
-      ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      RecipGeom<T> g;
-      const int Kv = 64 * snranks;
-      g.K[0] = Kv; g.K[1] = g.K[2] = 32;
-      for (int k = 0; k < 9; ++k) { g.hinv[k] = (T)inv[k]; g.Aop[k] = g.Jac[k] = T(0); }
-      g.xoff = 64 * srank; g.nloc0 = 64 + kGhost; g.wrap0 = 1 << 30;
-      sr = scalar_rows(pos, g, Kv, 64 * srank, 64 * (srank + 1), true);
-    }
-    { TIMED("tt_pair"); launch_tt_pair<T>(stream, na, nbr, pack_srows(pos, par, 4), bx, tab, dpos, Ed, sr.rows, sr.n, cutoff); }
-    read_scalar_energies(Ed, E, 1);
-    if (dpos_ && !on_device) {
-      HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
+    if (snranks > 1) sr = virtual_slab_rows(sc.pos, sc.inv);
+    { TIMED("tt_pair"); launch_tt_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
+    read_scalar_energies(sc.Ed, E, 1);
+    scalar_return_grad(sc, dpos_, on_device);
   }
 
   // dE/dc_list (Na,3) of the dispersion PME energy (real + reciprocal + self; admp/disp_pme.py:80-123): the pair part is a
@@ -2797,24 +2757,21 @@ struct Engine : EngineBase {
     double* Ed = energies_d.as<double>();
     HIP_TRY(hipMemsetAsync(Ed, 0, E_WORDS * sizeof(double), stream));
     HIP_TRY(hipMemsetAsync(out, 0, 3 * (size_t)na * sizeof(T), stream));
+    const std::array<double, 3> kp = disp_kp();
+    const int nch = (pmax - 4) / 2;
     if (snranks > 1) {      // slab rank (round 4): pair sums over its home rows, the channels' mesh potentials at its home atoms
       ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
       cls_sites_na = slab_sites_na = -1;
       const ScalarRows sr = scalar_rows(pos, g, K[0], X0, X1, true);
       launch_scalar_pair_pgrad<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, out, cutoff, sr.rows, sr.n);
-      const double kq[3] = {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
-      const int nc = (pmax - 4) / 2;
       const size_t nreal = nreal_local();
-      mesh.need(nc * nreal * sizeof(T));
+      mesh.need(nch * nreal * sizeof(T));
       ensure_bins(std::max(sr.n, 1));
-      int rc = launch_bin_bricks<T>(stream, sr.n, (const Site<T>*)nullptr, g, bins, sr.home, bases_d.as<int4>());
-      if (rc == 0) rc = launch_spread_scalar<T>(stream, nc, pos, cl, 3, g, bins, mesh.as<T>(), (long)nreal);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("dispersion spread: ") + hipGetErrorString((hipError_t)rc)};
-      bins.counters_zero = true;
-      for (int c = 0; c < nc; ++c) {
+      spread_bricks(sr, g, nch, pos, cl, nullptr);
+      for (int c = 0; c < nch; ++c) {
         ensure_gtab(box, inv, vol, 6 + 2 * c);
         convolve(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP);
-        launch_gather_value<T>(stream, sr.n, pos, cl, 3, c, g, mesh.as<T>() + c * nreal, 2.0 * kq[c], out, sr.home);
+        launch_gather_value<T>(stream, sr.n, pos, cl, 3, c, g, mesh.as<T>() + c * nreal, 2.0 * kp[c], out, sr.home);
       }
       HIP_TRY(hipStreamSynchronize(stream));
       return;
@@ -2823,13 +2780,10 @@ struct Engine : EngineBase {
     cls_sites_na = slab_sites_na = -1;
     sites.need(sizeof(Site<T>) * (size_t)na);
     ensure_bins(na);
-    const double kp[3] = {-std::pow(kappa, 6) / 12.0, -std::pow(kappa, 8) / 48.0, -std::pow(kappa, 10) / 240.0};
-    const int nch = (pmax - 4) / 2;
     for (int c = 0; c < nch; ++c) {
       ensure_gtab(box, inv, vol, 6 + 2 * c);
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed);
-      int rc = launch_spread<T>(stream, na, sites.as<Site<T>>(), 0, g, bins, mesh.as<T>(), nullptr, nullptr, 1, c > 0);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("launch_spread: ") + hipGetErrorString((hipError_t)rc)};
+      spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0);
       convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP);
       launch_gather_value<T>(stream, na, pos, cl, 3, c, g, mesh.as<T>(), 2.0 * kp[c], out);
     }
@@ -2844,15 +2798,7 @@ struct Engine : EngineBase {
     ScaleTab<T> tab = make_tab(ns, mS, nullptr);
     const T* pos = reinterpret_cast<const T*>(pos_);
     ScalarRows sr{nullptr, top.na, nullptr};
-    if (snranks > 1) {      // the rows of the rank's home atoms (per-atom outputs: home rows are this rank's results)
-      ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      RecipGeom<T> gv;
-      const int Kv = 64 * snranks;
-      gv.K[0] = Kv; gv.K[1] = gv.K[2] = 32;
-      for (int k = 0; k < 9; ++k) { gv.hinv[k] = (T)inv[k]; gv.Aop[k] = gv.Jac[k] = T(0); }
-      gv.xoff = 64 * srank; gv.nloc0 = 64 + kGhost; gv.wrap0 = 1 << 30;
-      sr = scalar_rows(pos, gv, Kv, 64 * srank, 64 * (srank + 1), true);
-    }
+    if (snranks > 1) sr = virtual_slab_rows(pos, inv);      // (per-atom outputs: the home rows are this rank's results)
     launch_scalar_pair_pgrad<T>(stream, 1, top.na, nbr, pos, reinterpret_cast<const T*>(abqc_), bx,
                                 tab, T(0), 0, reinterpret_cast<T*>(out_), cutoff, sr.rows, sr.n);
     HIP_TRY(hipStreamSynchronize(stream));
@@ -2868,18 +2814,13 @@ struct Engine : EngineBase {
     const PairProgram& pg = programs[id];
     ARG_CHECK(pg.n_params == 0 || par_, "atomic parameters missing");
     const int na = top.na;
-    double inv[9], vol;
-    make_box(box, inv, &vol);
-    const T* pos = stage_in(s_pos, pos_, 3 * (size_t)na, on_device);
-    const T* par = pg.n_params ? stage_in(s_par, par_, (size_t)pg.n_params * na, on_device) : nullptr;
-    grad.need(3 * (size_t)na * sizeof(T));
-    T* dpos = (dpos_ && on_device) ? reinterpret_cast<T*>(dpos_) : grad.as<T>();
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    double* Ed = energies_d.as<double>();
-    HIP_TRY(hipMemsetAsync(Ed, 0, E_SLOTS * sizeof(double), stream));
+    // (the program reads the scales themselves, below: the record's table goes unused)
+    const ScalarCall sc = scalar_begin(box, ns, mS, pos_, pg.n_params ? par_ : nullptr, (size_t)pg.n_params, dpos_, on_device, E_SLOTS);
+    const T* pos = sc.pos; const T* par = sc.par;
+    T* dpos = sc.dpos;
+    double* Ed = sc.Ed;
     T consts[34];                                   // box (9), box^-1 (9), mscale per covalent class (16)
-    for (int k = 0; k < 9; ++k) { consts[k] = (T)box[k]; consts[9 + k] = (T)inv[k]; }
+    for (int k = 0; k < 9; ++k) { consts[k] = (T)box[k]; consts[9 + k] = (T)sc.inv[k]; }
     for (int nb = 0; nb < 16; ++nb) consts[18 + nb] = (T)mS[((nb - 1) % ns + ns) % ns];      // admp/pme.py:681-683 wrap
     prog_consts.need(sizeof(consts));
     HIP_TRY(hipMemcpyAsync(prog_consts.p, consts, sizeof(consts), hipMemcpyHostToDevice, stream));
@@ -2897,7 +2838,7 @@ struct Engine : EngineBase {
     }
     double Eh2[E_SLOTS];
     HIP_TRY(hipMemcpyAsync(Eh2, Ed, sizeof(Eh2), hipMemcpyDeviceToHost, stream));
-    if (dpos_ && !on_device) HIP_TRY(hipMemcpyAsync(dpos_, dpos, 3 * (size_t)na * sizeof(T), hipMemcpyDeviceToHost, stream));
+    scalar_return_grad(sc, dpos_, on_device, false);
     HIP_TRY(hipStreamSynchronize(stream));
     E[0] = Eh2[E_REAL];
   }
@@ -3169,15 +3110,8 @@ struct Engine : EngineBase {
     ScalarRows sr{nullptr, na, nullptr};
     if (snranks > 1) {      // the class sums of the rank's home rows, added over the ranks
       ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      RecipGeom<T> gv;
-      if (have_ewald) { update_slab(); gv = make_geom(inv); sr = scalar_rows(pos, gv, K[0], X0, X1, true); }
-      else {                // a pair potential has no mesh: x-slabs of a virtual one, as in tt()
-        const int Kv = 64 * snranks;
-        gv.K[0] = Kv; gv.K[1] = gv.K[2] = 32;
-        for (int k = 0; k < 9; ++k) { gv.hinv[k] = (T)inv[k]; gv.Aop[k] = gv.Jac[k] = T(0); }
-        gv.xoff = 64 * srank; gv.nloc0 = 64 + kGhost; gv.wrap0 = 1 << 30;
-        sr = scalar_rows(pos, gv, Kv, 64 * srank, 64 * (srank + 1), true);
-      }
+      if (have_ewald) { update_slab(); sr = scalar_rows(pos, make_geom(inv), K[0], X0, X1, true); }
+      else sr = virtual_slab_rows(pos, inv);      // a pair potential has no mesh, as in tt()
     }
     { TIMED("mscale_grad"); launch_mscale_sums<T>(stream, kind, na, nbr, sites.as<Site<T>>(), pos, par, bx, pmax, cls, cutoff,
                                                   sr.rows, sr.n); }
