@@ -526,16 +526,18 @@ __device__ __forceinline__ void zy_plane_spread(const PlaneSpread<T>& sp, int px
 // 1 + jj: sums, row N - 1 - jj: differences), one word per lane and step of 4 positions; a lane ends up with ONE component of
 // X[k] and X[N-k] and takes the other product's partner component from lane ^ 8 (tools/experiments/dft_mfma.hip).  out = the
 // plane's spectrum at this workgroup's first column, os its row stride.
+// The tile's outputs are k = 1 + ib + i <= kl (the forward plan: ib = 16 mt, kl = H; the inverse plan: a piece of one of the
+// workgroup's two ranges); w0 / wn (uniform): this unit also writes the column sums X[0] / X[N/2].
 template <class T, int SIGN>
-__device__ __forceinline__ void dft_y_unit(const PlaneMfmaPlan& mp, int u, const Cx<T>* Z, const Cx<T>* tw, Cx<T>* out, int os) {
+__device__ __forceinline__ void dft_y_unit_rows(int N, int H, int KP, int ncols, int ib, int kl, int ct, bool w0, bool wn,
+                                                const Cx<T>* Z, const Cx<T>* tw, Cx<T>* out, int os) {
   typedef typename Mfma<T>::Acc Acc;
-  const int N = mp.N, H = mp.H, mt = u % mp.MT, ct = u / mp.MT;
   const int lane = threadIdx.x & 63, hi = plane_mfma_pos0(lane);
-  const int i = plane_mfma_tw_row(mt, lane), c = plane_mfma_col(ct, lane), comp = plane_mfma_comp(lane);
-  TwIdx ti(i < H ? i : 0, hi, N);
-  const bool live = c < mp.ncols;
+  const int i = ib + (lane & 15), c = plane_mfma_col(ct, lane), comp = plane_mfma_comp(lane);
+  TwIdx ti(i < kl ? i : 0, hi, N);
+  const bool live = c < ncols;
   const T* zc = reinterpret_cast<const T*>(Z + (live ? c : 0)) + comp;
-  const int rs = 2 * mp.ncols;                                  // row stride in words
+  const int rs = 2 * ncols;                                     // row stride in words
   // two operand sets in flight: the LDS reads of a step are issued before the products of the step before it
   struct Ops { Cx<T> w; T b[2]; };
   auto fetch = [&](Ops& o, int kk) {
@@ -554,20 +556,20 @@ __device__ __forceinline__ void dft_y_unit(const PlaneMfmaPlan& mp, int u, const
   };
   Ops A, B;
   fetch(A, hi);
-  for (int kk = hi; kk < mp.KP; kk += 8) {
-    const bool two = kk + 4 < mp.KP;                            // (uniform: KP is a multiple of 4)
+  for (int kk = hi; kk < KP; kk += 8) {
+    const bool two = kk + 4 < KP;                               // (uniform: KP is a multiple of 4)
     if (two) fetch(B, kk + 4);
     mul(A);
-    if (kk + 8 < mp.KP) fetch(A, kk + 8);
+    if (kk + 8 < KP) fetch(A, kk + 8);
     if (two) mul(B);
   }
   const T x0 = zc[0], xn = (N & 1) ? T(0) : zc[(N / 2) * rs];
   T* o = reinterpret_cast<T*>(out + (live ? c : 0)) + comp;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int k = plane_mfma_out_k(mt, lane, r);
+    const int k = 1 + ib + (lane >> 4) + 4 * r;
     const T other = __shfl_xor(R[r], 8, 64);
-    if (live && k <= H) {
+    if (live && k <= kl) {
       T base = x0 + P[r];
       if ((N & 1) == 0) base += (k & 1) ? -xn : xn;
       const T q = comp ? T(SIGN) * other : -T(SIGN) * other;    // im: + sgn R.re ; re: - sgn R.im
@@ -575,15 +577,28 @@ __device__ __forceinline__ void dft_y_unit(const PlaneMfmaPlan& mp, int u, const
       o[2 * (long)(N - k) * os] = base - q;
     }
   }
-  if (mt == 0) {                                                // (uniform) X_0 and X_{N/2}: position j = 1 + hi + 4 n
+  if (w0 || wn) {                                               // (uniform) X_0 and X_{N/2}: position j = 1 + hi + 4 n
     T s1 = (hi & 1) ? s0 : -s0;
     s0 += __shfl_xor(s0, 16, 64); s1 += __shfl_xor(s1, 16, 64);
     s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
     if (hi == 0 && live) {
-      o[0] = x0 + s0 + xn;
-      if ((N & 1) == 0) o[2 * (long)(N / 2) * os] = x0 + s1 + (((N / 2) & 1) ? -xn : xn);
+      if (w0) o[0] = x0 + s0 + xn;
+      if (wn && (N & 1) == 0) o[2 * (long)(N / 2) * os] = x0 + s1 + (((N / 2) & 1) ? -xn : xn);
     }
   }
+}
+
+template <class T, int SIGN>
+__device__ __forceinline__ void dft_y_unit(const PlaneMfmaPlan& mp, int u, const Cx<T>* Z, const Cx<T>* tw, Cx<T>* out, int os) {
+  const int mt = u % mp.MT, ct = u / mp.MT;
+  dft_y_unit_rows<T, SIGN>(mp.N, mp.H, mp.KP, mp.ncols, plane_mfma_tw_row(mt, 0), mp.H, ct, mt == 0, mt == 0, Z, tw, out, os);
+}
+// the inverse kernel's: every column of the plane, the tile's rows from the plan
+template <class T>
+__device__ __forceinline__ void dft_y_unit_inv(const PlaneMfmaInvYPlan& yp, int u, const Cx<T>* Z, const Cx<T>* tw, Cx<T>* V) {
+  const int mt = u % yp.MT, ct = u / yp.MT;
+  dft_y_unit_rows<T, +1>(yp.N, yp.H, yp.KP, yp.ncols, plane_mfma_inv_y_kb(yp, mt) - 1, plane_mfma_inv_y_ke(yp, mt) - 1, ct,
+                         mt == 0 && yp.s.own0, mt == 0 && yp.s.ownn, Z, tw, V, yp.ncols);
 }
 
 // One matrix unit of the forward z lines (PlaneMfmaZPlan): 16 outputs k against 16 real lines; the twiddle operand is
@@ -744,7 +759,75 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_zy_fwd(int N2, int N3, const T
   ZY_TRACE_END(4);
 }
 
-template <class T, int KQ>
+// One matrix unit of the inverse z lines (PlaneMfmaInvZPlan): 16 lines of the workgroup's list against 16 outputs j.  The data
+// operand is A[i = lane & 15][position] = V[line][1 + position] (.re for P, .im for R), the twiddle operand B[position][lane & 15]:
+// a lane ends up with output j = 1 + 16 jt + (lane & 15) of four lines, and 16 neighbouring lanes store 16 neighbouring words.
+template <class T>
+__device__ __forceinline__ void dft_z_unit_inv(const PlaneMfmaInvZPlan& zp, int u, const Cx<T>* V, int Kh, const int* lines,
+                                               const Cx<T>* tw, T* plane, T* acc) {
+  typedef typename Mfma<T>::Acc Acc;
+  const int N = zp.N, H = zp.H, jt = u % zp.JT, lt = u / zp.JT;
+  const int lane = threadIdx.x & 63, hi = lane >> 4;
+  const int li = plane_mfma_inv_z_op_line(lt, lane), j = plane_mfma_inv_z_tw_j(jt, lane);
+  TwIdx ti((j <= H ? j : 1) - 1, hi, N);
+  const bool live = li < zp.nlines;
+  const Cx<T>* v = V + (live ? lines[li] : 0) * Kh;
+  struct Ops { Cx<T> w, a; };
+  auto fetch = [&](Ops& o, int kk) {
+    o.w = tw[ti.m];
+    ti.step();
+    o.a = (live && kk < H) ? v[1 + kk] : Cx<T>{T(0), T(0)};
+  };
+  Acc P = {0, 0, 0, 0}, R = {0, 0, 0, 0};
+  T s0 = T(0);                                                  // this lane's share of its line's sum of real parts (j = 0 and N / 2)
+  auto mul = [&](const Ops& o) {
+    s0 += o.a.re;
+    P = Mfma<T>::mma(o.a.re, o.w.re, P);
+    R = Mfma<T>::mma(o.a.im, o.w.im, R);
+  };
+  Ops A, B;
+  fetch(A, hi);
+  for (int kk = hi; kk < zp.KP; kk += 8) {
+    const bool two = kk + 4 < zp.KP;                            // (uniform: KP is a multiple of 4)
+    if (two) fetch(B, kk + 4);
+    mul(A);
+    if (kk + 8 < zp.KP) fetch(A, kk + 8);
+    if (two) mul(B);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int lo = plane_mfma_inv_z_out_line(lt, lane, r);
+    if (lo < zp.nlines && j <= H) {
+      const int l = lines[lo];
+      T base = V[l * Kh].re + T(2) * P[r];
+      if ((N & 1) == 0) { const T Xn = V[l * Kh + N / 2].re; base += (j & 1) ? -Xn : Xn; }
+      const T a = base - T(2) * R[r], b = base + T(2) * R[r];
+      plane[(long)l * N + j] = a;
+      plane[(long)l * N + N - j] = b;
+      if (acc) { acc[(long)l * N + j] += a; acc[(long)l * N + N - j] += b; }
+    }
+  }
+  if (jt == 0) {                                                // (uniform) x_0 and x_{N/2}: position k = 1 + hi + 4 n
+    T s1 = (hi & 1) ? s0 : -s0;
+    s0 += __shfl_xor(s0, 16, 64); s1 += __shfl_xor(s1, 16, 64);
+    s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
+    if (hi == 0 && live) {
+      const long o = (long)lines[li] * N;
+      const T X0 = v[0].re, Xn = (N & 1) ? T(0) : v[N / 2].re;
+      const T a = X0 + T(2) * s0 + Xn;
+      plane[o] = a;
+      if (acc) acc[o] += a;
+      if ((N & 1) == 0) {
+        const T b = X0 + T(2) * s1 + (((N / 2) & 1) ? -Xn : Xn);
+        plane[o + N / 2] = b;
+        if (acc) acc[o + N / 2] += b;
+      }
+    }
+  }
+}
+
+// MF (double precision): the y and the z lines as matrix units of their plans where the line length allows it (H >= 16)
+template <class T, int KQ, bool MF = false>
 __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const Cx<T>* __restrict__ spec, T* __restrict__ mesh,
                                                          const Cx<T>* __restrict__ tw2g, const Cx<T>* __restrict__ tw3g,
                                                          long mesh_stride, long spec_stride, T* __restrict__ accum) {
@@ -764,7 +847,11 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
   ZY_TRACE(0);
   for (int t = threadIdx.x; t < N3; t += kZyBlock) tw3[t] = tw3g[t];
   for (int t = threadIdx.x; t < N2; t += kZyBlock) tw2[t] = tw2g[t];
-  if (threadIdx.x == 0) {            // the y lines this workgroup produces: both members of its output pairs
+  if constexpr (MF) {                // the same lines in the order of the matrix units (plane_inv_line)
+    const PlaneInvSplit sl = plane_inv_split(N2, (int)blockIdx.z, (int)gridDim.z);
+    for (int t = threadIdx.x; t < sl.nlines; t += kZyBlock) s_lines[t] = plane_inv_line(sl, t);
+    if (threadIdx.x == 0) s_nlines = sl.nlines;
+  } else if (threadIdx.x == 0) {     // the y lines this workgroup produces: both members of its output pairs
     int n = 0;
     for (int g = g0; g < g1; ++g)
       for (int q = 0; q < KQ; ++q) {
@@ -789,7 +876,13 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
   }
   __syncthreads();
   ZY_TRACE(1);
-  for (int task = threadIdx.x; task < (g1 - g0) * Kh; task += kZyBlock) {
+  bool yshare = false;                                          // (every output and column, or none)
+  if constexpr (MF) {
+    const PlaneMfmaInvYPlan yp = plane_mfma_inv_y_plan(N2, Kh, (int)blockIdx.z, (int)gridDim.z, kZyBlock / 64);
+    yshare = yp.nunits > 0;
+    for (int u = threadIdx.x >> 6; u < yp.nunits; u += yp.Wm) dft_y_unit_inv<T>(yp, u, Z, tw2, V);
+  }
+  for (int task = yshare ? (g1 - g0) * Kh : (int)threadIdx.x; task < (g1 - g0) * Kh; task += kZyBlock) {
     const int g = g0 + task / Kh, c = task % Kh;
     int k[KQ];
 #pragma unroll
@@ -809,7 +902,13 @@ __global__ __launch_bounds__(kZyBlock) void k_dft_yz_inv(int N2, int N3, const C
   ZY_TRACE(2);
   // z lines back: line l reads its half spectrum V[l][0 .. Kh)
   const int TK3 = (Kh + KQ - 1) / KQ, nl = s_nlines;
-  for (int task = threadIdx.x; task < nl * TK3; task += kZyBlock) {
+  bool zshare = false;                                          // (every line and output, or none)
+  if constexpr (MF) {
+    const PlaneMfmaInvZPlan zp = plane_mfma_inv_z_plan(N3, nl, kZyBlock / 64);
+    zshare = zp.nunits > 0;
+    for (int u = threadIdx.x >> 6; u < zp.nunits; u += zp.Wm) dft_z_unit_inv<T>(zp, u, V, Kh, s_lines, tw3, plane, acc);
+  }
+  for (int task = zshare ? nl * TK3 : (int)threadIdx.x; task < nl * TK3; task += kZyBlock) {
     const int l = s_lines[task / TK3], g = task % TK3;
     int j[KQ];
 #pragma unroll
@@ -927,17 +1026,33 @@ template <class T>
 bool launch_dft_zy(hipStream_t st, const int K[3], const T* tw, T* mesh, T* spec, int inverse, int nb, long mesh_stride,
                    long spec_stride, T* accum, const PlaneSpread<T>* sp, int* mfma_share) {
   const size_t sh = ZyLayout<T>(K[1], K[2]).total;
-  // the matrix-core share of the forward z and y lines (plane_mfma_plan.h), double precision; ADMP_DFT_PLANE_MFMA=0 launches the
-  // vector kernels (read per call: the parity test runs both forms in one process)
-  const bool mf = sizeof(T) == 8 && !inverse && env_flag("ADMP_DFT_PLANE_MFMA", true) &&
-                  (plane_mfma_y_plan(K[1], (K[2] / 2 + 1) / 2, kZyBlock / 64).CT > 0 ||
-                   plane_mfma_z_plan(K[2], 0, (K[2] / 2 + 1) / 2, K[1], kZyBlock / 64).MT > 0);
+  // the matrix-core share of the z and y lines (plane_mfma_plan.h), double precision; ADMP_DFT_PLANE_MFMA=0 launches the vector
+  // kernels, ADMP_DFT_PLANE_MFMA_INV=0 the vector form of the inverse kernel alone (read per call: the parity tests run both
+  // forms in one process)
+  bool mf = sizeof(T) == 8 && env_flag("ADMP_DFT_PLANE_MFMA", true);
+  if (mf && inverse)
+    mf = env_flag("ADMP_DFT_PLANE_MFMA_INV", true) &&
+         (plane_mfma_inv_y_plan(K[1], K[2] / 2 + 1, 0, 2, kZyBlock / 64).nunits > 0 ||
+          plane_mfma_inv_z_plan(K[2], plane_inv_split(K[1], 0, 2).nlines, kZyBlock / 64).nunits > 0);
+  else if (mf)
+    mf = plane_mfma_y_plan(K[1], (K[2] / 2 + 1) / 2, kZyBlock / 64).CT > 0 ||
+         plane_mfma_z_plan(K[2], 0, (K[2] / 2 + 1) / 2, K[1], kZyBlock / 64).MT > 0;
   if (mfma_share) *mfma_share = mf ? 1 : 0;
   const Cx<T>* t1 = reinterpret_cast<const Cx<T>*>(tw) + K[0];
   const Cx<T>* t2 = t1 + K[1];
   const dim3 grid(K[0], nb, 2);                  // two workgroups per plane
   static size_t attr_set[2] = {0, 0};            // more than 64 KB of dynamic LDS has to be asked for (per kernel and size)
   if (inverse) {
+    if constexpr (sizeof(T) == 8) {
+      if (mf) {
+        static size_t attr_inv_mf = 0;
+        auto kern = k_dft_yz_inv<T, 2, true>;
+        if (attr_inv_mf < sh) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr_inv_mf = sh; }
+        kern<<<grid, kZyBlock, sh, st>>>(K[1], K[2], reinterpret_cast<const Cx<T>*>(spec), mesh, t1, t2, mesh_stride, spec_stride / 2,
+                                         nb == 1 ? accum : nullptr);
+        return accum != nullptr && nb == 1;
+      }
+    }
     auto kern = k_dft_yz_inv<T, 2>;
     if (attr_set[1] < sh) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr_set[1] = sh; }
     kern<<<grid, kZyBlock, sh, st>>>(K[1], K[2], reinterpret_cast<const Cx<T>*>(spec), mesh, t1, t2, mesh_stride, spec_stride / 2,

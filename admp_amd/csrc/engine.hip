@@ -86,6 +86,8 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   int64_t xpass_stats[2] = {0, 0};
   // launches of the plane kernels of the direct-DFT convolution (admp_plane_mfma_stats): [0] with a matrix-core share, [1] without
   int64_t plane_mfma_stats[2] = {0, 0};
+  // the same launches by direction (admp_plane_mfma_stats4): forward with a share, forward vector, inverse with a share, inverse vector
+  int64_t plane_mfma_stats4[4] = {0, 0, 0, 0};
   // closing pair kernels of polarizable calls (admp_pair_rider_stats): [0] rode in an x pass, [1] launched on their own
   int64_t pair_rider_stats[2] = {0, 0};
   const void* U_src = nullptr;  // admp_set_dipole_source: read-only initial dipoles of the NEXT polarizable evaluation
@@ -981,7 +983,7 @@ struct Engine : EngineBase {
       int mf = 0;
       if (planes && sp) { TIMED("dft_spread_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, sp, &mf); }
       else if (planes) { TIMED("dft_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, nullptr, &mf); }
-      if (planes) ++plane_mfma_stats[mf ? 0 : 1];
+      if (planes) { ++plane_mfma_stats[mf ? 0 : 1]; ++plane_mfma_stats4[mf ? 0 : 1]; }
       else {
         { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 0); }
         { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec_p, 0); }
@@ -996,7 +998,8 @@ struct Engine : EngineBase {
       if (planes) {
         TIMED("dft_yz_inv");
         added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum, nullptr, &mf);
-        ++plane_mfma_stats[mf ? 0 : 1];
+        ++plane_mfma_stats[1];                       // (word [1] counts the inverse launches of either form)
+        ++plane_mfma_stats4[mf ? 2 : 3];
       }
       else {
         { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec_p, 1); }
@@ -3423,6 +3426,12 @@ int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out2, "null");
     for (int k = 0; k < 2; ++k) { out2[k] = e.plane_mfma_stats[k]; if (reset) e.plane_mfma_stats[k] = 0; }
+  });
+}
+int admp_plane_mfma_stats4(admp_handle* h, int64_t* out4, int reset) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(out4, "null");
+    for (int k = 0; k < 4; ++k) { out4[k] = e.plane_mfma_stats4[k]; if (reset) e.plane_mfma_stats4[k] = 0; }
   });
 }
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,

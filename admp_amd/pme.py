@@ -440,7 +440,10 @@ class ADMPPmeForce(HipForceBase):
         """Launches of the plane kernels of the direct-DFT mesh convolution so far (admp_plane_mfma_stats): dict of counters."""
         out = (ctypes.c_int64 * 2)()
         _lib.check(self._h, self._L.admp_plane_mfma_stats(self._h, out, 1 if reset else 0), 'admp_plane_mfma_stats')
-        return {'matrix_share': int(out[0]), 'vector': int(out[1])}
+        out4 = (ctypes.c_int64 * 4)()
+        _lib.check(self._h, self._L.admp_plane_mfma_stats4(self._h, out4, 1 if reset else 0), 'admp_plane_mfma_stats4')
+        # matrix_share: forward launches with a share; vector: every other launch, inverse ones of either form included
+        return {'matrix_share': int(out[0]), 'vector': int(out[1]), 'inverse_share': int(out4[2]), 'inverse_vector': int(out4[3])}
 
     def pair_rider_stats(self, reset=False):
         """Where the closing pair kernels of the polarizable calls ran so far (admp_pair_rider_stats): dict of counters."""

@@ -524,9 +524,14 @@ int admp_scf_stats(admp_handle* h, int64_t* out8, int reset);
 /* Which form the x passes of the direct-DFT mesh convolution took: out2 = {one real circulant product per line (G table
  * even along x: orthorhombic cells; ADMP_DFT_XCIRC=0 turns it off), forward transform * G * inverse transform}. */
 int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset);
-/* Launches of the plane kernels of the direct-DFT mesh convolution: out2 = {with a matrix-core share of their line products
- * (double precision, forward kernel, lines of 33 points and more; ADMP_DFT_PLANE_MFMA=0 turns it off), in the vector form}. */
+/* Launches of the plane kernels of the direct-DFT mesh convolution: out2 = {FORWARD launches with a matrix-core share of their
+ * line products (double precision, lines of 33 points and more; ADMP_DFT_PLANE_MFMA=0 turns it off), every other plane launch:
+ * forward ones in the vector form and inverse ones of EITHER form}. */
 int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset);
+/* The same launches by direction: out4 = {forward with a share, forward in the vector form, inverse with a share (double
+ * precision, a y or z line of 33 points and more; ADMP_DFT_PLANE_MFMA_INV=0 turns that one off alone), inverse in the vector
+ * form}.  The two sets of counters are reset separately. */
+int admp_plane_mfma_stats4(admp_handle* h, int64_t* out4, int reset);
 /* The k-space leg of a reciprocal pass alone, on a mesh of the caller's (admp/recip.py:400-426):
  *     mesh <- IFFT( G * FFT(mesh) ) (unnormalised: N times numpy's ifftn),   *E_out = 1/2 sum_k G(k) |FFT(mesh)(k)|^2
  * with G the handle's own table for `box`: which = 1: 2 DIELECTRIC Ck_1 / theta_k^2, gamma point zero; which = 6, 8, 10:

@@ -8,7 +8,7 @@
 //   S = 4      matrix only: every column in tiles (the fourth column tile masked down to 0 / 1 column)
 // The phase is repeated between barriers and stamped with wall_clock64 (100 MHz) by thread 0, as ADMP_DFTM_TRACE did.
 // Part 2: the phases of the library's k_dft_zy_fwd<double, 2, false / true> in the vector form (ADMP_DFT_PLANE_MFMA=0) and with
-// the matrix-core share, and of k_dft_yz_inv<double, 2>, at 97^3 (ADMP_ZY_TRACE).
+// the matrix-core share, and of k_dft_yz_inv<double, 2, false / true> the same way, at 97^3 (ADMP_ZY_TRACE).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -fno-slp-vectorize -DADMP_ZY_TRACE \
 //     -Iadmp_amd/csrc -Iinclude tools/ubench/plane_hybrid.hip -o plane_hybrid
 // run: plane_hybrid [out.json]
@@ -249,13 +249,13 @@ int main(int argc, char** argv) {
   for (int d = 0; d < 3; ++d) { sp.g.hinv[4 * d] = 1.0 / box; sp.g.Aop[4 * d] = -(double)N / box; sp.g.Jac[4 * d] = (double)N / box; }
   sp.g.whole_mesh();
   if (!dft_zy_spread_fits<double>(K, na)) { printf("the spread form does not fit\n"); return 1; }
-  constexpr int NK = 5;
+  constexpr int NK = 6;
   const char* kname[NK] = {"k_dft_zy_fwd<double,2,false,false>", "k_dft_zy_fwd<double,2,false,true>", "k_dft_zy_fwd<double,2,true,false>",
-                           "k_dft_zy_fwd<double,2,true,true>", "k_dft_yz_inv<double,2>"};
+                           "k_dft_zy_fwd<double,2,true,true>", "k_dft_yz_inv<double,2,false>", "k_dft_yz_inv<double,2,true>"};
   const char* pname[NK][4] = {{"load", "z lines", "pairing", "y lines + stores"}, {"load", "z lines", "pairing", "y lines + stores"},
                               {"spread", "z lines", "pairing", "y lines + stores"}, {"spread", "z lines", "pairing", "y lines + stores"},
-                              {"load + pairing", "y lines", "z lines + stores", ""}};
-  const int np[NK] = {4, 4, 4, 4, 3};
+                              {"load + pairing", "y lines", "z lines + stores", ""}, {"load + pairing", "y lines", "z lines + stores", ""}};
+  const int np[NK] = {4, 4, 4, 4, 3, 3};
   if (js) fprintf(js, " \"kernel_phases_ns\": {\n");
   for (int kk = 0; kk < NK; ++kk) {
     setenv("ADMP_DFT_PLANE_MFMA", (kk & 1) ? "1" : "0", 1);
@@ -263,7 +263,7 @@ int main(int argc, char** argv) {
     for (int run = 0; run < nrun; ++run) {
       hipEvent_t a, b; CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b));
       CHECK(hipEventRecord(a));
-      launch_dft_zy<double>(0, K, twd, mesh, spec, kk == 4, 1, 0, 0, nullptr, (kk == 2 || kk == 3) ? &sp : nullptr);
+      launch_dft_zy<double>(0, K, twd, mesh, spec, kk >= 4, 1, 0, 0, nullptr, (kk == 2 || kk == 3) ? &sp : nullptr);
       CHECK(hipEventRecord(b));
       CHECK(hipDeviceSynchronize());
       float ms; CHECK(hipEventElapsedTime(&ms, a, b));
