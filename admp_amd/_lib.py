@@ -82,6 +82,8 @@ PROTOTYPES = {
     'admp_plane_mfma_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_plane_mfma_stats4': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_mesh_convolve': (_i32, [_vp, _dp, _i32, _vp, _i32, _dp, _ip]),
+    'admp_slab_mesh_convolve': (_i32, [_vp, _dp, _i32, _vp, _i32, _dp, _ip]),
+    'admp_slab_lists': (_i32, [_vp, _i32, _i32, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _c.POINTER(_i64)]),
     'admp_pair_real': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _i32, _dp, _dp, _vp, _vp, _i32, _i32, _i32, _dp, _vp, _vp, _vp, _ip]),
     'admp_pair_rider_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_mesh_spread': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _ip]),

@@ -162,6 +162,7 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
                         const double* mS, const double* pS, const void* U, double* E, void* dpos, void* dU, void* dQl) = 0;
   virtual void local_frames(const void* pos, const double* box, void* out) = 0;
   virtual void mesh_convolve(const double* box, int which, void* data, int on_device, double* E_out, int32_t* info) = 0;
+  virtual void slab_mesh_convolve(const double* box, int which, void* data, int on_device, double* E_out, int32_t* info) = 0;
   virtual void pair_program_eval(int id, const void* pos, const double* box, const void* par, int ns, const double* mS,
                                  double* E, void* dpos, int on_device) = 0;
 
@@ -234,6 +235,8 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   virtual void prune_pairs(const void* pos, const double* box, double rc) = 0;
   virtual void slab_info(int64_t* out) = 0;
   virtual void slab_home(int32_t* out, int* n_home, int* n_import) = 0;
+  virtual void slab_lists(int na, int nranks, int32_t* owner, int32_t* bits, int32_t* home, int32_t* rows, int32_t* act,
+                          int32_t* imp, int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts) = 0;
 
   void free_topology() {
     if (top.axis_type) (void)hipFree(top.axis_type);
@@ -434,6 +437,7 @@ struct SlabState {
   int64_t tr_send[kSlabMaxRanks], tr_recv[kSlabMaxRanks];
   int64_t imp_cnt[kSlabMaxRanks], exp_cnt[kSlabMaxRanks];     // atoms imported from / exported to every rank
   int n_home = 0, n_act = 0, n_imp = 0, n_exp = 0;
+  bool tracked = false;         // the last decomposition compared its owners with the previous one's (mig_in / mig_out are lists)
   const int* home = nullptr;    // home atoms, ascending
   const int* rows = nullptr;    // home rows in the pair kernels' order (the table's class-grouped order, filtered)
   const int* act = nullptr;     // polarizable home atoms, ascending
@@ -657,6 +661,7 @@ struct Engine : EngineBase {
     launch_slab_concat(stream, si, L, (long)na, sl.imp.as<int>());
     launch_slab_concat(stream, se, L, (long)na, sl.exp.as<int>());
     sl.n_min = sl.n_mout = 0;
+    sl.tracked = track;
     if (track) {
       SlabSegs mi, mo;
       mi.off[0] = mo.off[0] = 0;
@@ -721,6 +726,35 @@ struct Engine : EngineBase {
     if (out) HIP_TRY(hipMemcpyAsync(out, sl.home, sizeof(int) * (size_t)sl.n_home, hipMemcpyDeviceToDevice, stream));
     if (n_home) *n_home = sl.n_home;
     if (n_import) *n_import = sl.n_imp;
+  }
+  // admp_slab_lists: what decompose() left on the device, copied to the host as it stands (no kernel runs)
+  void slab_lists(int na, int nranks, int32_t* owner, int32_t* bits, int32_t* home, int32_t* rows, int32_t* act, int32_t* imp,
+                  int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts) override {
+    ARG_CHECK(snranks > 1, "admp_slab_lists works on a slab-decomposed handle only");
+    ARG_CHECK(sl.home, "no decomposed evaluation has run on this handle");
+    ARG_CHECK(na == top.na && nranks == snranks, "n_atoms / nranks are not those of the handle");
+    ARG_CHECK(owner && bits && home && rows && act && imp && exp && mig_in && mig_out && counts, "null argument");
+    auto back = [&](int32_t* dst, const void* src, int n) {
+      if (n > 0) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    };
+    back(owner, sl.owner.p, na);
+    back(bits, sl.bits.p, na);
+    back(home, sl.home, sl.n_home);
+    back(rows, sl.rows, sl.n_home);
+    back(act, sl.act, sl.n_act);
+    back(imp, sl.imp.p, sl.n_imp);
+    back(exp, sl.exp.p, sl.n_exp);
+    back(mig_in, sl.mig_in.p, sl.n_min);
+    back(mig_out, sl.mig_out.p, sl.n_mout);
+    HIP_TRY(hipStreamSynchronize(stream));
+    counts[0] = sl.n_home; counts[1] = sl.n_act; counts[2] = sl.n_imp; counts[3] = sl.n_exp;
+    counts[4] = sl.tracked ? 1 : 0; counts[5] = sl.n_min; counts[6] = sl.n_mout; counts[7] = 0;
+    for (int t = 0; t < snranks; ++t) {
+      counts[8 + t] = sl.imp_cnt[t];
+      counts[8 + snranks + t] = sl.exp_cnt[t];
+      counts[8 + 2 * snranks + t] = sl.tracked ? sl.min_cnt[t] : 0;
+      counts[8 + 3 * snranks + t] = sl.tracked ? sl.mout_cnt[t] : 0;
+    }
   }
   // the residual word of an SCF check: maximum over the ranks (bit patterns of non-negative doubles are doubles)
   void reduce_check_word(unsigned long long* word) {
@@ -1169,6 +1203,33 @@ struct Engine : EngineBase {
     } else {
       info[0] = use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT;
     }
+  }
+
+  // admp_slab_mesh_convolve: the same leg on a slab rank -- its local mesh as an evaluation holds it between spread and gather
+  // (own planes, then the kGhost overhang planes meant for the next rank), through ensure_mesh, ensure_gtab and convolve(),
+  // which is slab_convolve with the x pass this handle takes; every rank of the communicator makes the call
+  void slab_mesh_convolve(const double* box, int which, void* data_, int on_device, double* E_out, int32_t* info) override {
+    ARG_CHECK(have_ewald, "admp_set_ewald first");
+    ARG_CHECK(snranks > 1, "admp_slab_mesh_convolve works on a slab-decomposed handle only (single rank: admp_mesh_convolve)");
+    ARG_CHECK(box && data_ && E_out && info, "null argument");
+    ARG_CHECK(which == 1 || which == 6 || which == 8 || which == 10, "which must be 1, 6, 8 or 10");
+    double inv[9], vol;
+    make_box(box, inv, &vol);
+    ensure_mesh();
+    ensure_gtab(box, inv, vol, which);
+    const size_t nreal = (size_t)nloc0() * K[1] * K[2];
+    T* m = on_device ? reinterpret_cast<T*>(data_) : mesh.as<T>();
+    if (!on_device) HIP_TRY(hipMemcpyAsync(m, data_, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
+    energies_d.need(2 * E_WORDS * sizeof(double));
+    ehalf = 0; other_clean = false;
+    HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
+    convolve(m, spec.as<T>(), gtab_cur, E_RECIP);
+    if (!on_device) HIP_TRY(hipMemcpyAsync(data_, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(E_out, Ed_cur() + E_RECIP, sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < ADMP_MESH_INFO_WORDS; ++k) info[k] = 0;
+    info[0] = use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT;
+    info[2] = X0; info[3] = X1; info[4] = Y0; info[5] = Y1; info[6] = fx_khp; info[7] = K[2] / 2 + 1;
   }
 
   ScaleTab<T> make_tab(int ns, const double* mS, const double* pS) {
@@ -3438,6 +3499,10 @@ int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_
                        int32_t* info16) {
   return guarded(h, [&](EngineBase& e) { e.mesh_convolve(box, which, mesh_inout, on_device, E_out, info16); });
 }
+int admp_slab_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
+                            int32_t* info16) {
+  return guarded(h, [&](EngineBase& e) { e.slab_mesh_convolve(box, which, mesh_inout, on_device, E_out, info16); });
+}
 int admp_pair_real(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
                    const void* tholes, int n_scales, const double* mScales, const double* pScales, const void* U,
                    const void* F, int which, int flags, int on_device, double* E_out, void* grad, void* pot, void* fld,
@@ -3468,6 +3533,12 @@ int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {
 }
 int admp_slab_home(admp_handle* h, int32_t* home_out, int* n_home, int* n_import) {
   return guarded(h, [&](EngineBase& e) { e.slab_home(home_out, n_home, n_import); });
+}
+int admp_slab_lists(admp_handle* h, int n_atoms, int nranks, int32_t* owner, int32_t* bits, int32_t* home, int32_t* rows,
+                    int32_t* act, int32_t* imp, int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts) {
+  return guarded(h, [&](EngineBase& e) {
+    e.slab_lists(n_atoms, nranks, owner, bits, home, rows, act, imp, exp, mig_in, mig_out, counts);
+  });
 }
 
 int admp_profile_enable(admp_handle* h, int on) {

@@ -514,6 +514,16 @@ int admp_set_comm_rccl(admp_handle* h, admp_rccl* c);
  * int32) receives the home atoms of the last evaluation in ascending order, *n_home their number; n_import (optional) the
  * number of atoms the rank read without owning them. */
 int admp_slab_home(admp_handle* h, int32_t* home_out, int* n_home, int* n_import);
+/* The lists of the last decomposed evaluation of a handle, copied to HOST arrays as they stand on the device (test entry: no
+ * kernel runs; ADMP_E_ARG on a single-rank handle, on a handle without a decomposed evaluation, and when n_atoms / nranks are
+ * not the handle's).  owner, bits: n_atoms words (owner of every atom; kSlabHome / kSlabPolar / reader bits of slab_kernels.hip).
+ * home (ascending), rows (the home rows in the pair kernels' order), act (polarizable home atoms), imp (atoms read from every
+ * other rank, rank after rank), mig_in, mig_out (atoms that changed hands since the handle's previous evaluation): room for
+ * n_atoms words each.  exp (atoms sent to every other rank, rank after rank; an atom may go to several): room for n_atoms *
+ * nranks words.  counts (8 + 4 nranks words): {n_home, n_act, n_import, n_export, 1 if the evaluation tracked migrants,
+ * n_mig_in, n_mig_out, 0}, then per rank the lengths of its segment of imp, exp, mig_in, mig_out. */
+int admp_slab_lists(admp_handle* h, int n_atoms, int nranks, int32_t* owner, int32_t* bits, int32_t* home, int32_t* rows,
+                    int32_t* act, int32_t* imp, int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts);
 
 /* How the polarizable evaluations of this handle were enqueued (the residual history of the previous calls decides between
  * the plain loop, a speculative first cycle and a chain of device-gated Jacobi steps: engine.hip pme()) and what the guesses
@@ -552,6 +562,20 @@ int admp_plane_mfma_stats4(admp_handle* h, int64_t* out4, int reset);
 #define ADMP_MESH_PATH_TWO_LEVEL 4     /* Good-Thomas split (pfa_kernels.hip) */
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
                        int32_t* info16);
+/* The same leg on the ranks of a slab-decomposed handle (test entry; a single-rank handle returns ADMP_E_ARG).  Needs
+ * admp_set_ewald, admp_slab_configure or admp_set_comm_rccl, and a communicator (no topology, no pairs); every rank makes the
+ * call, as with an evaluation.  mesh_inout is the rank's LOCAL mesh exactly as an evaluation holds it between spread and
+ * gather: (X1-X0) + 5 planes of K2 K3 words of the handle's type, on the device or on the host -- the rank's own planes, then
+ * the 5 overhang planes meant for the next rank.  The call runs the distributed convolution of an evaluation and nothing else
+ * (ghost planes sent on and added, y-z transforms, transpose, the x pass the handle would choose with the rank's rows of the G
+ * table, and back).  It returns phi on the own planes and, in the 5 ghost planes, what the closing shift delivered: the next
+ * rank's first 5 planes of phi.  *E_out is this rank's share of 1/2 sum_k G |S|^2 (its rows Y0 <= ky < Y1 of the transposed
+ * spectrum); the sum over the ranks is the energy.
+ * info16: [0] the x pass: ADMP_MESH_PATH_FUSED_X = the fused x kernel on the transposed layout, ADMP_MESH_PATH_ROCFFT = rocFFT
+ * 1-D lines around the G kernel; [2] X0 [3] X1 [4] Y0 [5] Y1; [6] row pitch of the y-z spectrum (complex numbers); [7] K3/2+1;
+ * every other word 0. */
+int admp_slab_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,
+                            int32_t* info16);
 /* One real-space pair kernel alone, and its raw per-atom rows (test entry; single rank: a slab-decomposed handle returns
  * ADMP_E_ARG).  The call does what an evaluation does up to that kernel -- sites prepared at the dipoles U as given (no SCF),
  * site classes compiled into the neighbour table, the inner table of admp_set_cutoff -- and launches it through the
