@@ -728,4 +728,13 @@ template <class T>
 int launch_md_fire(hipStream_t st, int n, T* pos, T* vel, const T* grad, const T* inv_mass, const double* par9, double ftol,
                    uint64_t call, double* rows, double* state16);
 
+// ---- vrescale_kernels.hip: one application of the stochastic velocity-rescaling thermostat (md_vrescale_math.h): the closing half
+// kick (grad != nullptr) and the kinetic energy as one double per workgroup in `rows` (>= kVrRowsBytes), then fold + rule + scale.
+// state16 (device): two slots of 8 doubles, slot call & 1 is read, the other written; n = 0 copies the slot forward.  Returns
+// hipError_t as int.
+constexpr size_t kVrRowsBytes = 256 * sizeof(double);
+template <class T>
+int launch_md_vrescale(hipStream_t st, int n, T* vel, const T* grad, const T* inv_mass, double half_dt_acc, int64_t n_dof,
+                       double kT_acc, double c, uint64_t seed, uint64_t step, uint64_t call, double* rows, double* state16);
+
 }  // namespace admp

@@ -1,5 +1,5 @@
 // The MD-driver helpers behind the admp_md_* entries of include/admp_hip.h (md_kernels.hip, mts_kernels.hip, con_kernels.hip,
-// mol_kernels.hip, fire_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
+// mol_kernels.hip, fire_kernels.hip, vrescale_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
 // profiler and its rank count (handle.h HandleCtx), nothing of the engine.  The driver of a handle is created by its first
 // admp_md_* call, in the handle's precision, and dies with the handle.
 //
@@ -8,13 +8,14 @@
 //   * Every other entry refuses a slab-decomposed handle with ADMP_E_STATE and "the MD helpers serve single-rank handles only",
 //     before it looks at any other argument ...
 //   * ... but admp_md_fire_step refuses it with ADMP_E_ARG and "... single-rank handles only (slab-decomposed handle)".
+//   * admp_md_vrescale refuses it like the older entries: ADMP_E_STATE, their text, before any other argument.
 //   * A missing plan gives ADMP_E_ARG with "<plan entry> must precede <this entry>".
 //   * admp_md_virial and admp_md_mol_sums clear the 21 doubles of their output before the launch.
 //   * admp_md_fire_step maps a non-zero return of launch_md_fire to ADMP_E_HIP with the prefix "FIRE step: ".
 //   * admp_md_mts_step checks n_inner before it looks for null pointers; the launches of the other two plans look for null
 //     inv_mass / box first (MdDriver::planned).
 //   * The profiler labels: md_bonded, md_kick_drift, md_langevin, md_random, md_bonded_box, md_virial, md_scale, md_mts,
-//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire.
+//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire, md_vrescale.
 //   * The three *_info layouts differ (see the three functions); in each, words 0-6 are zero while no plan is held and word 7,
 //     the launch count, is always reported.
 //   * Tests match on the error texts: they stay byte for byte.
@@ -355,6 +356,25 @@ struct MdDriver : HandleExt {
                                      fire_rows.as<double>(), state16_dev);
     if (rc != 0) throw Err{ADMP_E_HIP, std::string("FIRE step: ") + hipGetErrorString((hipError_t)rc)};
   }
+
+  // the velocity-rescaling thermostat (vrescale_kernels.hip, md_vrescale_math.h; admp_amd/md.py VRescale): the driver owns the
+  // rows of partial sums, the caller the state; every argument is checked before the first launch
+  DevBuf vr_rows;
+  void vrescale(int n, void* vel, const void* grad_, const void* inv_mass, double half_dt_acc, int64_t n_dof, double kT_acc,
+                double c, uint64_t seed, uint64_t step, uint64_t call, double* state16_dev) {
+    single_rank();
+    ARG_CHECK(n >= 0 && n <= INT_MAX / 4 && state16_dev && (n == 0 || (vel && inv_mass)), "bad argument");
+    ARG_CHECK(n_dof >= 1, "n_dof must be at least 1");
+    ARG_CHECK(c >= 0.0 && c <= 1.0, "c must lie in [0, 1]");
+    ARG_CHECK(std::isfinite(kT_acc) && kT_acc >= 0.0, "kT_acc must be finite and not negative");
+    ARG_CHECK(std::isfinite(half_dt_acc), "half_dt_acc must be finite");
+    vr_rows.need(kVrRowsBytes);
+    TIMED("md_vrescale");
+    const int rc = launch_md_vrescale<T>(stream, n, reinterpret_cast<T*>(vel), reinterpret_cast<const T*>(grad_),
+                                         reinterpret_cast<const T*>(inv_mass), half_dt_acc, n_dof, kT_acc, c, seed, step, call,
+                                         vr_rows.as<double>(), state16_dev);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("velocity rescaling: ") + hipGetErrorString((hipError_t)rc)};
+  }
 };
 
 template <class T>
@@ -468,6 +488,12 @@ int admp_md_mol_info(admp_handle* h, int64_t* out8) {
 int admp_md_fire_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
                       const double* params9, double ftol, uint64_t call, double* state16_dev) {
   return md_call(h, [&](auto& md) { md.fire_step(n_atoms, positions, velocities, grad, inv_mass, params9, ftol, call, state16_dev); });
+}
+int admp_md_vrescale(admp_handle* h, int n_atoms, void* velocities, const void* grad, const void* inv_mass, double half_dt_acc,
+                     int64_t n_dof, double kT_acc, double c, uint64_t seed, uint64_t step, uint64_t call, double* state16_dev) {
+  return md_call(h, [&](auto& md) {
+    md.vrescale(n_atoms, velocities, grad, inv_mass, half_dt_acc, n_dof, kT_acc, c, seed, step, call, state16_dev);
+  });
 }
 
 }  // extern "C"

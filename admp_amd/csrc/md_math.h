@@ -20,8 +20,9 @@ namespace admp {
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;      // round multipliers
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;      // Weyl increments of the key
-// streams of the drivers: the thermostat's noise, the initial velocities and the barostat's noise never share a counter
-constexpr uint32_t kStreamLangevin = 0, kStreamMaxwell = 1, kStreamBarostat = 2;
+// streams of the drivers: the thermostat's noise, the initial velocities, the barostat's noise and the velocity-rescaling
+// thermostat's (md_vrescale_math.h) never share a counter
+constexpr uint32_t kStreamLangevin = 0, kStreamMaxwell = 1, kStreamBarostat = 2, kStreamVRescale = 3;
 
 ADMP_HD uint32_t mulhi32(uint32_t a, uint32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -34,6 +34,13 @@ a `HarmonicBonded` and / or a `Constraints`.  Used by examples/md/npt_water.py -
 sums and maxima in double without atomics, then the decision -- downhill or uphill, the new time step, converged, failed -- taken
 on the device from a double-buffered state (csrc/md_fire_math.h), so an iteration reads nothing back and is bit-repeatable; with
 a `Constraints` it minimises on them.  Used by examples/md/minimize_water.py and by every driver with --minimizer fire.
+
+`VRescale` is the global thermostat: stochastic velocity rescaling (Bussi, Donadio and Parrinello 2007), the one the two
+barostats were designed to run with.  One application is one C call (admp_md_vrescale) of two kernels: the closing half kick of
+the step and the kinetic energy in double without atomics, then the draw of the new kinetic energy and the factor on the device
+from (seed, step) (csrc/md_vrescale_math.h) and one pass that scales the velocities -- nothing read back, bit-repeatable.  One
+factor for all atoms keeps constrained velocities on their constraints, and the state carries the heat the thermostat has put
+in, so E_pot + K - heat is conserved.  Used by every driver in examples/md with --thermostat vrescale.
 """
 import ctypes
 
@@ -45,6 +52,7 @@ from ._device import HipForceBase
 
 KB = 0.0083144626          # kJ/mol/K
 STREAM_LANGEVIN, STREAM_MAXWELL, STREAM_BAROSTAT = 0, 1, 2      # csrc/md_math.h: the users of the generator never share a counter
+STREAM_VRESCALE = 3
 BAR_PER_KJ_MOL_A3 = 16605.39      # 1 kJ/mol/A^3 in bar
 
 
@@ -880,3 +888,102 @@ class FireMinimizer:
         if info['failed']:
             raise FloatingPointError('FIRE: a force or a velocity is not finite (iteration %d)' % info['iterations'])
         return info
+
+
+class VRescale:
+    """Stochastic velocity rescaling at `temperature` (K) with relaxation time `tau_fs` (Bussi, Donadio, Parrinello, J. Chem.
+    Phys. 126, 014101, 2007); units as in VelocityVerlet (the rule is csrc/md_vrescale_math.h, the entry admp_md_vrescale).
+    Once per step all velocities are multiplied by one factor alpha = sqrt(K' / K), where K is their kinetic energy and
+
+        K' = (sqrt(c K) + sqrt((1 - c) kT / 2) R1)^2 + (1 - c) (kT / 2) S,   c = exp(-dt / tau), R1 ~ N(0, 1), S ~ chi^2(n_dof - 1)
+
+    with R1 and S functions of (seed, step) alone (stream 3 of the generator).  `n_dof` defaults to 3 N; pass 3 N - n_constraints
+    for constrained atoms, 3 N - 3 after maxwell_boltzmann(remove_com=True).  tau_fs = inf is c = 1 (alpha = 1 exactly: plain
+    dynamics), tau_fs = 0 is c = 0 (a fresh canonical kinetic energy every step).
+
+    `kick` is the closing half kick of a step (that of VelocityVerlet.kick or Langevin.kick, bit for bit) and the thermostat in
+    one C call; `apply` is the thermostat alone, for after ConstrainedLangevin.kick, MTSLangevin.kick or a barostat's apply at
+    friction 0.  Both then add 1 to `step`, which may be set (a restart draws the same noise again); `call` selects the slot of
+    the state and is the object's own.  The state is 2 x 8 doubles on the device (K before, K after, alpha, heat, applications,
+    tries, 0, flags); neither call reads anything back, `info()` is one host read.  E_pot + kinetic_energy() - heat() is the
+    conserved quantity of the thermostatted dynamics.  A kinetic energy that is not finite sets `failed`: nothing is scaled from
+    then on, until reset().  For a given number of atoms the result is a function of the inputs alone, bit for bit."""
+    ACC = VelocityVerlet.ACC
+    STATE_WORDS = ('k_before', 'k_after', 'alpha', 'heat', 'applications', 'tries')      # then a reserved word and the flags
+    FAILED = 1
+
+    def __init__(self, handle_owner, masses, dt_fs, temperature, tau_fs, seed, n_dof=None):
+        self._o = handle_owner
+        self.dt, self.T, self.tau, self.seed = float(dt_fs), float(temperature), float(tau_fs), int(seed)
+        if not (np.isfinite(self.T) and self.T >= 0 and np.isfinite(self.dt) and self.dt >= 0 and self.tau >= 0
+                and 0 <= self.seed < 2 ** 64):
+            raise ValueError('temperature, tau and dt must not be negative (temperature and dt finite); the seed is an unsigned '
+                             '64-bit number')
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if not (np.all(m > 0) and np.all(np.isfinite(m))):
+            raise ValueError('masses must be positive and finite')
+        self.n_atoms = len(m)
+        self.n_dof = 3 * self.n_atoms if n_dof is None else n_dof
+        if self.n_dof != int(self.n_dof) or self.n_dof < 1:
+            raise ValueError('n_dof must be an integer of at least 1')
+        self.n_dof = int(self.n_dof)
+        self.c = 0.0 if self.tau == 0.0 else float(np.exp(-self.dt / self.tau))      # (tau = inf: 1)
+        self.kT_acc = KB * self.T * self.ACC
+        self.inv_mass = handle_owner._real(1.0 / m)
+        self.state = torch.zeros((2, 8), dtype=torch.float64, device=handle_owner._device)
+        self.step = 0
+        self.reset()
+
+    def reset(self):
+        """a fresh state in both slots (alpha 1, everything else 0), call = 0: also what clears `failed`; `step` stays"""
+        fresh = torch.tensor([0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float64)
+        self.state.copy_(fresh.expand(2, 8))
+        self.call = 0
+
+    def _apply(self, vel, grad):
+        o = self._o
+        o._use_current_stream()
+        P = o._ptr
+        rc = o._L.admp_md_vrescale(o._h, self.n_atoms, P(vel), None if grad is None else P(grad), P(self.inv_mass),
+                                   0.5 * self.dt * self.ACC, self.n_dof, self.kT_acc, self.c, self.seed,
+                                   int(self.step) & (2 ** 64 - 1), self.call & (2 ** 64 - 1), P(self.state))
+        if rc == -1:                                                  # ADMP_E_ARG
+            msg = o._L.admp_last_error(o._h)
+            raise ValueError('admp_md_vrescale: %s' % (msg.decode() if msg else ''))
+        _lib.check(o._h, rc, 'admp_md_vrescale')
+        self.call += 1
+        self.step += 1
+
+    def kick(self, vel, grad):
+        """second half of a step, v -= (dt/2) 1e-4 grad / m with the gradient at r(t + dt), then the thermostat; step += 1"""
+        _checked(self._o, self.n_atoms, vel=vel, grad=grad)
+        self._apply(vel, grad)
+
+    def apply(self, vel):
+        """the thermostat alone on the velocities as they are; step += 1"""
+        _checked(self._o, self.n_atoms, vel=vel)
+        self._apply(vel, None)
+
+    def info(self):
+        """(host read) the state after the last application: k_before, k_after, heat (kJ/mol), alpha, applications, tries (of
+        the gamma deviate's rejection loop in the last draw), and the flag as the bool failed"""
+        w = self.state[self.call & 1].cpu().numpy()
+        out = dict(zip(self.STATE_WORDS, (float(x) for x in w[:6])))
+        for k in ('k_before', 'k_after', 'heat'):
+            out[k] /= self.ACC
+        for k in ('applications', 'tries'):
+            out[k] = int(out[k])
+        out['failed'] = int(w[7]) == self.FAILED
+        return out
+
+    def kinetic_energy(self):
+        """(host read) sum m v^2 / 2 of the velocities the last application left, in kJ/mol"""
+        return self.info()['k_after']
+
+    def temperature(self):
+        """(host read) 2 Ekin / (n_dof kB) of the velocities the last application left"""
+        return 2.0 * self.kinetic_energy() / (self.n_dof * KB)
+
+    def heat(self):
+        """(host read) the accumulated sum of (K after - K before) over the applications since reset(), in kJ/mol"""
+        return self.info()['heat']

@@ -7,6 +7,10 @@ launches what a step of nve_water.py launches, less the bonded kernel.  --fricti
 inner steps carry the Langevin thermostat at --temp with the noise of --seed.
 
     python examples/md/mts_water.py [--dt 2] [--inner 4] [--friction 0] [--seed 1] [the arguments of nve_water.py]
+                                    [--thermostat {langevin,vrescale}] [--tau-t 100]
+
+--thermostat vrescale keeps the friction at 0 and makes the closing outer half kick and stochastic velocity rescaling
+(admp_amd.md.VRescale) one C call per outer step; the log then carries the conserved quantity E_pot + E_kin - heat.
 
 The same minimisation, start velocities and summary line as nve_water.py, so the two can be compared run for run."""
 import argparse
@@ -18,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import KB, MASS, add_arguments, setup, minimize      # noqa: E402
+from water_md import KB, MASS, add_arguments, add_thermostat_arguments, drift_of, setup, minimize      # noqa: E402
 from admp_amd import settings                                      # noqa: E402
 
 
@@ -29,9 +33,12 @@ def main():
     ap.add_argument('--inner', type=int, default=4, help='inner steps on the bonded terms per outer step --dt')
     ap.add_argument('--friction', type=float, default=0.0, help='1/fs (0: constant energy)')
     ap.add_argument('--seed', type=int, default=1, help='of the thermostat\'s noise')
+    add_thermostat_arguments(ap)
     opt = ap.parse_args()
+    if opt.thermostat == 'vrescale' and opt.friction != 0.0:
+        ap.error('--thermostat vrescale runs at --friction 0')
     w = setup(opt)
-    from admp_amd.md import MTSLangevin
+    from admp_amd.md import MTSLangevin, VRescale
     n_mol, pos, mass, dt, dev, pme, bond, box = w.n_mol, w.pos, w.mass, w.dtype, 'cuda', w.pme, w.bond, w.box
     nbl, forces, epot_now, state = w.nbl, w.forces, w.epot_now, w.state
 
@@ -39,6 +46,7 @@ def main():
     vel = torch.randn(pos.shape, generator=g, device=dev, dtype=dt) * torch.sqrt(KB * opt.temp / mass) * 1e-2
     h = opt.dt
     mts = MTSLangevin(bond, np.tile(MASS, n_mol), h, opt.inner, opt.temp, opt.friction, opt.seed)
+    vr = opt.thermostat == 'vrescale' and VRescale(bond, np.tile(MASS, n_mol), h, opt.temp, opt.tau_t, opt.seed)
     pos, pairs, e123, grad = minimize(w, opt, pos)
     e123, grad = forces(pos, pairs, bonded=False)                      # the slow gradient: the calculators alone
     vel = vel.contiguous()
@@ -54,6 +62,13 @@ def main():
             nbl.prune(pos)
         e123, grad = forces(pos, pairs, bonded=False)
         rec = step % opt.log == 0 or step == opt.steps - 1
+        if vr:
+            vr.kick(vel, grad)                                         # v(t + h), then the thermostat: one call
+            if rec:
+                i = vr.info()
+                epot = epot_now(e123)
+                log.append((step, epot, i['k_after'], epot + i['k_after'] - i['heat'], i['heat']))
+            continue
         mts.kick(pos, vel, grad, want_ekin=rec)                        # v(t + h)
         if rec:
             epot, ekin = epot_now(e123), mts.kinetic_energy()          # (the bonded words are the kernel's, at the new positions)
@@ -61,8 +76,8 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     e0 = log[0][3]
-    for (s, ep, ek, et) in log:
-        print('step %5d  Epot %14.4f  Ekin %12.4f  Etot %14.4f  drift %+.3e' % (s, ep, ek, et, (et - e0) / abs(e0)))
+    for (s, ep, ek, et, *heat) in log:
+        print('step %5d  Epot %14.4f  Ekin %12.4f  %s %14.4f  drift %+.3e' % (s, ep, ek, 'conserved' if heat else 'Etot', et, (et - e0) / abs(e0)))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
         print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
@@ -73,7 +88,9 @@ def main():
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '
           'relative energy drift %.2e, T_final %.1f K; inner step %.3f fs (%d per outer step)'
           % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles', settings.PRECISION, h, wall / opt.steps * 1e3, ns_day,
-             opt.rebuild, (log[-1][3] - e0) / abs(e0), 2 * log[-1][2] / (3 * 3 * n_mol * KB), h / opt.inner, opt.inner))
+             opt.rebuild, (log[-1][3] - e0) / abs(e0), 2 * log[-1][2] / (3 * 3 * n_mol * KB), h / opt.inner, opt.inner)
+          + ('; velocity rescaling %.1f K, tau %g fs: conserved quantity drift %s, heat %+.4f kJ/mol'
+             % (opt.temp, opt.tau_t, drift_of(log, lambda r: r[3]), log[-1][4]) if vr else ''))
 
 
 if __name__ == '__main__':

@@ -10,6 +10,7 @@ the thermostat's generator): a run restarted at any step repeats it.
     python examples/md/npt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1]
                                     [--pressure 1] [--tau-p 1000] [--compress 4.5e-5] [--nbaro 10] [--pol] [--single] [--mesh K]
                                     [--molecular | --rigid [--bonds-only] [--tol T]]
+                                    [--thermostat {langevin,vrescale}] [--tau-t 100]
 
 The other arguments are those of nve_water.py.  Without --molecular or --rigid: isotropic scaling of the atoms only (one rank).
 --molecular: the same flexible water, but whole molecules are scaled about their centres of mass and the pressure is the
@@ -17,7 +18,10 @@ molecular one (admp_amd.md.MolecularCRescaleBarostat: admp_md_mol_sums, admp_md_
 rigid_water.py (constrained BAOAB, admp_amd.md.Constraints / ConstrainedLangevin; --bonds-only and --tol as there) under the
 molecular barostat, default --dt 2 with the lists rebuilt every 5 steps: a molecule moves rigidly in an application, so the
 constraints survive it without a re-projection -- the largest constraint error right after the application is logged with
-every record.
+every record.  --thermostat vrescale replaces the friction (then 0) by stochastic velocity rescaling (admp_amd.md.VRescale,
+relaxation time --tau-t), the thermostat the barostat was published with: the closing kick and the thermostat are one C call
+(--rigid: the thermostat follows the RATTLE kick).  The log then carries E_pot + E_kin - heat, which the thermostat conserves
+and only the barostat's work moves.
 """
 import argparse
 import os
@@ -28,7 +32,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import MASS, add_arguments, setup, minimize, rigid_start      # noqa: E402
+from water_md import MASS, add_arguments, add_thermostat_arguments, drift_of, setup, minimize, rigid_start      # noqa: E402
 from admp_amd import settings                                               # noqa: E402
 
 G_CM3_PER_AMU_A3 = 1.66053907      # 1 amu/A^3 in g/cm^3
@@ -49,7 +53,10 @@ def main():
     ap.add_argument('--tol', type=float, default=0.0, help='with --rigid: relative tolerance of the constraints (0: 1e-8 in double, '
                     '1e-6 in single)')
     ap.set_defaults(dt=None, rebuild=None)      # resolved below: they depend on --rigid
+    add_thermostat_arguments(ap)
     opt = ap.parse_args()
+    if opt.thermostat == 'vrescale':
+        opt.friction = 0.0
     if opt.dt is None:
         opt.dt = 2.0 if opt.rigid else 0.5
     if opt.rebuild is None:
@@ -61,7 +68,7 @@ def main():
     if (opt.bonds_only or opt.tol) and not opt.rigid:
         ap.error('--bonds-only and --tol belong to --rigid')
     w = setup(opt)
-    from admp_amd.md import CRescaleBarostat, Langevin, MolecularCRescaleBarostat, groups_of, maxwell_boltzmann
+    from admp_amd.md import CRescaleBarostat, Langevin, MolecularCRescaleBarostat, VRescale, groups_of, maxwell_boltzmann
     n_mol, pme, nbl, forces, epot_now, state, box = w.n_mol, w.pme, w.nbl, w.forces, w.epot_now, w.state, w.box
     masses = np.tile(MASS, n_mol)
     h = opt.dt
@@ -82,7 +89,9 @@ def main():
         else:
             baro = CRescaleBarostat(pme, masses, opt.nbaro * h, opt.temp, opt.pressure, opt.tau_p, opt.compress, opt.seed)
         pos, pairs, e123, grad = minimize(w, opt, w.pos)
-    log = []
+    vr = opt.thermostat == 'vrescale' and VRescale(con if opt.rigid else pme, masses, h, opt.temp, opt.tau_t, opt.seed,
+                                                   n_dof=rs.n_dof if opt.rigid else 3 * len(masses) - 3)
+    log, extra = [], []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for step in range(opt.steps):
@@ -98,7 +107,11 @@ def main():
         baro_now = (step + 1) % opt.nbaro == 0
         rec = baro_now and (step // opt.nbaro % max(opt.log // opt.nbaro, 1) == 0 or step + opt.nbaro >= opt.steps)
         if con is not None:
-            lv.kick(pos, vel, grad, box, want_ekin=rec)                # B, RATTLE: v(t + h)
+            lv.kick(pos, vel, grad, box, want_ekin=rec and not vr)     # B, RATTLE: v(t + h)
+            if vr:
+                vr.apply(vel)                                          # the thermostat: one factor for all velocities
+        elif vr:
+            vr.kick(vel, grad)                                         # B: v(t + h), then the thermostat: one call
         else:
             lv.kick(pos, vel, grad, want_ekin=rec)                     # B: v(t + h)
         if baro_now:
@@ -114,7 +127,10 @@ def main():
                 kin, rg, xi = baro.sums(pos, vel, grad)                # one launch, one host read
             p_inst = baro.pressure(box, dbox, kin, rg)
             if rec:
-                log.append((step, epot_now(e123), lv.temperature(), p_inst, abs(float(np.linalg.det(box)))))
+                log.append((step, epot_now(e123), vr.temperature() if vr else lv.temperature(), p_inst, abs(float(np.linalg.det(box)))))
+                if vr:
+                    i = vr.info()
+                    extra.append((step, log[-1][1], i['k_after'], i['heat']))
             baro.apply(pos, vel, box, p_inst, xi)                      # r, v and the cell (in place: the closures hold `box`)
             if rec and con is not None:                                # the constraints in the scaled cell, not re-projected
                 log[-1] += (constraint_error(pos),)
@@ -123,10 +139,11 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     m_tot = float(masses.sum())
-    for rec in log:
+    for k, rec in enumerate(log):
         (s, ep, tk, p, v) = rec[:5]
         print('step %5d  Epot %14.4f  T_kin %8.2f  P_inst %12.2f  V %14.4f  density %7.4f'
-              % (s, ep, tk, p, v, m_tot / v * G_CM3_PER_AMU_A3) + ('  constraints %.2e' % rec[5] if con is not None else ''))
+              % (s, ep, tk, p, v, m_tot / v * G_CM3_PER_AMU_A3) + ('  constraints %.2e' % rec[5] if con is not None else '')
+              + ('  Epot+Ekin-heat %14.4f' % (extra[k][1] + extra[k][2] - extra[k][3]) if vr else ''))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
         print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
@@ -141,6 +158,9 @@ def main():
               % (max(r[5] for r in log), constraint_error(pos), con.tolerance, con.max_sweeps_seen(), con.failures()))
     half = [r for r in log if r[0] >= opt.steps // 2]
     tk, pp, vv = (np.array([r[k] for r in half]) for k in (2, 3, 4))
+    if vr:
+        print('# velocity rescaling %.1f K, tau %g fs in place of the friction: E_pot + E_kin - heat moved by %s (the barostat\'s '
+              'work), heat %+.4f kJ/mol' % (opt.temp, opt.tau_t, drift_of(extra), extra[-1][3]))
     print('# %d waters, %s, %s, dt %.2f fs, Langevin %.1f K, friction %g /fs, seed %d, barostat %.1f bar, tau_p %g fs, every %d '
           'steps: over the second half T_kin mean %.1f K, P mean %.1f bar std %.1f bar, V mean %.2f A^3 std %.2f A^3 (%d records), '
           'V_final %.4f A^3; %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps and after each rescaling)'

@@ -9,8 +9,11 @@ is the kick of velocity Verlet.  The velocities start from a Maxwell-Boltzmann d
 
     python examples/md/nvt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1] [--pol]
                                     [--single] [--mesh K] [--log 10] [--prune M] [--predict k]
+                                    [--thermostat {langevin,vrescale}] [--tau-t 100]
 
-The other arguments are those of nve_water.py.
+--thermostat vrescale runs velocity Verlet (the same first-half kernel at friction 0) under stochastic velocity rescaling
+(admp_amd.md.VRescale, relaxation time --tau-t fs): the closing half kick and the thermostat are one C call, and the log gains
+the conserved quantity E_pot + E_kin - heat, whose drift the final line reports.  The other arguments are those of nve_water.py.
 """
 import argparse
 import os
@@ -21,7 +24,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import MASS, add_arguments, setup, minimize      # noqa: E402
+from water_md import MASS, add_arguments, add_thermostat_arguments, drift_of, setup, minimize      # noqa: E402
 from admp_amd import settings                                  # noqa: E402
 
 
@@ -30,15 +33,17 @@ def main():
     add_arguments(ap)
     ap.add_argument('--friction', type=float, default=0.05, help='1/fs')
     ap.add_argument('--seed', type=int, default=1, help='of the initial velocities and of the thermostat\'s noise')
+    add_thermostat_arguments(ap)
     opt = ap.parse_args()
     w = setup(opt)
-    from admp_amd.md import Langevin, maxwell_boltzmann
+    from admp_amd.md import Langevin, VRescale, maxwell_boltzmann
     n_mol, pme, nbl, forces, epot_now, state = w.n_mol, w.pme, w.nbl, w.forces, w.epot_now, w.state
     masses = np.tile(MASS, n_mol)
     h = opt.dt
     # units: A, fs, amu, kJ/mol
     vel = maxwell_boltzmann(pme, masses, opt.temp, opt.seed)
-    lv = Langevin(pme, masses, h, opt.temp, opt.friction, opt.seed)
+    vr = opt.thermostat == 'vrescale' and VRescale(pme, masses, h, opt.temp, opt.tau_t, opt.seed, n_dof=3 * len(masses) - 3)
+    lv = Langevin(pme, masses, h, opt.temp, 0.0 if vr else opt.friction, opt.seed)
     pos, pairs, e123, grad = minimize(w, opt, w.pos)
     log = []
     torch.cuda.synchronize()
@@ -51,18 +56,32 @@ def main():
             nbl.prune(pos)
         e123, grad = forces(pos, pairs)
         rec = step % opt.log == 0 or step == opt.steps - 1
+        if vr:
+            vr.kick(vel, grad)                                         # B: v(t + h), then the thermostat: one call
+            if rec:
+                i = vr.info()
+                log.append((step, epot_now(e123), i['k_after'], vr.temperature(), i['heat']))
+            continue
         lv.kick(pos, vel, grad, want_ekin=rec)                         # B: v(t + h)
         if rec:
             log.append((step, epot_now(e123), lv.kinetic_energy(), lv.temperature()))
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    for (s, ep, ek, tk) in log:
-        print('step %5d  Epot %14.4f  Ekin %12.4f  T_kin %8.2f' % (s, ep, ek, tk))
+    for (s, ep, ek, tk, *heat) in log:
+        print('step %5d  Epot %14.4f  Ekin %12.4f  T_kin %8.2f' % (s, ep, ek, tk)
+              + ('  conserved %14.4f' % (ep + ek - heat[0]) if heat else ''))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
         print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     tk = np.array([r[3] for r in log if r[0] >= opt.steps // 2])
+    if vr:
+        print('# %d waters, %s, %s, dt %.2f fs, velocity rescaling %.1f K, tau %g fs, seed %d: T_kin over the second half mean '
+              '%.1f K std %.1f K (%d records); conserved quantity drift %s; %.3f ms/step, %.2f ns/day (all terms, list rebuilt '
+              'every %d steps)'
+              % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles', settings.PRECISION, h, opt.temp, opt.tau_t, opt.seed,
+                 tk.mean(), tk.std(), len(tk), drift_of(log), wall / opt.steps * 1e3, ns_day, opt.rebuild))
+        return
     print('# %d waters, %s, %s, dt %.2f fs, Langevin %.1f K, friction %g /fs, seed %d: T_kin over the second half mean %.1f K '
           'std %.1f K (%d records); %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps)'
           % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles', settings.PRECISION, h, opt.temp, opt.friction, opt.seed,

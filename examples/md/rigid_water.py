@@ -8,6 +8,11 @@ nve_water.py launches, with the two half-step kernels replaced by the two constr
 the noise of --seed.  --bonds-only constrains the two O-H bonds only and keeps the harmonic angle (admp_amd.md.HarmonicBonded).
 
     python examples/md/rigid_water.py [--dt 2] [--bonds-only] [--friction 0] [--seed 1] [--tol T] [the arguments of nve_water.py]
+                                      [--thermostat {langevin,vrescale}] [--tau-t 100]
+
+--thermostat vrescale keeps the friction at 0 and applies stochastic velocity rescaling (admp_amd.md.VRescale over the constrained
+degrees of freedom) after the RATTLE kick of every step: one factor for all velocities leaves them on the constraints.  The log
+then carries the conserved quantity E_pot + E_kin - heat and the final line its drift.
 
 Start: the flexible minimisation of the other drivers, the positions projected onto the constraints, Maxwell-Boltzmann
 velocities projected likewise and rescaled to --temp over the constrained degrees of freedom."""
@@ -20,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from water_md import MASS, add_arguments, setup, rigid_start      # noqa: E402
+from water_md import MASS, add_arguments, add_thermostat_arguments, drift_of, setup, rigid_start      # noqa: E402
 from admp_amd import settings                                     # noqa: E402
 
 
@@ -32,7 +37,10 @@ def main():
     ap.add_argument('--friction', type=float, default=0.0, help='1/fs (0: constant energy)')
     ap.add_argument('--seed', type=int, default=1, help='of the start velocities and the thermostat\'s noise')
     ap.add_argument('--tol', type=float, default=0.0, help='relative tolerance of the constraints (0: 1e-8 in double, 1e-6 in single)')
+    add_thermostat_arguments(ap)
     opt = ap.parse_args()
+    if opt.thermostat == 'vrescale' and opt.friction != 0.0:
+        ap.error('--thermostat vrescale runs at --friction 0')
     w = setup(opt)
     n_mol, box = w.n_mol, w.box
     nbl, state, pme = w.nbl, w.state, w.pme
@@ -40,6 +48,10 @@ def main():
     con, integ, tol, gradient, epot_now, constraint_error = rs.con, rs.integ, rs.tol, rs.gradient, rs.epot_now, rs.constraint_error
     pos, vel, pairs_l, e123, grad = rs.pos, rs.vel, rs.pairs, rs.e123, rs.grad
     h = opt.dt
+    vr = None
+    if opt.thermostat == 'vrescale':
+        from admp_amd.md import VRescale
+        vr = VRescale(con, np.tile(MASS, n_mol), h, opt.temp, opt.tau_t, opt.seed, n_dof=rs.n_dof)
     log = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -51,15 +63,21 @@ def main():
             nbl.prune(pos)
         e123, grad = gradient(pos, pairs_l)
         rec = step % opt.log == 0 or step == opt.steps - 1
-        integ.kick(pos, vel, grad, box, want_ekin=rec)                     # B, RATTLE: one kernel
-        if rec:
+        integ.kick(pos, vel, grad, box, want_ekin=rec and not vr)          # B, RATTLE: one kernel
+        if vr:
+            vr.apply(vel)                                                  # the thermostat: sums, then one factor for all
+            if rec:
+                i = vr.info()
+                epot = epot_now(e123)
+                log.append((step, epot, i['k_after'], epot + i['k_after'] - i['heat'], vr.temperature(), constraint_error(pos), i['heat']))
+        elif rec:
             epot, ekin = epot_now(e123), integ.kinetic_energy()
             log.append((step, epot, ekin, epot + ekin, integ.temperature(), constraint_error(pos)))
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     e0 = log[0][3]
-    for (s, ep, ek, et, tk, ce) in log:
-        print('step %5d  Epot %14.4f  Ekin %12.4f  Etot %14.4f  drift %+.3e  T %7.2f  constraints %.2e' % (s, ep, ek, et, (et - e0) / abs(e0), tk, ce))
+    for (s, ep, ek, et, tk, ce, *heat) in log:
+        print('step %5d  Epot %14.4f  Ekin %12.4f  %s %14.4f  drift %+.3e  T %7.2f  constraints %.2e' % (s, ep, ek, 'conserved' if heat else 'Etot', et, (et - e0) / abs(e0), tk, ce))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
         print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
@@ -71,7 +89,9 @@ def main():
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '
           'relative energy drift %.2e, T_final %.1f K'
           % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles', settings.PRECISION, h, wall / opt.steps * 1e3, ns_day,
-             opt.rebuild, (log[-1][3] - e0) / abs(e0), log[-1][4]))
+             opt.rebuild, (log[-1][3] - e0) / abs(e0), log[-1][4])
+          + ('; velocity rescaling %.1f K, tau %g fs: conserved quantity drift %s, heat %+.4f kJ/mol'
+             % (opt.temp, opt.tau_t, drift_of(log, lambda r: r[3]), log[-1][6]) if vr else ''))
 
 
 if __name__ == '__main__':

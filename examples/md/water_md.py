@@ -55,6 +55,19 @@ def add_arguments(ap):
                     'tensor operations per step; at a tight threshold it saves one to two field evaluations per step')
 
 
+def add_thermostat_arguments(ap):
+    ap.add_argument('--thermostat', choices=('langevin', 'vrescale'), default='langevin', help='langevin: the friction and noise of '
+                    'the integrator (--friction); vrescale: stochastic velocity rescaling (admp_amd.md.VRescale) on the integrator at '
+                    'friction 0 -- one factor for all velocities per step, so diffusion and dipole dynamics are not damped')
+    ap.add_argument('--tau-t', type=float, default=100.0, help='fs: relaxation time of --thermostat vrescale')
+
+
+def drift_of(log, conserved=lambda r: r[1] + r[2] - r[-1]):
+    """'d kJ/mol over n steps' of the conserved quantity (E_pot + E_kin - heat of records (step, E_pot, E_kin, ..., heat)) between
+    the first and the last record"""
+    return '%+.4f kJ/mol over %d steps' % (conserved(log[-1]) - conserved(log[0]), log[-1][0] - log[0][0])
+
+
 def setup(opt):
     """calculators, lists and forces of the box of opt.waters molecules; returns a namespace with pos (device tensor), box,
     n_mol, dtype, pme (the calculator that lends its handle and stream to the integrator), nbl, forces, epot_now, state; for

@@ -397,6 +397,26 @@ int admp_set_pairs_from_positions(admp_handle* h, const void* positions, const d
  *                       launches nothing and copies the slot forward on the stream.  ADMP_E_ARG for a null pointer, n_atoms < 0,
  *                       dt_min, dt_max or max_step not finite and positive, dt_min > dt_max, f_inc < 1, f_dec, alpha_start or
  *                       f_alpha outside (0, 1], n_delay < 0, ftol negative or not finite -- and for a slab-decomposed handle.
+ *   admp_md_vrescale    one application of the stochastic velocity-rescaling thermostat (Bussi, Donadio, Parrinello 2007; the rule
+ *                       is csrc/md_vrescale_math.h) in two launches, its draw and its decision on the device, nothing read back.
+ *                       With grad != NULL the first launch makes the closing half kick of a step, v -= half_dt_acc grad inv_mass
+ *                       -- admp_md_kick_drift with dt = 0, bit for bit -- before it sums; grad = NULL is the thermostat alone.
+ *                       K = sum v^2 / inv_mass / 2 of those velocities is reduced in double on both precisions, without atomics
+ *                       (one double per workgroup, folded in a fixed order).  With c = exp(-dt / tau) and kT_acc = 1e-4 kB T:
+ *                       K' = (sqrt(c K) + sqrt((1 - c) kT_acc / 2) R1)^2 + (1 - c) (kT_acc / 2) S, R1 ~ N(0, 1), S ~ chi^2(n_dof
+ *                       - 1), both functions of (seed, step) alone on stream 3 of the generator (S through a gamma deviate by
+ *                       rejection, at most 64 tries); alpha = sqrt(K' / K), rounded to the handle's precision once; v *= alpha.
+ *                       K = 0 and c = 1 draw nothing: alpha = 1 exactly.  state16_dev (DEVICE, the caller's): two slots of 8
+ *                       doubles = K before, K after (= alpha^2 K with the rounded alpha), alpha, heat = the accumulated sum of
+ *                       (K after - K before), applications, tries of the last draw, 0, flags; the call reads slot call & 1 and
+ *                       writes slot (call + 1) & 1 in full, `call` being the caller's call counter.  A K or a factor that is not
+ *                       finite, or a draw out of tries, sets flag 1 (failed): nothing is scaled, in this call or any later one,
+ *                       and words 0-6 are carried over, until the caller writes a fresh state.  Energies in the internal unit
+ *                       (kJ/mol times 1e-4).  For a given n velocities and state are functions of the inputs alone, bit for bit.
+ *                       n_atoms = 0 launches nothing and copies the slot forward on the stream.  ADMP_E_ARG for a null
+ *                       state pointer, a null velocities or inv_mass pointer (unless n_atoms = 0: an empty device array has no
+ *                       address), n_atoms < 0, n_dof < 1, c outside [0, 1] or not finite, kT_acc negative or not finite,
+ *                       half_dt_acc not finite.
  * All but the first two set the handle's device, check their launch, and refuse slab-decomposed handles (ADMP_E_STATE;
  * admp_md_fire_step: ADMP_E_ARG); admp_md_bonded_box and all after it check every argument (n < 0 included) before anything is
  * launched. */
@@ -439,6 +459,9 @@ int admp_md_mol_scale(admp_handle* h, int n_atoms, void* positions, void* veloci
 int admp_md_mol_info(admp_handle* h, int64_t* out8);
 int admp_md_fire_step(admp_handle* h, int n_atoms, void* positions, void* velocities, const void* grad, const void* inv_mass,
                       const double* params9, double ftol, uint64_t call, double* state16_dev);
+int admp_md_vrescale(admp_handle* h, int n_atoms, void* velocities, const void* grad /* may be NULL: thermostat only */,
+                     const void* inv_mass, double half_dt_acc, int64_t n_dof, double kT_acc, double c, uint64_t seed, uint64_t step,
+                     uint64_t call, double* state16_dev);
 
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
