@@ -79,7 +79,10 @@ PROTOTYPES = {
     'admp_slab_configure': (_i32, [_vp, _i32, _i32]),
     'admp_slab_info': (_i32, [_vp, _c.POINTER(_i64)]),
     'admp_scf_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
-    'admp_xpass_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
+    'admp_scf_aspc': (_i32, [_vp, _i32, _i32, _dbl]),
+    'admp_scf_aspc_reset': (_i32, [_vp]),
+    'admp_scf_aspc_info': (_i32, [_vp, _c.POINTER(_i64), _dp]),
+    'admp_xpass_stats':(_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_plane_mfma_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_plane_mfma_stats4': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_mesh_convolve': (_i32, [_vp, _dp, _i32, _vp, _i32, _dp, _ip]),
@@ -127,6 +130,8 @@ class AdmpComm(_c.Structure):
 OPT_REFERENCE_KPOINTS = 1
 OPT_KEEP_POL_SITES = 2
 OPT_SIDE_STREAM = 3
+OPT_ASPC_HOLD = 4
+E_ARG, E_STATE = -1, -5
 RCCL_ID_BYTES, RCCL_NTAGS = 128, 8
 # admp_mesh_convolve: words of its info array, values of info[0]
 MESH_INFO_WORDS = 16

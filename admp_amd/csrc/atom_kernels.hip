@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kAtomBlock) void k_jacobi_delta(int n_act, const in
                                                              T* __restrict__ Ucart, Site<T>* __restrict__ sites,
                                                              Site<T>* __restrict__ isites,
                                                              const unsigned long long* __restrict__ gate,
-                                                             unsigned long long gate_bits) {
+                                                             unsigned long long gate_bits, T relax) {
   const int slot = blockIdx.x * kAtomBlock + threadIdx.x;
   if (slot >= n_act) return;
   const int i = act[slot];
@@ -137,7 +137,8 @@ __global__ __launch_bounds__(kAtomBlock) void k_jacobi_delta(int n_act, const in
   // that check passed (bit patterns of non-negative doubles order like the numbers) the step is a zero step: U keeps its
   // bits and every kernel of the increment that follows adds exact zeros
   const bool on = !gate || *gate >= gate_bits;
-  const T s = on ? -pol[i] * T(1.0 / kDielectric) : T(0);
+  // relax: the corrector's omega of a fixed-form call (scf_fixed, engine.hip); a factor 1 leaves the bits of s as they are
+  const T s = on ? -pol[i] * T(1.0 / kDielectric) * relax : T(0);
   const T dx = field[3 * i] * s, dy = field[3 * i + 1] * s, dz = field[3 * i + 2] * s;     // admp/pme.py:138
   Ucart[3 * i] += dx; Ucart[3 * i + 1] += dy; Ucart[3 * i + 2] += dz;
   Site<T> r = sites[i];
@@ -148,6 +149,19 @@ __global__ __launch_bounds__(kAtomBlock) void k_jacobi_delta(int n_act, const in
   for (int k = 0; k < 9; ++k) r.Q[k] = T(0);
   r.U[0] = dz; r.U[1] = dx; r.U[2] = dy;
   isites[slot] = r;
+}
+
+// Predictor of a fixed-form call (scf_aspc.h): out = sum_j B_j U(n-j) over the stored dipole sets in ring order, every
+// element accumulated in double from j = 1 upwards and rounded once; one coalesced pass over the n words of each set
+template <class T>
+__global__ __launch_bounds__(kAtomBlock) void k_aspc_predict(long n, AspcSets<T> h, T* __restrict__ out) {
+  const long i = (long)blockIdx.x * kAtomBlock + threadIdx.x;
+  if (i >= n) return;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < kAspcMaxSets; ++j)
+    if (j < h.n) acc += h.B[j] * (double)h.U[j][i];
+  out[i] = (T)acc;
 }
 
 // (Na,3,3) local frames, rows x, y, z (admp/spatial.py:76-142): the diagnostic behind ADMPPmeForce.construct_local_frames
@@ -715,11 +729,15 @@ void launch_field_finish(hipStream_t st, int na, const Site<T>* sites, const T* 
 }
 template <class T>
 void launch_jacobi_delta(hipStream_t st, int n_act, const int* act, const T* pol, const T* field, T* Ucart, Site<T>* sites,
-                         Site<T>* isites, const unsigned long long* gate, double gate_min) {
+                         Site<T>* isites, const unsigned long long* gate, double gate_min, double relax) {
   unsigned long long bits;
   std::memcpy(&bits, &gate_min, sizeof(bits));
   if (n_act > 0)
-    k_jacobi_delta<T><<<nblk(n_act), kAtomBlock, 0, st>>>(n_act, act, pol, field, Ucart, sites, isites, gate, bits);
+    k_jacobi_delta<T><<<nblk(n_act), kAtomBlock, 0, st>>>(n_act, act, pol, field, Ucart, sites, isites, gate, bits, (T)relax);
+}
+template <class T>
+void launch_aspc_predict(hipStream_t st, long n, const AspcSets<T>& h, T* out) {
+  if (n > 0) k_aspc_predict<T><<<(unsigned)((n + kAtomBlock - 1) / kAtomBlock), kAtomBlock, 0, st>>>(n, h, out);
 }
 template <class T>
 void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, const Site<T>* sites,
@@ -797,7 +815,8 @@ void launch_scale_add(hipStream_t st, int na, const T* vals, int stride, int cha
   template void launch_field_finish<T>(hipStream_t, int, const Site<T>*, const T*, const T*, const T*, const T*, T, T*,  \
                                        unsigned long long*, const int*, const int*);                                    \
   template void launch_jacobi_delta<T>(hipStream_t, int, const int*, const T*, const T*, T*, Site<T>*, Site<T>*,        \
-                                       const unsigned long long*, double);                                            \
+                                       const unsigned long long*, double, double);                                    \
+  template void launch_aspc_predict<T>(hipStream_t, long, const AspcSets<T>&, T*);                                      \
   template void launch_finish<T>(hipStream_t, const Topology&, const T*, const Box<T>&, const Site<T>*, const T*,        \
                                  const T*, int, T, T*, T*, T*, double*, const int*, int, const FieldFin<T>&, const int*);
 INST(float)

@@ -34,6 +34,7 @@
 #include "launch.h"
 #include "rccl_comm.h"
 #include "scf_policy.h"
+#include "scf_aspc.h"
 
 using namespace admp;
 
@@ -90,6 +91,15 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   int64_t plane_mfma_stats4[4] = {0, 0, 0, 0};
   // closing pair kernels of polarizable calls (admp_pair_rider_stats): [0] rode in an x pass, [1] launched on their own
   int64_t pair_rider_stats[2] = {0, 0};
+  // admp_scf_aspc: predictor-corrector dipoles for consecutive polarizable calls (scf_aspc.h).  The ring arithmetic lives
+  // here, the dipole sets themselves in the engine's device buffers.  aspc_calls: [0] calls that ran the fixed form,
+  // [1] warm-up calls, [2] fallback calls; aspc_resid: max|dE/dU| at the predicted dipoles of the last fixed-form call
+  AspcRing aspc;
+  int64_t aspc_calls[3] = {0, 0, 0};
+  double aspc_resid = 0.0;
+  int aspc_hold = 0;            // ADMP_OPT_ASPC_HOLD: the calls are not time steps, the history stays as it is
+  bool aspc_dirty = false;      // a copy into the ring's next slot has been enqueued and not yet counted
+  void aspc_off() { aspc.configure(-1, 1, 0.0); aspc_dirty = false; }
   const void* U_src = nullptr;  // admp_set_dipole_source: read-only initial dipoles of the NEXT polarizable evaluation
   const void* U_src_now = nullptr;   // ... taken over by that evaluation (Engine::pme), consumed by its site pass
   double cutoff = 0.0;          // admp_set_cutoff: listed pairs beyond it are skipped (0: every listed pair, as the reference)
@@ -298,6 +308,7 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   void set_topology(int na, const int32_t* atype, const int32_t* aidx, const int32_t* eptr, const int32_t* ecol,
                     const int32_t* enb) {
     ARG_CHECK(na > 0 && na <= kColMask, "n_atoms out of range");
+    aspc.drop();                // dipoles of another system
     free_topology();
     top.na = na;
     std::vector<int32_t> t5(na, NoAxisType), idx(3 * (size_t)na, -1);
@@ -552,6 +563,8 @@ struct Engine : EngineBase {
     ARG_CHECK(lmax_ >= 0 && lmax_ <= 2, "l > 2 (beyond quadrupole) not supported");   // admp/recip.py:275
     kappa = kappa_; K[0] = K1; K[1] = K2; K[2] = K3; lmax = lmax_; lpol = lpol_ ? 1 : 0;
     have_ewald = true;
+    aspc.drop();                // the stored dipoles belong to the old parameters
+    if (!lpol) aspc_off();
   }
 
   // ---- slab decomposition state (nranks == 1: the whole mesh is local) ---------------------------------
@@ -1493,6 +1506,9 @@ struct Engine : EngineBase {
     if (side) (void)hipStreamSynchronize(side);
     side_busy = false;
     ev.active = false;
+    // a set that was being written when the call failed may have replaced the oldest one: the history starts again.
+    // A call that failed before that leaves it unadvanced.
+    if (aspc_dirty) { aspc.drop(); aspc_dirty = false; }
   }
   // Order of submission around a fork: dispatch-bound systems (<= 16384 atoms) submit the side work AFTER the first kernel of
   // the main chain that follows (see recip_pass); larger ones first -- there the pair kernel is long and wants the early start.
@@ -1694,12 +1710,12 @@ struct Engine : EngineBase {
     *n_act = nact_known();
     return fmax;
   }
-  void scf_jacobi(int n_act, const unsigned long long* gate = nullptr, double gate_min = 0.0) {
+  void scf_jacobi(int n_act, const unsigned long long* gate = nullptr, double gate_min = 0.0, double relax = 1.0) {
     if (n_act > 0) {
       isites.need(sizeof(Site<T>) * (size_t)n_act);
       TIMED("jacobi_update");
       launch_jacobi_delta<T>(stream, n_act, act_list(), ev.pol, field.as<T>(), ev.U, sites.as<Site<T>>(),
-                             isites.as<Site<T>>(), gate, gate_min);
+                             isites.as<Site<T>>(), gate, gate_min, relax);
     }
     if (snranks > 1) exchange_U(1);       // every rank takes part, whatever its own count
   }
@@ -1742,9 +1758,11 @@ struct Engine : EngineBase {
   // phi with a field epilogue, which yields the same reciprocal field (and the residual) for every atom
   // full_grad: the closing pair kernel (gradient rows full_grad) may ride in this increment's x pass -- the dipoles are
   // final; returns whether it did
+  // no_field: nobody reads the field of the new dipoles (last corrector of a fixed-form call): phi alone is brought up to
+  // date, the real-space increment and the field gather are not run
   bool scf_increment(int n_act, unsigned long long* check_word = nullptr,   // fld_pair / fld_recip / phi <- their values for the dipoles after scf_jacobi
                      const std::function<void()>& extra_side = nullptr, bool field_from_total_phi = false,
-                     T* full_grad = nullptr) {
+                     T* full_grad = nullptr, bool no_field = false) {
     if (n_act <= 0 && snranks == 1) {
       if (extra_side) on_side(extra_side);
       return false;
@@ -1753,7 +1771,7 @@ struct Engine : EngineBase {
     PairFieldArgs<T> fr;   // (filled below, once the sub-table is current; it may ride in the x pass)
     bool ride = false;
     auto side_work = [&] {
-      if (!ride)
+      if (!ride && !no_field)
         on_side([&] {
           TIMED("pair_field_ind");
           launch_pair_field_ind<T>(stream, fr);
@@ -1768,7 +1786,7 @@ struct Engine : EngineBase {
       ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
     }
     fr = pair_field_ind_args(n_act);
-    ride = rider_ok() && field_rider<T>(fr);
+    ride = !no_field && rider_ok() && field_rider<T>(fr);
     if (first) side_work();
     const size_t nreal = nreal_local();
     mesh2.need(nreal * sizeof(T));
@@ -1791,7 +1809,7 @@ struct Engine : EngineBase {
     const bool added = convolve(mesh2.as<T>(), spec.as<T>(), gtab_cur, E_SCRATCH, mesh.as<T>(), nullptr, fused ? &sp : nullptr,
                                 ride ? &fr : nullptr, full_rides ? &pr : nullptr);
     join_side();
-    if (!field_from_total_phi) {
+    if (!field_from_total_phi && !no_field) {
       TIMED("gather_field_ind");
       launch_gather_field<T>(stream, n_act, isites.as<Site<T>>(), ev.g, mesh2.as<T>(), fld_recip.as<T>(), nullptr, 1, nullptr,
                              act_list(), check_word ? field_epilogue(check_word) : FieldFin<T>()); }
@@ -2008,6 +2026,70 @@ struct Engine : EngineBase {
       run.i = nhat + 1;
     }
   }
+  // Fixed form (admp_scf_aspc; scf_aspc.h): the call starts from the predictor's dipoles and takes a fixed number of relaxed
+  // Jacobi steps -- the chained form without its gates, its replay and its guesses.  First field evaluation, n_corrector
+  // times (step with factor omega, increment), the closing pass, all enqueued at once and read back with one
+  // synchronisation.  The residual at the predicted dipoles is what the first field finish leaves in E_FMAX.  Between two
+  // correctors the field finish needs a zero word for its maximum: the chain words of this evaluation's energy block
+  // serve as that, nobody reads them.  The field of the FINAL dipoles is read by nobody either (the closing pair kernel
+  // works from the sites, the closing gather from the accumulated phi), so the last increment updates phi alone.
+  void scf_fixed(ScfRun& run, const PmeIo& io) {
+    const int n_act = run.n_act = nact_known();
+    const int nc = aspc.n_corrector();
+    const double omega = aspc.omega();
+    recip_pass_first_field(E_SCF_RECIP);
+    next_check_word();
+    first_gather_field(field_epilogue(fmax_word()));
+    launch_field_check(fmax_word());
+    const bool early_full = overlap_ok();       // the closing pair kernel next to the last increment's mesh chain
+    bool full_rode = false;                     // ... or inside its x pass (pair_rider_ok(): never both)
+    for (int c = 0; c < nc; ++c) {
+      scf_jacobi(n_act, nullptr, 0.0, omega);
+      if (c < nc - 1) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(Ed_cur() + E_FMAX1 + c);
+        scf_increment(n_act, w);
+        launch_field_check(w);
+      } else if (early_full) {                  // (the dipoles are final now)
+        scf_increment(n_act, nullptr, [&] { stage_pair_full(io.gbuf); }, true, nullptr, true);
+      } else {
+        full_rode = scf_increment(n_act, nullptr, nullptr, true, io.gbuf, true);
+      }
+    }
+    if (!early_full && !full_rode) stage_pair_full(io.gbuf);
+    const FinishArgs<T> fin_c = finish_args(io.dpos != nullptr, io.dQl);
+    stage_gather(mesh.as<T>(), io.gbuf, nullptr, false, Ed_cur() + E_SLOTS, &fin_c);
+    launch_finish_only(io.dpos ? io.gbuf : nullptr, io.dQl);
+    read_energies(E_PARTS_SUM, io.E);
+    nact_seen();
+    aspc_resid = Eh[E_FMAX];
+    run.have_base = run.phi_accum = run.phi_valid = run.done = run.finished = true;
+    run.cyc = nc;
+    run.flag = 1;
+    ev.active = false;
+    scf_stats[7] += nc;
+    scf.forget();                               // the residuals of the other forms continue nothing across this call
+  }
+  // the predictor of a fixed-form or fallback call: U_p from the ring, in ring order; it becomes the call's dipole source
+  DevBuf aspc_set[kAspcMaxSets], aspc_pred;
+  void aspc_predict() {
+    const size_t n = 3 * (size_t)top.na;
+    AspcSets<T> h;
+    h.n = aspc.slots();
+    for (int j = 1; j <= h.n; ++j) { h.U[j - 1] = aspc_set[aspc.slot(j)].template as<T>(); h.B[j - 1] = aspc_coef(aspc.order(), j); }
+    aspc_pred.need(n * sizeof(T));
+    { TIMED("aspc_predict"); launch_aspc_predict<T>(stream, (long)n, h, aspc_pred.as<T>()); }
+    U_src_now = aspc_pred.p;
+  }
+  // the dipoles this call used for its forces join the history: one copy on the stream, no host round trip
+  void aspc_store(const T* U) {
+    const size_t bytes = 3 * (size_t)top.na * sizeof(T);
+    DevBuf& slot = aspc_set[aspc.next_slot()];
+    slot.need(bytes);                           // (grows only after set_topology, which has dropped the history)
+    aspc_dirty = true;
+    HIP_TRY(hipMemcpyAsync(slot.p, U, bytes, hipMemcpyDeviceToDevice, stream));
+    aspc.push();
+    aspc_dirty = false;
+  }
   // Steady-state MD regime (the previous call converged at its first check): evaluate the FIRST SCF cycle
   // with the full kernels -- they produce dE/dU alongside the gradient -- so that, when the check passes
   // again, the step is already finished (no separate field kernels, no second pass).  Same arithmetic and
@@ -2084,9 +2166,17 @@ struct Engine : EngineBase {
            const double* mS, const double* pS, void* U_, int max_cycle, double thresh, double* E, void* dpos_,
            void* dQl_, int* ncyc, int* conv, int on_device) override {
     const PmeIo io = stage_pme_io(pos_, box, Ql_, pol_, thole_, U_, E, dpos_, dQl_, on_device);
+    // admp_scf_aspc with a full history: the call starts from the predicted dipoles, whatever the caller passed
+    const bool aspc_on = lpol && aspc.on() && !aspc_hold && snranks == 1;
+    const bool predicted = aspc_on && aspc.full() && max_cycle >= 1 && have_top && have_ewald && have_pairs;
+    if (predicted) aspc_predict();
     stage_begin(io.pos, box, io.Ql, io.pol, io.thole, ns, mS, pS, io.U);
     ScfRun run;
-    if (lpol) {
+    // the fixed form needs the polarizable rows on the host (can_chain of scf.plan); otherwise the ordinary SCF from U_p
+    const bool fixed = predicted && !act_fresh && act_n > 0;
+    if (lpol && fixed) {
+      scf_fixed(run, io);
+    } else if (lpol) {
       ARG_CHECK(max_cycle >= 1, "max_cycle must be >= 1");
       // which form of the first cycle: ADMP_SPECULATE=0 / 1 forces the plain / the speculative one (A/B, tests)
       static const ScfSwitches sw = {env_int("ADMP_SPECULATE", -1), env_int("ADMP_SCF_CHAIN_MAX", 200000)};
@@ -2102,6 +2192,10 @@ struct Engine : EngineBase {
       scf.observe(run.f_first, run.f_final, run.cyc);
     }
     closing_pass(run, io);
+    if (aspc_on) {
+      aspc_store(io.U);
+      ++aspc_calls[fixed ? 0 : (predicted ? 2 : 1)];
+    }
     unstage_pme_io(io, U_, dpos_, dQl_, on_device);
     if (ncyc) *ncyc = run.cyc;
     if (conv) *conv = run.flag;
@@ -3373,6 +3467,7 @@ int admp_set_option(admp_handle* h, int option, int value) {
       case ADMP_OPT_REFERENCE_KPOINTS: e.ref_korder = value ? 1 : 0; break;
       case ADMP_OPT_KEEP_POL_SITES: e.keep_pol_sites = value ? 1 : 0; break;
       case ADMP_OPT_SIDE_STREAM: e.side_stream_on = value ? 1 : 0; break;
+      case ADMP_OPT_ASPC_HOLD: e.aspc_hold = value ? 1 : 0; break;
       default: throw Err{ADMP_E_ARG, "unknown option"};
     }
   });
@@ -3439,6 +3534,7 @@ int admp_slab_configure(admp_handle* h, int rank, int nranks) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(nranks >= 1 && nranks <= kSlabMaxRanks && rank >= 0 && rank < nranks, "bad rank / nranks (at most 28 ranks)");
     e.srank = rank; e.snranks = nranks;
+    if (nranks > 1) e.aspc_off();      // (the fixed form is a single-rank form)
   });
 }
 int admp_slab_info(admp_handle* h, int64_t* out11) {
@@ -3459,6 +3555,7 @@ int admp_set_comm_rccl(admp_handle* h, admp_rccl* c) {
     ARG_CHECK(rccl_nranks(c) <= kSlabMaxRanks, "at most 28 slab ranks");
     e.rccl = c;
     e.srank = rccl_rank(c); e.snranks = rccl_nranks(c);
+    if (e.snranks > 1) e.aspc_off();
     e.have_comm = true;
   });
 }
@@ -3469,6 +3566,32 @@ int admp_set_cutoff(admp_handle* h, double rc) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(rc >= 0.0, "negative cutoff");
     e.cutoff = rc;
+  });
+}
+int admp_scf_aspc(admp_handle* h, int order, int n_corrector, double omega) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(aspc_args_ok(order, n_corrector, omega),
+              "order must be -1 (off) or 0..4, n_corrector 1..6, omega <= 0 (Kolafa's value) or in (0, 1]");
+    if (order >= 0) {
+      if (!e.have_ewald || !e.lpol) throw Err{ADMP_E_STATE, "admp_scf_aspc needs a polarizable handle (admp_set_ewald with lpol)"};
+      if (e.snranks > 1) throw Err{ADMP_E_STATE, "admp_scf_aspc: not on a slab-decomposed handle"};
+    }
+    e.aspc.configure(order, n_corrector, omega);
+    e.aspc_dirty = false;
+    for (int64_t& c : e.aspc_calls) c = 0;
+    e.aspc_resid = 0.0;
+  });
+}
+int admp_scf_aspc_reset(admp_handle* h) {
+  return guarded(h, [&](EngineBase& e) { e.aspc.drop(); });
+}
+int admp_scf_aspc_info(admp_handle* h, int64_t* out8, double* out2) {
+  return guarded(h, [&](EngineBase& e) {
+    ARG_CHECK(out8 && out2, "null");
+    out8[0] = e.aspc.order(); out8[1] = e.aspc.on() ? e.aspc.n_corrector() : 0; out8[2] = e.aspc.count();
+    for (int k = 0; k < 3; ++k) out8[3 + k] = e.aspc_calls[k];
+    out8[6] = out8[7] = 0;
+    out2[0] = e.aspc.omega(); out2[1] = e.aspc_resid;
   });
 }
 int admp_scf_stats(admp_handle* h, int64_t* out8, int reset) {

@@ -14,6 +14,7 @@
 #include "mts_plan.h"
 #include "pfa_maps.h"
 #include "pme_math.h"
+#include "scf_aspc.h"
 #include "spline_math.h"
 
 namespace admp {
@@ -166,7 +167,18 @@ void launch_field_finish(hipStream_t st, int na, const Site<T>* sites, const T* 
 template <class T>
 void launch_jacobi_delta(hipStream_t st, int n_act, const int* act, const T* pol, const T* field, T* Ucart, Site<T>* sites,
                          Site<T>* isites, const unsigned long long* gate = nullptr /* device word: bit pattern of the residual */,
-                         double gate_min = 0.0 /* with gate: a zero step unless residual >= gate_min */);
+                         double gate_min = 0.0 /* with gate: a zero step unless residual >= gate_min */,
+                         double relax = 1.0 /* factor on the step: the corrector's omega of a fixed-form call */);
+// the predictor of a fixed-form call: out[i] = sum_{j < n} B[j] U[j][i] over `n_words` words, U[j] = the dipoles of j + 1
+// calls ago (scf_aspc.h); accumulated in double, rounded once
+template <class T>
+struct AspcSets {
+  int n = 0;
+  const T* U[kAspcMaxSets] = {};
+  double B[kAspcMaxSets] = {};
+};
+template <class T>
+void launch_aspc_predict(hipStream_t st, long n_words, const AspcSets<T>& h, T* out);
 // self term + polarization penalty energies, self potential, local-frame adjoint, dE/dQ_local
 template <class T>
 void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, const Site<T>* sites,

@@ -14,6 +14,7 @@ Differences a caller can see: arrays may be numpy or torch (results come back in
 `positions`); covalent_map may also be a scipy sparse matrix (mandatory beyond ~50k atoms); the x/y k-column
 quirk of the reference (admp/recip.py:339-340) is not emulated, see DESIGN.md.
 """
+import contextlib
 import ctypes
 import math
 import warnings
@@ -338,7 +339,8 @@ class ADMPPmeForce(HipForceBase):
         the polarization penalty D |U|^2 / (2 alpha) (admp/pme.py:760-774).  Sites with pol <= 1e-8 get 0 for dE/dpol."""
         if not self.lpol:
             raise RuntimeError('get_pol_thole_gradients needs lpol=True')
-        self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=U_init)
+        with self._not_a_step():
+            self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=U_init)
         with self._on_stream():
             na = self.n_atoms
             pos = self._real(positions, (na, 3))
@@ -369,8 +371,9 @@ class ADMPPmeForce(HipForceBase):
         na = self.n_atoms
         if self.lpol:
             pol, tholes, mScales, pScales, dScales = rest
-            self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales,
-                            U_init=kw.get('U_init'))
+            with self._not_a_step():
+                self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales,
+                                U_init=kw.get('U_init'))
         else:
             (mScales,) = rest
             pol = tholes = pScales = None
@@ -401,7 +404,8 @@ class ADMPPmeForce(HipForceBase):
         dE/ddScales is identically zero (the reference ignores dScales: uscales = 1, pme.py:472)."""
         if not self.lpol:
             raise RuntimeError('get_pscale_gradient needs lpol=True')
-        self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=U_init)
+        with self._not_a_step():
+            self.get_energy(positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=U_init)
         self._use_current_stream()
         na = self.n_atoms
         pos = self._real(positions, (na, 3))
@@ -421,6 +425,53 @@ class ADMPPmeForce(HipForceBase):
         (examples/openmm_api/run.py:44-46).  The energy is linear in mScales and its induced part carries pScales, so neither
         the values of mScales nor the induced dipoles enter."""
         return self._mscale_gradient(0, positions, box, pairs, self._pad_Q(Q_local), 9, len(self._host64(mScales)))
+
+    # ---- predictor-corrector dipoles for molecular dynamics (admp_scf_aspc) ---------------------------------------------
+    def set_aspc(self, order=2, n_corrector=1, omega=None):
+        """Always-stable predictor-corrector dipoles (Kolafa 2004) instead of an SCF to a threshold.  While the mode is on,
+        EVERY polarizable `get_forces` or `get_energy` (or `get_forces_and_dQ`, `optimize_Uind`) of this object is a time
+        step: the first order + 2 of them run as before and fill the history (warm-up); every later one starts from the
+        polynomial extrapolation of the last order + 2 dipole sets and takes `n_corrector` Jacobi steps damped by `omega`
+        (None: Kolafa's (order + 2) / (2 order + 3)) -- 1 + n_corrector field evaluations, no residual check, one host
+        synchronisation.  `U_init`, POL_CONV and MAX_N_POL are then ignored; `n_cycle` and `lconverg` report what the library
+        returned (n_corrector, True).  `set_aspc(None)` switches the mode off; any call drops the history, and so does
+        `update_env`.  Call `reset_aspc()` after positions jump.  The box and parameter gradients converge their own dipoles
+        and are not time steps.  ValueError for order outside 0..4, n_corrector outside 1..6, omega outside (0, 1]."""
+        if not self.lpol:
+            raise RuntimeError('set_aspc needs lpol=True')
+        if order is None:
+            order, n_corrector, omega = -1, 1, None
+        if isinstance(order, bool) or isinstance(n_corrector, bool) or int(order) != order or int(n_corrector) != n_corrector:
+            raise ValueError('set_aspc: order and n_corrector must be integers')
+        if omega is not None and not (0.0 < float(omega) <= 1.0):      # (a NaN fails both comparisons)
+            raise ValueError('set_aspc: omega must lie in (0, 1], got %r' % (omega,))
+        rc = self._L.admp_scf_aspc(self._h, int(order), int(n_corrector), 0.0 if omega is None else float(omega))
+        if rc == _lib.E_ARG:
+            raise ValueError('set_aspc: ' + self._L.admp_last_error(self._h).decode())
+        _lib.check(self._h, rc, 'admp_scf_aspc')
+
+    def reset_aspc(self):
+        """Keep the mode of `set_aspc`, drop the stored dipoles: the next order + 2 calls warm up again."""
+        _lib.check(self._h, self._L.admp_scf_aspc_reset(self._h), 'admp_scf_aspc_reset')
+
+    def aspc_info(self):
+        """State of `set_aspc` (admp_scf_aspc_info): order (-1: off), n_corrector, omega, stored dipole sets, calls that ran
+        the fixed form / warmed up / fell back to the ordinary SCF from the predicted dipoles, and max|dE/dU| at the
+        predicted dipoles of the last fixed-form call."""
+        out8, out2 = (ctypes.c_int64 * 8)(), (ctypes.c_double * 2)()
+        _lib.check(self._h, self._L.admp_scf_aspc_info(self._h, out8, out2), 'admp_scf_aspc_info')
+        return {'order': int(out8[0]), 'n_corrector': int(out8[1]), 'stored': int(out8[2]), 'fixed': int(out8[3]),
+                'warmup': int(out8[4]), 'fallback': int(out8[5]), 'omega': float(out2[0]), 'residual': float(out2[1])}
+
+    @contextlib.contextmanager
+    def _not_a_step(self):
+        """ADMP_OPT_ASPC_HOLD around an evaluation that only converges the dipoles for a box or parameter gradient"""
+        opt = self._L.admp_set_option
+        _lib.check(self._h, opt(self._h, _lib.OPT_ASPC_HOLD, 1), 'admp_set_option')
+        try:
+            yield
+        finally:
+            _lib.check(self._h, opt(self._h, _lib.OPT_ASPC_HOLD, 0), 'admp_set_option')
 
     def scf_stats(self, reset=False):
         """How the polarizable calls were enqueued and what wrong guesses cost (admp_scf_stats): dict of counters."""

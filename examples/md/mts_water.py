@@ -48,6 +48,7 @@ def main():
     mts = MTSLangevin(bond, np.tile(MASS, n_mol), h, opt.inner, opt.temp, opt.friction, opt.seed)
     vr = opt.thermostat == 'vrescale' and VRescale(bond, np.tile(MASS, n_mol), h, opt.temp, opt.tau_t, opt.seed)
     pos, pairs, e123, grad = minimize(w, opt, pos)
+    w.start_aspc()                                                     # --aspc: every polarizable call is a time step from here
     e123, grad = forces(pos, pairs, bonded=False)                      # the slow gradient: the calculators alone
     vel = vel.contiguous()
     log = []
@@ -80,7 +81,7 @@ def main():
         print('step %5d  Epot %14.4f  Ekin %12.4f  %s %14.4f  drift %+.3e' % (s, ep, ek, 'conserved' if heat else 'Etot', et, (et - e0) / abs(e0)))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
-        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     info = mts.plan_info()
     print('# multiple time steps: %d tiles of at most %d atoms, %d B of LDS per workgroup' % (info['tiles'], info['tile_atoms'],

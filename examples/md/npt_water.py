@@ -89,6 +89,7 @@ def main():
         else:
             baro = CRescaleBarostat(pme, masses, opt.nbaro * h, opt.temp, opt.pressure, opt.tau_p, opt.compress, opt.seed)
         pos, pairs, e123, grad = minimize(w, opt, w.pos)
+    w.start_aspc()                                                     # --aspc: every polarizable call is a time step from here
     vr = opt.thermostat == 'vrescale' and VRescale(con if opt.rigid else pme, masses, h, opt.temp, opt.tau_t, opt.seed,
                                                    n_dof=rs.n_dof if opt.rigid else 3 * len(masses) - 3)
     log, extra = [], []
@@ -135,6 +136,7 @@ def main():
             if rec and con is not None:                                # the constraints in the scaled cell, not re-projected
                 log[-1] += (constraint_error(pos),)
             pairs = nbl.allocate(pos)
+            w.aspc_jump()                                              # --aspc: the scaled configuration starts a new history
             e123, grad = forces(pos, pairs)                            # the next kick takes the scaled configuration's gradients
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
@@ -146,7 +148,7 @@ def main():
               + ('  Epot+Ekin-heat %14.4f' % (extra[k][1] + extra[k][2] - extra[k][3]) if vr else ''))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
-        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     if con is not None or opt.molecular:
         info = baro.plan_info()

@@ -8,7 +8,7 @@ energies) and the achieved ns/day including neighbour rebuilds.  Per step the ho
 themselves do (each returns its energy as a number, like the reference's get_forces); the bonded and kinetic energies
 stay on the device until a line is logged.
 
-    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict]
+    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]]
 
 --mesh K: K1 = K2 = K3 = K instead of the reference's rule (admp/pme.py:146-172), e.g. 128 for the 98 304-atom box of
 BASELINE configs[2] (the rule gives 305 = 5 * 61 there: every convolution then runs on the two-level DFT kernels, 0.7 ms
@@ -42,6 +42,7 @@ def main():
     h = opt.dt
     vv = VelocityVerlet(pme, np.tile(MASS, n_mol), h)
     pos, pairs, e123, grad = minimize(w, opt, pos)
+    w.start_aspc()                                                     # --aspc: every polarizable call is a time step from here
     vel = vel.contiguous()
     log = []
     torch.cuda.synchronize()
@@ -65,7 +66,7 @@ def main():
         print('step %5d  Epot %14.4f  Ekin %12.4f  Etot %14.4f  drift %+.3e' % (s, ep, ek, et, (et - e0) / abs(e0)))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
-        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('\n'.join(w.scf_lines()))
         # which form the library chose for every polarizable call (residual history, engine.hip pme()) and what wrong guesses cost
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '

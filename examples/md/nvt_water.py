@@ -8,7 +8,7 @@ is the kick of velocity Verlet.  The velocities start from a Maxwell-Boltzmann d
 (friction * time of a few units) it fluctuates around --temp with the relative width sqrt(2 / 3N).
 
     python examples/md/nvt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1] [--pol]
-                                    [--single] [--mesh K] [--log 10] [--prune M] [--predict k]
+                                    [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]]
                                     [--thermostat {langevin,vrescale}] [--tau-t 100]
 
 --thermostat vrescale runs velocity Verlet (the same first-half kernel at friction 0) under stochastic velocity rescaling
@@ -45,6 +45,7 @@ def main():
     vr = opt.thermostat == 'vrescale' and VRescale(pme, masses, h, opt.temp, opt.tau_t, opt.seed, n_dof=3 * len(masses) - 3)
     lv = Langevin(pme, masses, h, opt.temp, 0.0 if vr else opt.friction, opt.seed)
     pos, pairs, e123, grad = minimize(w, opt, w.pos)
+    w.start_aspc()                                                     # --aspc: every polarizable call is a time step from here
     log = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -72,7 +73,7 @@ def main():
               + ('  conserved %14.4f' % (ep + ek - heat[0]) if heat else ''))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
-        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     tk = np.array([r[3] for r in log if r[0] >= opt.steps // 2])
     if vr:

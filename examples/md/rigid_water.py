@@ -47,6 +47,7 @@ def main():
     rs = rigid_start(w, opt, np.tile(MASS, n_mol))      # constraints, integrator, gradient closure; the start on the constraints
     con, integ, tol, gradient, epot_now, constraint_error = rs.con, rs.integ, rs.tol, rs.gradient, rs.epot_now, rs.constraint_error
     pos, vel, pairs_l, e123, grad = rs.pos, rs.vel, rs.pairs, rs.e123, rs.grad
+    w.start_aspc()                                                     # --aspc: every polarizable call is a time step from here
     h = opt.dt
     vr = None
     if opt.thermostat == 'vrescale':
@@ -80,7 +81,7 @@ def main():
         print('step %5d  Epot %14.4f  Ekin %12.4f  %s %14.4f  drift %+.3e  T %7.2f  constraints %.2e' % (s, ep, ek, 'conserved' if heat else 'Etot', et, (et - e0) / abs(e0), tk, ce))
     ns_day = opt.steps * h * 1e-6 / wall * 86400.0
     if opt.pol:
-        print('# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / state['n']))
+        print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
     info = con.plan_info()
     print('# constraints: %d tiles of at most %d atoms, %d B of LDS per workgroup, most sweeps of a cluster %d; '

@@ -50,7 +50,13 @@ def add_arguments(ap):
     ap.add_argument('--mesh', type=int, default=0, help='PME mesh size per dimension (0: the reference rule)')
     ap.add_argument('--log', type=int, default=10, help='steps between energy records (each costs two host reads)')
     ap.add_argument('--thresh', type=float, default=1e-2, help='SCF threshold of --pol (the reference default 10 does not conserve energy)')
-    ap.add_argument('--predict', type=int, default=0, choices=(0, 1, 2, 3), help='start the SCF from a polynomial predictor over the last k + 1 '
+    start = ap.add_mutually_exclusive_group()
+    start.add_argument('--aspc', type=int, default=-1, choices=(0, 1, 2, 3, 4), metavar='K', help='always-stable predictor-corrector dipoles '
+                       'of order K in the library (ADMPPmeForce.set_aspc, switched on after the minimiser): after K + 2 warm-up steps '
+                       'every step is the predictor and --aspc-corr damped Jacobi steps, 1 + --aspc-corr field evaluations, no SCF to '
+                       '--thresh and no residual read')
+    ap.add_argument('--aspc-corr', type=int, default=1, metavar='N', help='corrector steps of --aspc (1: Kolafa\'s scheme)')
+    start.add_argument('--predict', type=int, default=0, choices=(0, 1, 2, 3), help='start the SCF from a polynomial predictor over the last k + 1 '
                     'converged dipoles (Kolafa\'s always-stable predictor coefficients: k = 1 is 2 U(n-1) - U(n-2)) instead of U(n-1): a few '
                     'tensor operations per step; at a tight threshold it saves one to two field evaluations per step')
 
@@ -148,6 +154,11 @@ def setup(opt):
                 del hist[:-(opt.predict + 1)]
             state['cyc'] = state.get('cyc', 0) + pme.n_cycle + 1
             state['n'] = state.get('n', 0) + 1
+            if state.get('aspc_on'):      # the steps after the warm-up are counted on their own
+                state['aspc_calls'] += 1
+                if state['aspc_calls'] > opt.aspc + 2:
+                    state['aspc_cyc'] += pme.n_cycle + 1
+                    state['aspc_n'] += 1
         else:
             e1, g = pme.get_forces(p, box, pairs, Q, mS)
         e2, g2 = disp.get_forces(p, box, pairs, cl, mS)
@@ -173,9 +184,34 @@ def setup(opt):
         d = d + tt_obj.get_energy_and_box_gradient(p, box, pairs, mS, a_, b_, q_, c6)[1]
         return d + bond.get_energy_and_box_gradient(p, box)[1] if bonded else d
 
+    def start_aspc():
+        """--aspc: switched on once the minimiser is done (every polarizable call is a time step from here on)"""
+        if not opt.pol or opt.aspc < 0:
+            return
+        pme.set_aspc(opt.aspc, opt.aspc_corr)
+        state.update(aspc_on=True, aspc_calls=0, aspc_cyc=0, aspc_n=0, cyc=0, n=0)
+
+    def aspc_jump():
+        """after anything that moves atoms discontinuously: the stored dipoles say nothing about the next step"""
+        if state.get('aspc_on'):
+            pme.reset_aspc()
+            state['aspc_calls'] = 0
+
+    def scf_lines():
+        """the lines a --pol run prints about its SCF"""
+        out = ['# mean SCF cycles per evaluation (thresh %g): %.1f' % (settings.POL_CONV, state['cyc'] / max(state['n'], 1))]
+        if state.get('aspc_on'):
+            i = pme.aspc_info()
+            out.append('# ASPC order %d, %d corrector step(s), omega %.4f: %.2f field evaluations per step after the warm-up '
+                       '(%d fixed-form, %d warm-up, %d fallback calls; residual at the last predicted dipoles %.3e)'
+                       % (i['order'], i['n_corrector'], i['omega'], state['aspc_cyc'] / max(state['aspc_n'], 1), i['fixed'],
+                          i['warmup'], i['fallback'], i['residual']))
+        return out
+
     par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
-                                 forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient)
+                                 forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient,
+                                 start_aspc=start_aspc, aspc_jump=aspc_jump, scf_lines=scf_lines)
 
 
 def minimize_fire(w, opt, pos, gradient=None, epot=None, constraints=None, label='minimize'):

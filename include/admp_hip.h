@@ -73,10 +73,14 @@ enum {
                                       following admp_pme_energy_grad calls is the one of the previous call (the values may
                                       change); the library then keeps its list of those sites instead of rebuilding it in
                                       every call.  Default 0 (rebuild every call).  Speed only, never results. */
-  ADMP_OPT_SIDE_STREAM = 3         /* value 0: every kernel of a call runs on the handle's stream.  Default 1: on systems up to
+  ADMP_OPT_SIDE_STREAM = 3,        /* value 0: every kernel of a call runs on the handle's stream.  Default 1: on systems up to
                                       200 000 atoms the real-space pair kernels run on a second stream next to the mesh chain
                                       of the same call.  Speed only; switched off by measurements that bracket single kernels
                                       with events (the event time of a kernel that shares the chip is not its duration). */
+  ADMP_OPT_ASPC_HOLD = 4           /* value 1: while admp_scf_aspc is on, the following admp_pme_energy_grad calls are NOT time
+                                      steps: they run as without the mode and leave its history alone (a wrapper that
+                                      converges the dipoles ahead of a box or parameter gradient sets it around that call).
+                                      Default 0. */
 };
 int admp_set_option(admp_handle* h, int option, int value);
 
@@ -554,6 +558,34 @@ int admp_slab_lists(admp_handle* h, int n_atoms, int nranks, int32_t* owner, int
  * that needed more steps than enqueued, chained calls that enqueued more than needed, field increments that ran for nothing
  * in those, Jacobi steps in total}; reset != 0 clears the counters.  The results never depend on the form. */
 int admp_scf_stats(admp_handle* h, int64_t* out8, int reset);
+
+/* Always-stable predictor-corrector dipoles (J. Kolafa, J. Comput. Chem. 25, 335, 2004) for molecular dynamics: while the
+ * mode is on, EVERY polarizable admp_pme_energy_grad of this handle counts as one time step.  With order k the handle keeps
+ * the dipoles U(n-1) .. U(n-k-2) that its last k + 2 such calls used for their forces (a ring of device arrays of the
+ * handle's precision) and a call runs the fixed form:
+ *     U_p = sum_{j=1..k+2} B_j U(n-j),   B_j = (-1)^(j+1) j C(2k+4, k+2-j) / C(2k+2, k+1)
+ *     n_corrector times:  U <- U - omega pol (dE/dU at U) / DIELECTRIC          (first from U = U_p)
+ *     energies, gradient and dE/dQ_local at U; U joins the history and is returned in U_inout
+ * That is 1 + n_corrector field evaluations (the later ones incremental), no residual read and one host synchronisation.
+ * The call ignores U_inout's initial values, admp_set_dipole_source, thresh and max_cycle (max_cycle >= 1 is still asked
+ * for) and reports n_cycle = n_corrector, converged = 1.
+ *   order        -1 turns the mode off (the default) and drops the history; 0..4 turns it on
+ *   n_corrector  1 .. 6
+ *   omega        <= 0: Kolafa's (k + 2) / (2k + 3); otherwise 0 < omega <= 1.  n_corrector > 1 with omega = 1 is n plain
+ *                Jacobi steps from U_p.
+ * Anything else (a NaN included) is ADMP_E_ARG; a non-polarizable or slab-decomposed handle ADMP_E_STATE.  Every accepted
+ * call drops the history and clears the counters; configuring the handle as a slab afterwards turns the mode off.
+ * While fewer than k + 2 sets are stored a call runs exactly as without the mode and its final dipoles are stored (warm-up).
+ * A call whose polarizable rows the host does not know yet starts from U_p and runs the ordinary SCF to the caller's
+ * threshold (fallback); its result is stored as well.  admp_set_topology and admp_set_ewald drop the history; a failed call
+ * leaves it unadvanced or drops it.  Only admp_pme_energy_grad advances it: the fixed-dipole, box-gradient, parameter-gradient
+ * and diagnostic entries do not touch it.
+ * admp_scf_aspc_reset keeps the mode and drops the history: for a driver whose positions have just jumped.
+ * admp_scf_aspc_info: out8 = {order, n_corrector, stored sets, fixed-form calls, warm-up calls, fallback calls, 0, 0},
+ * out2 = {omega in effect, max|dE/dU| at the predicted dipoles of the last fixed-form call (it comes back with the energies)}. */
+int admp_scf_aspc(admp_handle* h, int order, int n_corrector, double omega);
+int admp_scf_aspc_reset(admp_handle* h);
+int admp_scf_aspc_info(admp_handle* h, int64_t* out8, double* out2);
 /* Which form the x passes of the direct-DFT mesh convolution took: out2 = {one real circulant product per line (G table
  * even along x: orthorhombic cells; ADMP_DFT_XCIRC=0 turns it off), forward transform * G * inverse transform}. */
 int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset);
