@@ -29,6 +29,7 @@
 #include "../../include/admp_hip.h"
 #include "dev_buf.h"
 #include "dft_math.h"
+#include "dipole_math.h"
 #include "disp_plan.h"
 #include "handle.h"
 #include "launch.h"
@@ -171,6 +172,8 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   virtual void pme_at_U(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                         const double* mS, const double* pS, const void* U, double* E, void* dpos, void* dU, void* dQl) = 0;
   virtual void local_frames(const void* pos, const double* box, void* out) = 0;
+  virtual void dipoles(const void* pos, const double* box, const void* Ql, const void* U, const void* inv_mass, int n_groups,
+                       const int32_t* group_start, const int32_t* group_atoms, double* mu_groups, double* out16) = 0;
   virtual void mesh_convolve(const double* box, int which, void* data, int on_device, double* E_out, int32_t* info) = 0;
   virtual void slab_mesh_convolve(const double* box, int which, void* data, int on_device, double* E_out, int32_t* info) = 0;
   virtual void pair_program_eval(int id, const void* pos, const double* box, const void* par, int ns, const double* mS,
@@ -2237,6 +2240,26 @@ struct Engine : EngineBase {
     launch_local_frames<T>(stream, top, reinterpret_cast<const T*>(pos), bx, reinterpret_cast<T*>(out));
   }
 
+  // admp_pme_dipoles: the frames are those of this handle's topology, which is why the entry lives here.  Every refusal comes
+  // before the first launch; nothing is read back.
+  DevBuf dip_rows;
+  void dipoles(const void* pos, const double* box, const void* Ql, const void* U, const void* inv_mass, int n_groups,
+               const int32_t* group_start, const int32_t* group_atoms, double* mu_groups, double* out16) override {
+    if (snranks > 1) throw Err{ADMP_E_STATE, "admp_pme_dipoles does not work on a slab-decomposed handle"};
+    if (!have_top) throw Err{ADMP_E_STATE, "admp_set_topology must precede admp_pme_dipoles"};
+    ARG_CHECK(pos && box && Ql && inv_mass && group_start && group_atoms && out16, "null argument");
+    ARG_CHECK(n_groups >= 0, "negative number of groups");
+    for (int k = 0; k < 9; ++k) ARG_CHECK(std::isfinite(box[k]), "box is not finite");
+    double inv[9], vol;
+    const Box<T> bx = make_box(box, inv, &vol);      // (refuses a singular box)
+    ARG_CHECK(std::isfinite(vol), "box is not finite");
+    dip_rows.need(sizeof(double) * kDipoleRowWords * (size_t)std::max(1, dipole_rows(n_groups)));
+    const int rc = launch_dipoles<T>(stream, top, reinterpret_cast<const T*>(pos), bx, reinterpret_cast<const T*>(Ql),
+                                     reinterpret_cast<const T*>(U), reinterpret_cast<const T*>(inv_mass), n_groups, group_start,
+                                     group_atoms, mu_groups, dip_rows.as<double>(), out16);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("admp_pme_dipoles: ") + hipGetErrorString((hipError_t)rc)};
+  }
+
   // ---- box gradient: dE/dbox at fixed Cartesian positions = jax.grad(get_energy, argnums=1) of the
   // reference (admp/pme.py:108 with argnums; README.md:7 "force and virial").  The device kernels accumulate
   //   xw[9]  sum shift (x) dE/dr over boundary-crossing pairs and frame vectors + sum_atoms x (x) dE_recip/dx
@@ -3459,6 +3482,14 @@ int admp_pair_program_energy_grad(admp_handle* h, int program_id, const void* po
 
 int admp_local_frames(admp_handle* h, const void* positions, const double* box, void* frames_out) {
   return guarded(h, [&](EngineBase& e) { e.local_frames(positions, box, frames_out); });
+}
+
+int admp_pme_dipoles(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* U,
+                     const void* inv_mass, int n_groups, const int32_t* group_start_dev, const int32_t* group_atoms_dev,
+                     double* mu_groups_dev, double* out16_dev) {
+  return guarded(h, [&](EngineBase& e) {
+    e.dipoles(positions, box, Q_local, U, inv_mass, n_groups, group_start_dev, group_atoms_dev, mu_groups_dev, out16_dev);
+  });
 }
 
 int admp_set_option(admp_handle* h, int option, int value) {

@@ -153,6 +153,14 @@ void launch_prepare_sites(hipStream_t st, const Topology& top, const T* pos, con
                           const int* list = nullptr /* optional: only the rows of these atoms ... */, int nlist = 0 /* ... this many */);
 template <class T>
 void launch_local_frames(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, T* out /* (na,3,3) */);
+// The dipole observable (dipole_kernels.hip): molecular dipoles mu_groups (n_groups,3; may be null) and the 16 words of
+// admp_pme_dipoles over the groups of a CSR pair; rows: dipole_rows(n_groups) * 12 doubles of scratch.  No atomics, no read-back;
+// n_groups = 0 zeroes out16 on the stream.  Returns hipError_t as int.
+int dipole_rows(int n_groups);
+template <class T>
+int launch_dipoles(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, const T* Ql, const T* U /* may be null */,
+                   const T* inv_mass, int n_groups, const int* group_start, const int* group_atoms, double* mu_groups, double* rows,
+                   double* out16);
 // field (Cartesian dE/dU) = pair (harmonic order) + recip (cartesian) + self + penalty; also max |field| over
 // sites with pol > 0.001 (admp/pme.py:130,136) into *fmax_bits (order-preserving bit pattern of a non-negative real)
 // Every per-atom / per-row launcher below takes an optional index list (`list`/`rows`, nullptr = atoms 0..n-1):

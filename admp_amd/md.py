@@ -41,6 +41,12 @@ the step and the kinetic energy in double without atomics, then the draw of the 
 from (seed, step) (csrc/md_vrescale_math.h) and one pass that scales the velocities -- nothing read back, bit-repeatable.  One
 factor for all atoms keeps constrained velocities on their constraints, and the state carries the heat the thermostat has put
 in, so E_pot + K - heat is conserved.  Used by every driver in examples/md with --thermostat vrescale.
+
+`DipoleRecorder` records the dipole observable along a run: the molecular dipoles' statistics and the cell dipole, split into
+charge, permanent-dipole and induced parts, one row of 16 doubles per `record` in a device array (admp_pme_dipoles: two kernels
+without atomics, the arithmetic in csrc/dipole_math.h), read when the run ends; `group_csr` turns group labels into the CSR pair
+the kernel walks, `dielectric_constant` the rows into the static dielectric constant.  `ADMPPmeForce.get_dipoles` is the same
+call with one host read.  Used by every driver in examples/md with --dipoles N.
 """
 import ctypes
 
@@ -987,3 +993,162 @@ class VRescale:
     def heat(self):
         """(host read) the accumulated sum of (K after - K before) over the applications since reset(), in kJ/mol"""
         return self.info()['heat']
+
+
+# ---- the dipole observable (include/admp_hip.h admp_pme_dipoles; csrc/dipole_math.h) ------------------------------------------
+DEBYE_PER_E_ANGSTROM = 4.80320471
+
+
+def group_csr(groups):
+    """group labels (n_atoms; see `groups_of`) -> (group_start (n_groups + 1), group_atoms (n_atoms)), int32: the groups
+    ordered by their smallest atom, the atoms ascending inside a group, so that a group's anchor comes first."""
+    g = np.asarray(groups)
+    if g.ndim != 1:
+        raise ValueError('the group labels must be one-dimensional, got shape %s' % (g.shape,))
+    if g.size and not np.issubdtype(g.dtype, np.integer):
+        raise ValueError('the group labels must be integers')
+    n = len(g)
+    if n >= 2 ** 31:
+        raise ValueError('too many atoms')
+    _, inv = np.unique(g, return_inverse=True)
+    inv = inv.reshape(-1)
+    n_groups = int(inv.max()) + 1 if n else 0
+    first = np.full(n_groups, n, dtype=np.int64)
+    np.minimum.at(first, inv, np.arange(n))
+    rank = np.empty(n_groups, dtype=np.int64)
+    rank[np.argsort(first, kind='stable')] = np.arange(n_groups)
+    gid = rank[inv]                                                   # the group of every atom, groups by smallest atom
+    atoms = np.argsort(gid, kind='stable')                            # (stable: ascending inside a group)
+    start = np.concatenate([[0], np.cumsum(np.bincount(gid, minlength=n_groups))])
+    return start.astype(np.int32), atoms.astype(np.int32)
+
+
+def _checked_as(o, shape, **tensors):
+    """`_checked` for any shape"""
+    for name, t in tensors.items():
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == o._device.index):
+            raise ValueError('%s must be a tensor on the handle\'s device' % name)
+        if t.dtype != o._dtype:
+            raise ValueError('%s must be of the handle\'s precision (%s), got %s' % (name, o._dtype, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s must have shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+
+
+class _DipoleInputs:
+    """what a dipole call needs besides the step's arrays, on the device of `pme`: the CSR pair of the groups and 1 / m.  Made
+    once per (labels, masses) and kept on the calculator, so that neither is marshalled again step after step."""
+
+    def __init__(self, pme, groups, masses):
+        n = pme.n_atoms
+        g = np.asarray(groups)
+        if g.ndim != 1 or len(g) != n:
+            raise ValueError('%s group labels for %d atoms' % (g.shape, n))
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if len(m) != n:
+            raise ValueError('%d masses for %d atoms' % (len(m), n))
+        if not (np.all(m > 0) and np.all(np.isfinite(m))):
+            raise ValueError('masses must be positive and finite')
+        start, atoms = group_csr(g)
+        self.n_groups = len(start) - 1
+        self.start = torch.as_tensor(start).to(pme._device)
+        self.atoms = torch.as_tensor(atoms).to(pme._device)
+        self.inv_mass = pme._real(1.0 / m)
+
+    @classmethod
+    def of(cls, pme, groups, masses):
+        g = np.ascontiguousarray(np.asarray(groups))
+        m = np.ascontiguousarray(np.asarray(masses, dtype=np.float64))
+        key = (g.dtype.str, g.shape, g.tobytes(), m.tobytes())
+        cache = pme.__dict__.setdefault('_dipole_inputs', {})
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= 4:
+                cache.clear()
+            hit = cache[key] = cls(pme, g, m)
+        return hit
+
+
+def _dipoles_into(pme, inp, positions, box, Q_local, U, mu, out16_ptr):
+    """one admp_pme_dipoles call on the current stream: the arguments checked (the library reads raw pointers), the 16 words
+    written at `out16_ptr`, the molecular dipoles into `mu` (a device tensor, or None).  No host read."""
+    n = pme.n_atoms
+    _checked_as(pme, (n, 3), positions=positions)
+    _checked_as(pme, (n, 9), Q_local=Q_local)
+    if U is None and pme.lpol:
+        if not getattr(pme, '_have_U', False):
+            raise RuntimeError('U=None on a polarizable calculator means the dipoles of its last get_forces / get_energy call, '
+                               'and there has been none')
+        U = pme._real(pme.U_ind, (n, 3))
+    elif U is not None:
+        _checked_as(pme, (n, 3), U=U)
+    pme._use_current_stream()
+    boxa, _ = pme._harr('box', box, 9)
+    P = pme._ptr
+    rc = pme._L.admp_pme_dipoles(pme._h, P(positions), boxa, P(Q_local), P(U), P(inp.inv_mass), inp.n_groups, P(inp.start),
+                                 P(inp.atoms), P(mu), out16_ptr)
+    if rc == _lib.E_ARG:
+        msg = pme._L.admp_last_error(pme._h)
+        raise ValueError('admp_pme_dipoles: %s' % (msg.decode() if msg else ''))
+    _lib.check(pme._h, rc, 'admp_pme_dipoles')
+
+
+def _dipole_dict(w, mu=None):
+    """the 16 words of admp_pme_dipoles (host) as the dict of ADMPPmeForce.get_dipoles"""
+    ng = max(float(w[12]), 1.0)
+    out = {'M_charge': w[0:3].copy(), 'M_permanent': w[3:6].copy(), 'M_induced': w[6:9].copy(), 'mean_abs': float(w[9] / ng),
+           'rms': float(np.sqrt(w[10] / ng)), 'max_abs': float(w[11])}
+    out['M'] = out['M_charge'] + out['M_permanent'] + out['M_induced']
+    if mu is not None:
+        out['mu'] = mu
+    return out
+
+
+class DipoleRecorder:
+    """Records the dipole observable along a run without a host read per step.  `pme` is the ADMPPmeForce whose topology defines
+    the frames, `groups` the labels of `groups_of` (molecules), `masses` in any unit.  `record` writes the 16 words of
+    admp_pme_dipoles (include/admp_hip.h: the charge, permanent and induced parts of the cell dipole M, sum |mu_c|, sum |mu_c|^2,
+    max |mu_c|, the number of groups; e A) into the next row of a device array of `n_rows` rows; `rows()` is the one host read."""
+
+    def __init__(self, pme, groups, masses, n_rows):
+        if int(n_rows) != n_rows or n_rows < 0:
+            raise ValueError('n_rows must be a non-negative integer')
+        self._pme = pme
+        self._inp = _DipoleInputs.of(pme, groups, masses)
+        self.n_rows = int(n_rows)
+        self._rows = torch.zeros((self.n_rows, 16), dtype=torch.float64, device=pme._device)
+        self.k = 0
+
+    def record(self, positions, box, Q_local, U=None):
+        """row k of the array from the arrays of this step (device tensors of the calculator's precision; U=None on a
+        polarizable calculator: the dipoles of its last get_forces call), then k += 1.  IndexError when the array is full."""
+        if self.k >= self.n_rows:
+            raise IndexError('the recorder\'s %d rows are full' % self.n_rows)
+        _dipoles_into(self._pme, self._inp, positions, box, Q_local, U, None, self._rows.data_ptr() + 128 * self.k)
+        self.k += 1
+
+    def rows(self):
+        """(host read) the rows recorded so far, (k, 16) float64"""
+        return self._rows[:self.k].cpu().numpy()
+
+    def summary(self):
+        """(host read) the list of `get_dipoles`-style dicts of the rows recorded so far"""
+        return [_dipole_dict(w) for w in self.rows()]
+
+    def reset(self):
+        """start over at row 0"""
+        self.k = 0
+
+
+def dielectric_constant(M_rows, volume, temperature):
+    """static dielectric constant from the fluctuations of the cell dipole (conducting boundary, as Ewald sums imply):
+    1 + 4 pi DIELECTRIC (<M . M> - <M> . <M>) / (3 V kB T), with M_rows (n, 3) in e A, the volume in A^3, the temperature in K
+    and DIELECTRIC = e^2 / (4 pi eps0) in kJ/mol A of admp_amd.pme.  Pure numpy."""
+    from .pme import DIELECTRIC
+    M = np.asarray(M_rows, dtype=np.float64).reshape(-1, 3)
+    if len(M) == 0:
+        raise ValueError('no rows')
+    mean = M.mean(axis=0)
+    fluct = (M * M).sum(axis=1).mean() - mean @ mean
+    return 1.0 + 4.0 * np.pi * DIELECTRIC * fluct / (3.0 * float(volume) * KB * float(temperature))

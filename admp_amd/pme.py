@@ -106,6 +106,7 @@ class ADMPPmeForce(HipForceBase):
         self.get_energy._value_and_box_grad = self.get_energy_and_box_gradient      # ... argnums=1
         if self.lpol:
             self.U_ind = np.zeros((self.n_atoms, 3))      # reset with the closures, admp/pme.py:79
+            self._have_U = False                          # (get_dipoles: no polarizable call has filled U_ind yet)
             def energy_fn(*a, **k):                       # plain function objects, like the reference's closures
                 return self._energy_fn(*a, **k)
             energy_fn._grads = {0: self._grad_pos_fn, 4: self._grad_U_fn}
@@ -255,6 +256,24 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(self._h, self._L.admp_local_frames(self._h, self._ptr(pos), boxa, self._ptr(out)), 'admp_local_frames')
         return self._like(out, positions)
 
+    def get_dipoles(self, positions, box, Q_local, groups, masses, U=None, per_group=False):
+        """Molecular dipoles and the cell dipole M = sum_c mu_c, split into their charge, permanent-dipole and induced parts
+        (include/admp_hip.h admp_pme_dipoles; the definitions are in csrc/dipole_math.h and DESIGN.md section 8).  `groups` are
+        the labels of admp_amd.md.groups_of (host integers, one per atom: the molecules), `masses` host values; positions
+        (Na,3), Q_local (Na,9) and U (Na,3) are contiguous device tensors of the calculator's precision.  U=None on a polarizable
+        calculator means `self.U_ind`, the dipoles of the last get_forces / get_energy call (RuntimeError if there has been none);
+        on a non-polarizable one it means zero.  Returns a dict of host values in e A (1 e A = 4.80320471 D): M, M_charge,
+        M_permanent, M_induced (3,), mean_abs, rms and max_abs of |mu_c| over the groups and, with per_group, mu (n_groups, 3)
+        in group order (groups by their smallest atom).  The itinerant dipole q_c R_c of charged groups is not part of M.  One
+        host read.  An MD loop records through admp_amd.md.DipoleRecorder instead, which reads nothing back per step."""
+        from .md import _DipoleInputs, _dipole_dict, _dipoles_into
+        inp = _DipoleInputs.of(self, groups, masses)
+        buf = torch.empty(16 + (3 * inp.n_groups if per_group else 0), dtype=torch.float64, device=self._device)
+        mu = buf[16:] if per_group and inp.n_groups else None
+        _dipoles_into(self, inp, positions, box, Q_local, U, mu, buf.data_ptr())
+        w = buf.cpu().numpy()
+        return _dipole_dict(w[:16], w[16:].reshape(-1, 3).copy() if per_group else None)
+
     def _pme_recip(self, positions, box, Q):
         """Reciprocal-space energy of GLOBAL multipoles Q (Na, (lmax+1)^2) (generate_pme_recip, admp/recip.py:21-431, with
         gamma=False): evaluated by a sibling handle without local frames and with an empty pair list."""
@@ -295,6 +314,7 @@ class ADMPPmeForce(HipForceBase):
 
     def _store_scf(self, r, like):
         self.U_ind = self._like(r['U'], like)
+        self._have_U = True
         self.lconverg = r['flag']
         self.n_cycle = r['i']
         self._warn_unconverged(r)

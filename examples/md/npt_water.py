@@ -10,7 +10,7 @@ the thermostat's generator): a run restarted at any step repeats it.
     python examples/md/npt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1]
                                     [--pressure 1] [--tau-p 1000] [--compress 4.5e-5] [--nbaro 10] [--pol] [--single] [--mesh K]
                                     [--molecular | --rigid [--bonds-only] [--tol T]]
-                                    [--thermostat {langevin,vrescale}] [--tau-t 100]
+                                    [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N]
 
 The other arguments are those of nve_water.py.  Without --molecular or --rigid: isotropic scaling of the atoms only (one rank).
 --molecular: the same flexible water, but whole molecules are scaled about their centres of mass and the pressure is the
@@ -105,6 +105,7 @@ def main():
         if opt.prune and (step + 1) % opt.prune == 0:
             nbl.prune(pos)
         e123, grad = forces(pos, pairs)
+        w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         baro_now = (step + 1) % opt.nbaro == 0
         rec = baro_now and (step // opt.nbaro % max(opt.log // opt.nbaro, 1) == 0 or step + opt.nbaro >= opt.steps)
         if con is not None:
@@ -150,6 +151,8 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
+    for line in w.dipole_lines():
+        print(line)
     if con is not None or opt.molecular:
         info = baro.plan_info()
         print('# molecular scaling: %d groups in %d tiles of at most %d atoms, %d B of LDS per workgroup'

@@ -8,8 +8,10 @@ energies) and the achieved ns/day including neighbour rebuilds.  Per step the ho
 themselves do (each returns its energy as a number, like the reference's get_forces); the bonded and kinetic energies
 stay on the device until a line is logged.
 
-    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]]
+    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]] [--dipoles N]
 
+--dipoles N records the molecular and cell dipoles every N steps on the device (admp_amd.md.DipoleRecorder) and prints, when the
+run ends, the mean molecular dipole in Debye, its permanent and induced shares, and the dielectric constant of the run.
 --mesh K: K1 = K2 = K3 = K instead of the reference's rule (admp/pme.py:146-172), e.g. 128 for the 98 304-atom box of
 BASELINE configs[2] (the rule gives 305 = 5 * 61 there: every convolution then runs on the two-level DFT kernels, 0.7 ms
 each -- with a tight SCF that, not the host, is most of a step).
@@ -54,6 +56,7 @@ def main():
         if opt.prune and (step + 1) % opt.prune == 0:
             nbl.prune(pos)
         e123, grad = forces(pos, pairs)
+        w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         vv.kick(pos, vel, grad, want_ekin=rec)                         # v(t + h)
         if rec:
@@ -69,6 +72,8 @@ def main():
         print('\n'.join(w.scf_lines()))
         # which form the library chose for every polarizable call (residual history, engine.hip pme()) and what wrong guesses cost
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
+    for line in w.dipole_lines():
+        print(line)
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '
           'relative energy drift %.2e, T_final %.1f K' % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles',
                                                          settings.PRECISION, h, wall / opt.steps * 1e3, ns_day, opt.rebuild,

@@ -50,6 +50,9 @@ def add_arguments(ap):
     ap.add_argument('--mesh', type=int, default=0, help='PME mesh size per dimension (0: the reference rule)')
     ap.add_argument('--log', type=int, default=10, help='steps between energy records (each costs two host reads)')
     ap.add_argument('--thresh', type=float, default=1e-2, help='SCF threshold of --pol (the reference default 10 does not conserve energy)')
+    ap.add_argument('--dipoles', type=int, default=0, metavar='N', help='record the molecular and cell dipoles every N steps (0: off; '
+                    'admp_amd.md.DipoleRecorder: two small kernels per record, nothing read back until the run ends) and print the mean '
+                    'molecular dipole, its permanent and induced shares and the dielectric constant of the run')
     start = ap.add_mutually_exclusive_group()
     start.add_argument('--aspc', type=int, default=-1, choices=(0, 1, 2, 3, 4), metavar='K', help='always-stable predictor-corrector dipoles '
                        'of order K in the library (ADMPPmeForce.set_aspc, switched on after the minimiser): after K + 2 warm-up steps '
@@ -208,10 +211,42 @@ def setup(opt):
                           i['warmup'], i['fallback'], i['residual']))
         return out
 
+    dip = {}
+
+    def record_dipoles(step, p):
+        """--dipoles N: every N steps one row with the dipoles of the last forces() call and one without them (the permanent
+        share), each two small kernels on the calculator's stream; no host read"""
+        n_rec = getattr(opt, 'dipoles', 0)
+        if not n_rec or step % n_rec:
+            return
+        if not dip:
+            from admp_amd.md import DipoleRecorder
+            rows = (opt.steps + n_rec - 1) // n_rec
+            labels, masses = np.repeat(np.arange(n_mol), 3), np.tile(MASS, n_mol)
+            dip.update(full=DipoleRecorder(pme, labels, masses, rows), static=DipoleRecorder(pme, labels, masses, rows),
+                       zero=torch.zeros_like(p), volumes=[])
+        dip['full'].record(p, box, Q, state['U'] if opt.pol else None)
+        dip['static'].record(p, box, Q, dip['zero'])
+        dip['volumes'].append(abs(float(np.linalg.det(np.asarray(box, dtype=np.float64).reshape(3, 3)))))
+
+    def dipole_lines():
+        """the lines a --dipoles run prints when it ends (the one host read of each recorder)"""
+        if not dip:
+            return []
+        from admp_amd.md import DEBYE_PER_E_ANGSTROM as D, dielectric_constant
+        full, static = dip['full'].rows(), dip['static'].rows()
+        mean, perm = D * (full[:, 9] / full[:, 12]).mean(), D * (static[:, 9] / static[:, 12]).mean()
+        M = full[:, 0:3] + full[:, 3:6] + full[:, 6:9]
+        eps = dielectric_constant(M, float(np.mean(dip['volumes'])), opt.temp)
+        return ['# dipoles over %d records: mean molecular dipole %.4f D (permanent share %.4f D, induced share %.4f D); dielectric '
+                'constant %.2f at %.1f K -- a few hundred steps do not converge the dielectric constant: the cell dipole relaxes over '
+                'tens of picoseconds' % (len(full), mean, perm, mean - perm, eps, opt.temp)]
+
     par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
                                  forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient,
-                                 start_aspc=start_aspc, aspc_jump=aspc_jump, scf_lines=scf_lines)
+                                 start_aspc=start_aspc, aspc_jump=aspc_jump, scf_lines=scf_lines, record_dipoles=record_dipoles,
+                                 dipole_lines=dipole_lines)
 
 
 def minimize_fire(w, opt, pos, gradient=None, epot=None, constraints=None, label='minimize'):

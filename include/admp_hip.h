@@ -175,6 +175,35 @@ int admp_tt_box_grad(admp_handle* h, const void* positions, const double* box, c
  * Diagnostic only -- the hot path builds the frames inside its first kernel and never materialises them. */
 int admp_local_frames(admp_handle* h, const void* positions, const double* box, void* frames_out);
 
+/* No counterpart in the reference: the dipole observable of a multipolar, polarizable model -- molecular (per-group) dipoles and
+ * the cell dipole M, split into their charge, permanent-dipole and induced parts (admp_amd/csrc/dipole_math.h, dipole_kernels.hip).
+ * Groups are sets of atoms narrower than half the cell (the labels of admp_amd.md.groups_of); the anchor a of a group is its
+ * lowest-numbered atom, and atoms may be wrapped into the cell independently.  For atom i of group c:
+ *   d_i  = minimum image of r_i - r_a (exactly r_i - r_a when no translation was applied),  D_c = sum m_i d_i / M_c
+ *   p_i  = x_loc X_i + y_loc Y_i + z_loc Z_i with (z_loc, x_loc, y_loc) = Q_local[i, 1:4] (harmonics 10, 11c, 11s) and X_i, Y_i,
+ *          Z_i the rows of the atom's local frame (what admp_local_frames returns)
+ *   U_i  = the induced dipole (global Cartesian); zero when U is NULL
+ *   mu_c = sum_i [ q_i (d_i - D_c) + p_i + U_i ],  q_i = Q_local[i, 0];   M = sum_c mu_c
+ * A neutral group's mu_c does not depend on the origin, a charged group's is taken about its centre of mass, a single atom gives
+ * p_i + U_i.  The itinerant term q_c R_c of charged groups is NOT part of M: it is not defined under periodic boundaries.
+ * Unit: that of Q_local -- e A for positions in A (1 e A = 4.80320471 D).
+ *   positions (Na,3), Q_local (Na,9), U (Na,3; may be NULL), inv_mass (Na) 1/m_i: real of the handle's precision, DEVICE pointers
+ *   box               9 HOST doubles, lattice vectors in rows
+ *   group_start_dev   (n_groups + 1) int32, group_atoms_dev (Na) int32, DEVICE pointers: group c is the atoms
+ *                     group_atoms[group_start[c] .. group_start[c + 1]), ascending, so that the anchor comes first; a group has no
+ *                     size cap.  An index outside 0 .. Na - 1 is passed over, a range outside 0 .. Na makes an empty group.
+ *   mu_groups_dev     (n_groups,3) doubles, DEVICE pointer, may be NULL: mu_c
+ *   out16_dev         16 doubles, DEVICE pointer: [0..2] charge part of M, [3..5] permanent part, [6..8] induced part,
+ *                     [9] sum_c |mu_c|, [10] sum_c |mu_c|^2, [11] max_c |mu_c|, [12] n_groups, [13..15] 0
+ * The frames and d_i are formed in the handle's precision; every product and sum runs in double.  Two kernels on the handle's
+ * stream, no atomics (the 16 words and mu_c are the same bit for bit from run to run), no host synchronisation: an MD loop can
+ * record a row per step and read them when the run ends.  n_groups = 0 launches nothing and zeroes out16_dev on the stream.
+ * ADMP_E_ARG, before anything is launched, for a NULL required pointer, n_groups < 0, or a singular or non-finite box;
+ * ADMP_E_STATE without a topology (admp_set_topology) or on a slab-decomposed handle. */
+int admp_pme_dipoles(admp_handle* h, const void* positions, const double* box, const void* Q_local,
+                     const void* U /* may be NULL */, const void* inv_mass, int n_groups, const int32_t* group_start_dev,
+                     const int32_t* group_atoms_dev, double* mu_groups_dev /* (n_groups,3), may be NULL */, double* out16_dev);
+
 /* replaces: ADMPDispPmeForce.get_energy / get_forces (admp/disp_pme.py:44-77, 80-279).
  *   c_list (Na,3) real: C6, C8, C10 per atom (columns above pmax ignored); E_out[3] = real, recip, self */
 int admp_disp_energy_grad(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax,
