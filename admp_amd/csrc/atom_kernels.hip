@@ -8,6 +8,7 @@
 
 #include <cstring>
 
+#include "../../include/admp_hip.h"
 #include "launch.h"
 #include "reduce.h"
 
@@ -564,8 +565,8 @@ __global__ __launch_bounds__(kFinishBlock) void k_finish_rows(Topology top, Box<
 #pragma unroll
           for (int c = 0; c < 3; ++c) {                                  // (group mates: inside this run by construction)
             pz[c] = spos[lz][c];
-            if (ix >= 0) px[c] = spos[ix - a0][c];
-            if (iy >= 0) py[c] = spos[iy - a0][c];
+            if (usex && ix >= 0) px[c] = spos[ix - a0][c];          // (a slot the axis type does not use may hold any atom:
+            if (usey && iy >= 0) py[c] = spos[iy - a0][c];          //  the groups are built from the used ones alone)
           }
           FrameWork<T> w;
           local_frame_fwd(type, box, s.r, pz, px, py, w);
@@ -739,37 +740,62 @@ template <class T>
 void launch_aspc_predict(hipStream_t st, long n, const AspcSets<T>& h, T* out) {
   if (n > 0) k_aspc_predict<T><<<(unsigned)((n + kAtomBlock - 1) / kAtomBlock), kAtomBlock, 0, st>>>(n, h, out);
 }
-template <class T>
-void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, const Site<T>* sites,
-                   const T* pol, const T* Ucart, int lpol, T kappa, T* pot, T* grad, T* dQlocal, double* energies,
-                   const int* list, int nlist, const FieldFin<T>& ff, const int* slab_bits) {
+// The kernel launch_finish takes for this topology (admp_site_close reports it; the rules and switches stay in this file):
+// out4 = {ADMP_FINISH_FORM_*, frame groups, runs of the row form, workgroups of the row form's launch (0: another form)}.
+void finish_launch_choice(const Topology& top, bool list, bool slab_bits, int out4[4]) {
+  out4[1] = top.ngroups; out4[2] = top.nrowblk; out4[3] = 0;
   // molecular liquid at scale: one thread per frame group (below ~8k atoms the 4-lane pull form is faster: latency bound).
   // ADMP_FINISH_GROUPS_MIN overrides the threshold; read per call so that the parity tests can force either form.
   const int gmin = env_int("ADMP_FINISH_GROUPS_MIN", 8192);
   if ((!list || slab_bits) && top.ngroups > 0 && top.na > gmin) {
     // ADMP_FINISH_ROWS=0: the one-thread-per-group form of round 2 (A/B, tests)
-    if (top.rows_blk && env_flag("ADMP_FINISH_ROWS", true))      // (per call as well)
-      k_finish_rows<T><<<top.nrowblk < 1024 ? top.nrowblk : 1024, kFinishBlock, 0, st>>>(top, box, sites, pol, lpol, kappa, pot, grad,
-                                                                                         dQlocal, energies, ff,
-                                                                                         list ? slab_bits : nullptr);
-    else
-      k_finish_groups<T><<<nblk(top.ngroups), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad,
-                                                                   dQlocal, energies, ff, list ? slab_bits : nullptr);
+    if (top.rows_blk && env_flag("ADMP_FINISH_ROWS", true)) {      // (per call as well)
+      // ADMP_FINISH_ROWS_GRID: cap of the launch, 1..1024 (per call: tests enter the grid-stride loop with a few runs)
+      int cap = env_int("ADMP_FINISH_ROWS_GRID", 1024);
+      cap = cap < 1 ? 1 : (cap > 1024 ? 1024 : cap);
+      out4[0] = ADMP_FINISH_FORM_ROWS;
+      out4[3] = top.nrowblk < cap ? top.nrowblk : cap;
+    } else {
+      out4[0] = ADMP_FINISH_FORM_GROUPS;
+    }
     return;
   }
-  if (!list && top.inv_ptr)   // single GPU: pull formulation, no atomics
-  {
+  if (!list && top.inv_ptr) {   // single GPU: pull formulation, no atomics
     static const int lanes4_max = env_int("ADMP_FINISH4_MAX", 8192);
-    if (top.na <= lanes4_max)   // 3072 atoms: 9.6 vs 14.5 us; 30k atoms: 19.9 vs 14.2 us; 98k: 47 vs 21 us
+    // 3072 atoms: 9.6 vs 14.5 us; 30k atoms: 19.9 vs 14.2 us; 98k: 47 vs 21 us
+    out4[0] = top.na <= lanes4_max ? ADMP_FINISH_FORM_PULL4 : ADMP_FINISH_FORM_PULL1;
+    return;
+  }
+  out4[0] = ADMP_FINISH_FORM_LIST;
+}
+
+template <class T>
+void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<T>& box, const Site<T>* sites,
+                   const T* pol, const T* Ucart, int lpol, T kappa, T* pot, T* grad, T* dQlocal, double* energies,
+                   const int* list, int nlist, const FieldFin<T>& ff, const int* slab_bits) {
+  int c[4];
+  finish_launch_choice(top, list != nullptr, slab_bits != nullptr, c);
+  switch (c[0]) {
+    case ADMP_FINISH_FORM_ROWS:
+      k_finish_rows<T><<<c[3], kFinishBlock, 0, st>>>(top, box, sites, pol, lpol, kappa, pot, grad, dQlocal, energies, ff,
+                                                      list ? slab_bits : nullptr);
+      break;
+    case ADMP_FINISH_FORM_GROUPS:
+      k_finish_groups<T><<<nblk(top.ngroups), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad,
+                                                                   dQlocal, energies, ff, list ? slab_bits : nullptr);
+      break;
+    case ADMP_FINISH_FORM_PULL4:
       k_finish_pull<T, 4><<<nblk(4 * top.na), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad,
                                                                    dQlocal, energies, ff);
-    else
+      break;
+    case ADMP_FINISH_FORM_PULL1:
       k_finish_pull<T, 1><<<nblk(top.na), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad,
                                                                dQlocal, energies, ff);
+      break;
+    default:
+      k_finish<T><<<nblk(nlist), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad, dQlocal,
+                                                      energies, list, nlist);
   }
-  else
-    k_finish<T><<<nblk(nlist), kAtomBlock, 0, st>>>(top, pos, box, sites, pol, Ucart, lpol, kappa, pot, grad, dQlocal,
-                                                    energies, list, nlist);
 }
 
 template <class T>

@@ -240,6 +240,11 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   virtual void mesh_gather(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, const void* U,
                            const void* phi, int which, int on_device, double* E_out, void* pot, void* grad, void* fld,
                            int32_t* info) = 0;
+  virtual void site_table(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, const void* U,
+                          int on_device, void* sites_out, int32_t* act_out, int32_t* info) = 0;
+  virtual void site_close(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, const void* U,
+                          const void* pot_in, const void* phi_in, int which, int want_dQ, int on_device, double* E_out,
+                          void* grad_out, void* dQ_out, double* vir_out, int32_t* info) = 0;
   virtual void mscale_grad(int kind, const void* pos, const double* box, const void* par, int pmax, int ns, double* out,
                            int on_device) = 0;
   virtual void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) = 0;
@@ -3242,6 +3247,103 @@ struct Engine : EngineBase {
     scf.forget();
   }
 
+  // admp_site_table / admp_site_close: the first and the last stage of an evaluation alone -- the site pass of stage_begin and
+  // what it leaves (site rows, list of polarizable sites, flag word), and the closing kernels on a dE/dQ_global of the
+  // caller's through the evaluation's own launchers (tests compare every row with a float64 reference).
+  void site_table(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, const void* U_,
+                  int on_device, void* sites_out, int32_t* act_out, int32_t* info) override {
+    const MeshIn in = mesh_stage("admp_site_table", pos_, box, Ql_, pol_, thole_, U_, on_device);
+    ARG_CHECK(sites_out && info && (!lpol || act_out), "null argument");
+    const size_t na = (size_t)top.na;
+    act_n = -1;                      // the list is built by this call, whatever ADMP_OPT_KEEP_POL_SITES vouches for
+    mesh_begin(in, box);
+    ev.active = false;
+    double E[4];
+    read_energies(E_RECIP, E);       // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    int w[2];
+    std::memcpy(w, &Eh[E_NACT], sizeof(w));
+    const int n_act = lpol ? w[0] : 0;
+    // every other word of this call's half of the energy block was cleared by the site pass of the call before (or by the
+    // memset of a first call) and nothing has written to it since
+    int dirty = 0;
+    for (int k = 0; k < E_WORDS; ++k) dirty += (k != E_NACT && Eh[k] != 0.0) ? 1 : 0;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIP_TRY(hipMemcpyAsync(sites_out, sites.p, sizeof(Site<T>) * na, kind, stream));
+    if (n_act > 0)                   // before nact_seen puts the list in atom order
+      HIP_TRY(hipMemcpyAsync(act_out, act_d.p, sizeof(int) * (size_t)n_act, kind, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    nact_seen();
+    info[0] = n_act; info[1] = w[1]; info[2] = ev.bases ? 1 : 0; info[3] = dirty;
+    scf.forget();
+  }
+  void site_close(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, const void* U_,
+                  const void* pot_in, const void* phi_in, int which, int want_dQ, int on_device, double* E_out, void* grad_out,
+                  void* dQ_out, double* vir_out, int32_t* info) override {
+    const MeshIn in = mesh_stage("admp_site_close", pos_, box, Ql_, pol_, thole_, U_, on_device);
+    ARG_CHECK(which >= 0 && which <= 2,
+              "which must be 0 (the closing kernel), 1 (the closing epilogue of the gather) or 2 (the frame virial)");
+    ARG_CHECK(pot_in && info, "null argument");
+    if (which < 2) ARG_CHECK(E_out && grad_out && (!want_dQ || dQ_out), "null output");
+    else ARG_CHECK(vir_out != nullptr, "null output");
+    if (which == 1) {
+      ARG_CHECK(phi_in != nullptr, "which = 1: the gather needs a mesh phi_in");
+      ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
+      ARG_CHECK(fuse_fin_ok(), "which = 1: this handle's evaluations do not close in the gather (no frame groups, or more "
+                               "atoms than ADMP_FUSE_FIN_MAX)");
+    }
+    const size_t na = (size_t)top.na, nreal = (size_t)K[0] * K[1] * K[2];
+    const hipMemcpyKind in_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    grad.need(3 * na * sizeof(T));
+    T* dQ = nullptr;
+    if (which < 2 && want_dQ) {
+      if (on_device) dQ = reinterpret_cast<T*>(dQ_out);
+      else { s_dQ.need(9 * na * sizeof(T)); dQ = s_dQ.as<T>(); }
+    }
+    mesh_begin(in, box);
+    HIP_TRY(hipMemcpyAsync(pot.p, pot_in, 9 * na * sizeof(T), in_kind, stream));
+    for (int k = 0; k < 4; ++k) info[k] = 0;
+    if (which < 2) {
+      HIP_TRY(hipMemsetAsync(grad.p, 0, 3 * na * sizeof(T), stream));
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_SELF, 0, 2 * sizeof(double), stream));
+    }
+    if (which == 0) {
+      finish_launch_choice(top, false, false, info);
+      launch_finish_only(grad.as<T>(), dQ);
+    } else if (which == 1) {
+      const T* phi = reinterpret_cast<const T*>(phi_in);
+      if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(mesh.p, phi_in, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
+        phi = mesh.as<T>();
+      }
+      if (lpol) HIP_TRY(hipMemsetAsync(fld_recip.p, 0, 3 * na * sizeof(T), stream));
+      HIP_TRY(hipMemsetAsync(Ed_cur() + E_SLOTS, 0, E_PARTS * sizeof(double), stream));
+      const FinishArgs<T> fin = finish_args(true, dQ);
+      stage_gather(phi, grad.as<T>(), lpol ? fld_recip.as<T>() : nullptr, false, Ed_cur() + E_SLOTS, &fin);
+      launch_finish_only(grad.as<T>(), dQ);      // (the gather did this work: a no-op, as in an evaluation)
+      info[0] = ADMP_FINISH_FORM_GATHER_EPILOGUE;
+      info[1] = top.ngathblk;
+    } else {
+      vir_d.need(V_WORDS * sizeof(double));
+      HIP_TRY(hipMemsetAsync(vir_d.p, 0, 9 * sizeof(double), stream));
+      launch_frame_virial<T>(stream, top, ev.pos, ev.bx, sites.as<Site<T>>(), lpol, (T)kappa, pot.as<T>(), vir_d.as<double>(),
+                             nullptr, top.na);
+      HIP_TRY(hipMemcpyAsync(vir_out, vir_d.p, 9 * sizeof(double), hipMemcpyDeviceToHost, stream));
+      info[0] = -1;
+    }
+    ev.active = false;
+    double E[4];
+    read_energies(E_PARTS_SUM, E);
+    nact_seen();
+    if (which < 2) {
+      E_out[0] = E[2]; E_out[1] = E[3];
+      HIP_TRY(hipMemcpyAsync(grad_out, grad.p, 3 * na * sizeof(T), out_kind, stream));
+      if (dQ && !on_device) HIP_TRY(hipMemcpyAsync(dQ_out, dQ, 9 * na * sizeof(T), out_kind, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    scf.forget();
+  }
+
   // dE/dpScales[k] at the dipoles given (device pointers): class sums of pair_pscale_deriv, folded like dE/dmScales
   void pscale_grad(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
                    const double* mS, const double* pS, const void* U, double* out) override {
@@ -3677,6 +3779,20 @@ int admp_mesh_gather(admp_handle* h, const void* positions, const double* box, c
                      void* grad, void* fld, int32_t* info4) {
   return guarded(h, [&](EngineBase& e) {
     e.mesh_gather(positions, box, Q_local, pol, tholes, U, phi_in, which, on_device, E_out, pot, grad, fld, info4);
+  });
+}
+int admp_site_table(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                    const void* tholes, const void* U, int on_device, void* sites_out, int32_t* act_out, int32_t* info4) {
+  return guarded(h, [&](EngineBase& e) {
+    e.site_table(positions, box, Q_local, pol, tholes, U, on_device, sites_out, act_out, info4);
+  });
+}
+int admp_site_close(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                    const void* tholes, const void* U, const void* pot_in, const void* phi_in, int which, int want_dQ,
+                    int on_device, double* E_out2, void* grad_out, void* dQ_out, double* vir_out9, int32_t* info4) {
+  return guarded(h, [&](EngineBase& e) {
+    e.site_close(positions, box, Q_local, pol, tholes, U, pot_in, phi_in, which, want_dQ, on_device, E_out2, grad_out, dQ_out,
+                 vir_out9, info4);
   });
 }
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset) {

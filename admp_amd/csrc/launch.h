@@ -195,6 +195,9 @@ void launch_finish(hipStream_t st, const Topology& top, const T* pos, const Box<
                    const FieldFin<T>& ff = FieldFin<T>(),
                    const int* slab_bits = nullptr /* slab rank: per-atom words, kSlabHome marks the rank's own atoms (with a
                                                      home list); the frame-group kernel then serves the groups of home atoms */);
+// which kernel launch_finish takes for this topology (list / slab_bits: whether the call hands one over), see atom_kernels.hip:
+// out4 = {ADMP_FINISH_FORM_*, frame groups, runs of the row form, workgroups of the row form's launch}
+void finish_launch_choice(const Topology& top, bool list, bool slab_bits, int out4[4]);
 // dispersion: site rows carrying one scalar channel (Q[0] = vals[i*stride+chan], no dipoles/quadrupoles); also
 // accumulates coef * sum_i vals^2 into energies[E_SELF] (the self term of admp/disp_pme.py:254-279)
 template <class T>

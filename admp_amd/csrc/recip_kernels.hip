@@ -1053,8 +1053,8 @@ __global__ __launch_bounds__(kGsBlock) void k_gather_staged(int na, const Site<T
 #pragma unroll
           for (int c2 = 0; c2 < 3; ++c2) {
             pz[c2] = LF.spos[lz][c2];
-            if (ix >= 0) px[c2] = LF.spos[ix - slot0][c2];
-            if (iy >= 0) py[c2] = LF.spos[iy - slot0][c2];
+            if (usex && ix >= 0) px[c2] = LF.spos[ix - slot0][c2];      // (unused slots may hold any atom, see k_finish_rows)
+            if (usey && iy >= 0) py[c2] = LF.spos[iy - slot0][c2];
           }
           FrameWork<T> w;
           local_frame_fwd(type, box, st.r, pz, px, py, w);

@@ -599,6 +599,55 @@ class ADMPPmeForce(HipForceBase):
         _lib.check(self._h, rc, 'admp_mesh_gather')
         return {'E': E.value, 'pot': pot, 'grad': grad, 'fld': fld, 'info': tuple(int(v) for v in info)}
 
+    def site_table(self, positions, box, pairs, Q_local, pol=None, tholes=None, U=None):
+        """The site pass alone (admp_site_table), at the dipoles `U` as given.  Returns a dict: sites (Na,20) device tensor --
+        r, Q global, U in harmonic order, pol^(1/6), thole, 3 pad words (pad[0] = 1: charge-only) --, act: the list of
+        polarizable sites as the device wrote it (int32 device tensor of n_act words; None on a handle that is not polarizable),
+        n_act, flags (class flags word), records, dirty_energy_words.  A diagnostic for tests."""
+        pos, Q, pol_t, th_t, U_t = self._mesh_inputs(positions, pairs, Q_local, pol, tholes, U)
+        na = self.n_atoms
+        sites = torch.empty((na, 20), dtype=self._dtype, device=self._device)
+        act = torch.full((na,), -1, dtype=torch.int32, device=self._device) if self.lpol else None
+        info = (ctypes.c_int * 4)()
+        P = self._ptr
+        rc = self._L.admp_site_table(self._h, P(pos), _lib.darr(self._host64(box, 9)), P(Q), P(pol_t), P(th_t), P(U_t), 1,
+                                     P(sites), P(act), info)
+        _lib.check(self._h, rc, 'admp_site_table')
+        v = [int(x) for x in info]
+        return {'sites': sites, 'act': act[:v[0]] if act is not None else None, 'n_act': v[0], 'flags': v[1],
+                'records': v[2], 'dirty_energy_words': v[3]}
+
+    def site_close(self, positions, box, pairs, Q_local, pot, pol=None, tholes=None, U=None, phi=None, which=0, want_dQ=True):
+        """The closing kernels alone (admp_site_close) on `pot` (Na,9) = dE/dQ_global of the caller's: which = 0 the closing
+        kernel the handle's evaluations would launch, 1 the closing epilogue of the gather on the mesh `phi` (pot is then the
+        pair part), 2 the frame virial.  Returns a dict: which < 2: E_self, E_pen, grad (Na,3) = the frame adjoint (+ the
+        gather's gradient for which = 1), dQ (Na,9) = dE/dQ_local or None, form, ngroups, nrowblk, rows_grid (which = 1:
+        ngathblk); which = 2: vir (3,3) float64 numpy.  A diagnostic for tests."""
+        pos, Q, pol_t, th_t, U_t = self._mesh_inputs(positions, pairs, Q_local, pol, tholes, U)
+        na = self.n_atoms
+        pot_t = self._real(pot, (na, 9))
+        phi_t = self._real(phi, (self.K1, self.K2, self.K3)) if phi is not None else None
+        grad = dQ = None
+        if which != 2:
+            grad = torch.empty((na, 3), dtype=self._dtype, device=self._device)
+            dQ = torch.empty((na, 9), dtype=self._dtype, device=self._device) if want_dQ else None
+        E = (ctypes.c_double * 2)()
+        vir = (ctypes.c_double * 9)()
+        info = (ctypes.c_int * 4)()
+        P = self._ptr
+        rc = self._L.admp_site_close(self._h, P(pos), _lib.darr(self._host64(box, 9)), P(Q), P(pol_t), P(th_t), P(U_t),
+                                     P(pot_t), P(phi_t), int(which), 1 if want_dQ else 0, 1, E, P(grad), P(dQ), vir, info)
+        _lib.check(self._h, rc, 'admp_site_close')
+        v = [int(x) for x in info]
+        if which == 2:
+            return {'vir': np.array(list(vir), dtype=np.float64).reshape(3, 3)}
+        out = {'E_self': E[0], 'E_pen': E[1], 'grad': grad, 'dQ': dQ, 'form': _lib.FINISH_FORMS[v[0]]}
+        if which == 1:
+            out['ngathblk'] = v[1]
+        else:
+            out.update(ngroups=v[1], nrowblk=v[2], rows_grid=v[3])
+        return out
+
     def optimize_Uind(self, positions, box, pairs, Q_local, pol, tholes, mScales, pScales, dScales, U_init=None,
                       maxiter=None, thresh=None):
         """Jacobi SCF of the induced dipoles; returns (U, converged, i) like admp/pme.py:111-143."""

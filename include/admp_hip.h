@@ -718,6 +718,41 @@ int admp_mesh_spread(admp_handle* h, const void* positions, const double* box, c
 int admp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
                      const void* tholes, const void* U, const void* phi_in, int which, int on_device, double* E_out, void* pot,
                      void* grad, void* fld, int32_t* info4);
+/* The site table alone (test entry, single rank, prerequisites as admp_mesh_spread): what an evaluation does up to the end of
+ * its site pass (k_prepare_sites), at the dipoles U as given.
+ *   sites_out (Na,20)  the site rows as the handle's type lays them out: r (3), Q global (9), U in harmonic order z, x, y (3),
+ *                      pol^(1/6), thole, 3 pad words (pad[0] = 1 marks a charge-only site)
+ *   act_out (Na int32) the list of polarizable sites (pol > 0) as the device wrote it, before the host sorts it: the first
+ *                      info4[0] words; polarizable handles (else untouched, may be NULL)
+ * Words of the handle's type (act_out: int32) on the device (on_device != 0) or on the host, like the inputs.
+ * info4 = {number of polarizable sites (0 on a handle that is not polarizable), the class flags word of the call (bit 0: the
+ * neighbour table's charge-only classes are stale, bit 1: they could be better), 1 if stencil records were written, the number
+ * of energy words of this call's half of the energy block, other than the count, that did not read zero (the site pass of
+ * the call before clears them: always 0)}. */
+int admp_site_table(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                    const void* tholes, const void* U, int on_device, void* sites_out, int32_t* act_out, int32_t* info4);
+/* The closing kernels alone (test entry, single rank, prerequisites and site preparation as admp_mesh_spread), on a
+ * dE/dQ_global of the caller's, through the evaluation's own launchers.
+ *   which = 0: launch_finish on pot_in (Na,9): the self term is added to the potential, and the call returns E_out = {self
+ *              energy, polarization penalty}, grad_out (Na,3) = the local-frame adjoint alone (what the closing kernel adds to
+ *              a zeroed gradient) and, if want_dQ, dQ_out (Na,9) = dE/dQ_local.
+ *              info4 = {ADMP_FINISH_FORM_* of the launch, frame groups, runs of the row form, workgroups of the row form}.
+ *   which = 1: the same work in the closing epilogue of the gather on phi_in (K1 K2 K3 words, required): pot_in is the pair part,
+ *              the gather adds the reciprocal part to it and to the gradient.  ADMP_E_ARG where an evaluation would not take
+ *              this form (no frame groups, more atoms than ADMP_FUSE_FIN_MAX).
+ *              info4 = {ADMP_FINISH_FORM_GATHER_EPILOGUE, runs of the gather, 0, 0}.
+ *   which = 2: k_frame_virial on pot_in: vir_out (9 doubles, host) = sum over the frames' used axis vectors of (minimum-image
+ *              shift) (x) dE/d(vector); E_out, grad_out, dQ_out unused.  info4 = {-1, 0, 0, 0}.
+ * Words of the handle's type on the device (on_device != 0) or on the host, inputs and outputs alike; E_out, vir_out: host. */
+#define ADMP_FINISH_FORM_PULL4 0            /* k_finish_pull<4>: four lanes per atom over its inverse frame map */
+#define ADMP_FINISH_FORM_PULL1 1            /* k_finish_pull<1> */
+#define ADMP_FINISH_FORM_GROUPS 2           /* k_finish_groups: one lane per frame group */
+#define ADMP_FINISH_FORM_ROWS 3             /* k_finish_rows: one lane per atom, runs of whole frame groups through LDS */
+#define ADMP_FINISH_FORM_GATHER_EPILOGUE 4  /* k_gather_staged<.., FIN> */
+#define ADMP_FINISH_FORM_LIST 5             /* k_finish over a list of atoms (slab ranks without frame groups) */
+int admp_site_close(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
+                    const void* tholes, const void* U, const void* pot_in, const void* phi_in, int which, int want_dQ,
+                    int on_device, double* E_out2, void* grad_out, void* dQ_out, double* vir_out9, int32_t* info4);
 /* Where the closing pair kernel of the polarizable calls ran: out2 = {inside the x pass of a mesh convolution (small
  * double-precision systems on the direct-DFT mesh, one stream; ADMP_PAIR_RIDER=0 turns it off), in a launch of its own}. */
 int admp_pair_rider_stats(admp_handle* h, int64_t* out2, int reset);
