@@ -579,6 +579,25 @@ struct CellScratch {
   int ensure(int na, int ncell);
   void release();
 };
+// cell-sorted record of one atom (CellScratch::spos): a sweep reads ONE 16-B (f32) / 32-B (f64) word per candidate instead of
+// an index and three scattered coordinates
+template <class T>
+struct alignas(4 * sizeof(T)) CellAtom {
+  T x, y, z;
+  int id;
+};
+// the binning stage alone: cs.start (cell starts of the grid n, n[0] n[1] n[2] + 1 words) and cs.spos (the records; inside a
+// cell in NO particular order: for sweeps that do not depend on it) from the positions; no host synchronisation.  Returns
+// hipError_t as int.
+template <class T>
+int cell_bin_pack(hipStream_t st, int na, const T* pos, const Box<T>& box, const int n[3], CellScratch& cs);
+// (rdf_kernels.hip) the typed pair-distance counts of one frame ADDED to out (channels x n_bins 64-bit counters) by the plan of
+// rdf_plan.h; tags: type | group << 4 per atom (rdf_math.h); cs: the scratch of the cell form.  Integer atomics only, no host
+// synchronisation.  Returns hipError_t as int.
+struct RdfPlan;
+template <class T>
+int launch_rdf(hipStream_t st, const RdfPlan& plan, int n_atoms, const T* pos, const int* tags, const Box<T>& box, int n_types,
+               double r_max, int n_bins, CellScratch& cs, unsigned long long* out);
 template <class T>
 int cell_count_pairs(hipStream_t st, int na, const T* pos, const Box<T>& box, const double* heights, double rc,
                      CellScratch& cs, long long* n_pairs);

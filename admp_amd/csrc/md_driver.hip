@@ -1,5 +1,5 @@
 // The MD-driver helpers behind the admp_md_* entries of include/admp_hip.h (md_kernels.hip, mts_kernels.hip, con_kernels.hip,
-// mol_kernels.hip, fire_kernels.hip, vrescale_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
+// mol_kernels.hip, fire_kernels.hip, vrescale_kernels.hip, rdf_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
 // profiler and its rank count (handle.h HandleCtx), nothing of the engine.  The driver of a handle is created by its first
 // admp_md_* call, in the handle's precision, and dies with the handle.
 //
@@ -15,7 +15,7 @@
 //   * admp_md_mts_step checks n_inner before it looks for null pointers; the launches of the other two plans look for null
 //     inv_mass / box first (MdDriver::planned).
 //   * The profiler labels: md_bonded, md_kick_drift, md_langevin, md_random, md_bonded_box, md_virial, md_scale, md_mts,
-//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire, md_vrescale.
+//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire, md_vrescale, md_rdf.
 //   * The three *_info layouts differ (see the three functions); in each, words 0-6 are zero while no plan is held and word 7,
 //     the launch count, is always reported.
 //   * Tests match on the error texts: they stay byte for byte.
@@ -32,6 +32,7 @@
 #include "handle.h"
 #include "launch.h"
 #include "md_fire_math.h"
+#include "rdf_plan.h"
 
 using namespace admp;
 
@@ -375,6 +376,36 @@ struct MdDriver : HandleExt {
                                          vr_rows.as<double>(), state16_dev);
     if (rc != 0) throw Err{ADMP_E_HIP, std::string("velocity rescaling: ") + hipGetErrorString((hipError_t)rc)};
   }
+
+  // radial distribution functions (rdf_kernels.hip, rdf_math.h, rdf_plan.h; admp_amd/md.py RdfRecorder): needs no topology.  The
+  // driver owns the scratch of the cell form; every argument is checked before anything is launched, the slab refusal first.
+  CellScratch rdf_cells;
+  ~MdDriver() override {
+    (void)hipSetDevice(ctx.device);
+    rdf_cells.release();
+  }
+  void rdf(int n, const void* pos, const double* box, const int32_t* tags, int n_types, double r_max, int n_bins, uint64_t* hist_dev,
+           int force, int64_t* info4) {
+    single_rank();
+    ARG_CHECK(box && hist_dev && (n <= 0 || (pos && tags)), "bad argument (null pointer)");
+    ARG_CHECK(n <= INT_MAX / 4, "bad argument");
+    ARG_CHECK(std::isfinite(r_max), "r_max must be finite");
+    const Box<T> bx = finite_box(box);
+    double inv[9], vol, heights[3];
+    invert3(box, inv, &vol);
+    for (int d = 0; d < 3; ++d) heights[d] = 1.0 / std::sqrt(inv[0 + d] * inv[0 + d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
+    const RdfPlan p = rdf_make_plan(n, heights, r_max, n_types, n_bins, sizeof(T), force);
+    if (p.error) throw Err{ADMP_E_ARG, p.error};
+    if (info4) {
+      info4[0] = p.form; info4[1] = p.workgroups; info4[2] = p.form == RDF_FORM_TILES ? p.n_tiles : p.n_cells;
+      info4[3] = (int64_t)p.lds_bytes;
+    }
+    if (p.form == RDF_FORM_NONE) return;
+    TIMED("md_rdf");
+    const int rc = launch_rdf<T>(stream, p, n, reinterpret_cast<const T*>(pos), tags, bx, n_types, r_max, n_bins, rdf_cells,
+                                 reinterpret_cast<unsigned long long*>(hist_dev));
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("radial distribution: ") + hipGetErrorString((hipError_t)rc)};
+  }
 };
 
 template <class T>
@@ -494,6 +525,10 @@ int admp_md_vrescale(admp_handle* h, int n_atoms, void* velocities, const void* 
   return md_call(h, [&](auto& md) {
     md.vrescale(n_atoms, velocities, grad, inv_mass, half_dt_acc, n_dof, kT_acc, c, seed, step, call, state16_dev);
   });
+}
+int admp_md_rdf(admp_handle* h, int n_atoms, const void* positions_dev, const double* box, const int32_t* tags_dev, int n_types,
+                double r_max, int n_bins, uint64_t* hist_dev, int force, int64_t* info4) {
+  return md_call(h, [&](auto& md) { md.rdf(n_atoms, positions_dev, box, tags_dev, n_types, r_max, n_bins, hist_dev, force, info4); });
 }
 
 }  // extern "C"

@@ -47,6 +47,12 @@ charge, permanent-dipole and induced parts, one row of 16 doubles per `record` i
 without atomics, the arithmetic in csrc/dipole_math.h), read when the run ends; `group_csr` turns group labels into the CSR pair
 the kernel walks, `dielectric_constant` the rows into the static dielectric constant.  `ADMPPmeForce.get_dipoles` is the same
 call with one host read.  Used by every driver in examples/md with --dipoles N.
+
+`RdfRecorder` accumulates radial distribution functions along a run: the typed pair-distance counts of a frame are added to a
+device histogram of 64-bit counters by one C call (admp_md_rdf: pairs of 256-atom tiles up to 4096 atoms, a cell sweep above;
+integer atomics only, so the counts are bit-identical from run to run; csrc/rdf_math.h, rdf_plan.h, rdf_kernels.hip) and read
+when the run ends; `rdf_normalise` turns counts into g_ab(r) and running coordination numbers, `rdf_tags` types and group labels
+into the per-atom tags.  Used by every driver in examples/md with --rdf N.
 """
 import ctypes
 
@@ -1152,3 +1158,132 @@ def dielectric_constant(M_rows, volume, temperature):
     mean = M.mean(axis=0)
     fluct = (M * M).sum(axis=1).mean() - mean @ mean
     return 1.0 + 4.0 * np.pi * DIELECTRIC * fluct / (3.0 * float(volume) * KB * float(temperature))
+
+
+# ---- radial distribution functions (include/admp_hip.h admp_md_rdf; csrc/rdf_math.h, rdf_plan.h) ------------------------------
+RDF_MAX_TYPES, RDF_MAX_COUNTERS, RDF_NOT_COUNTED, RDF_MAX_GROUPS = 8, 16384, 15, 2 ** 27
+RDF_FORMS = ('none', 'tiles', 'cells')      # info()['form']: word 0 of admp_md_rdf's info4
+
+
+def rdf_channel(a, b, n_types):
+    """the row of the unordered type pair (a, b) in the histogram (csrc/rdf_math.h rdf_channel)"""
+    a, b = (a, b) if a <= b else (b, a)
+    return a * n_types - a * (a - 1) // 2 + (b - a)
+
+
+def rdf_tags(types, groups=None):
+    """per-atom types (ints; negative: not counted; at most 0..7) and group labels (those of `groups_of`; None: every atom its
+    own group, no exclusions) -> (tags int32 = type | group << 4 as admp_md_rdf reads them, n_types, atoms per type)"""
+    t = np.asarray(types)
+    if t.ndim != 1 or (t.size and not np.issubdtype(t.dtype, np.integer)):
+        raise ValueError('types must be a one-dimensional array of integers')
+    n = len(t)
+    t = t.astype(np.int64)
+    if n and t.max() >= RDF_MAX_TYPES:
+        raise ValueError('at most %d types (0..%d), got type %d' % (RDF_MAX_TYPES, RDF_MAX_TYPES - 1, t.max()))
+    n_types = max(int(t.max()) + 1, 1) if n else 1
+    if groups is None:
+        g = np.arange(n, dtype=np.int64)
+    else:
+        g = np.asarray(groups)
+        if g.ndim != 1 or len(g) != n or (g.size and not np.issubdtype(g.dtype, np.integer)):
+            raise ValueError('groups must be %d integer labels, got shape %s' % (n, g.shape))
+        g = np.unique(g, return_inverse=True)[1].reshape(-1).astype(np.int64)
+    if n and g.max() >= RDF_MAX_GROUPS:
+        raise ValueError('at most 2^27 groups')
+    tags = (np.where(t < 0, RDF_NOT_COUNTED, t) | (g << 4)).astype(np.int32)
+    return tags, n_types, np.bincount(t[t >= 0], minlength=n_types).astype(np.int64)
+
+
+def rdf_normalise(counts, type_counts, r_max, n_frames, sum_inv_volume):
+    """pair counts -> (r, g, n).  counts (channels, n_bins): the pairs per channel (rdf_channel) and bin summed over n_frames
+    frames, type_counts the atoms N_a of every type, sum_inv_volume the sum of 1 / V over the frames.  r: the bin centres;
+    g[(a, b)] = g[(b, a)] = counts / (N_pairs V_shell sum 1/V) with V_shell = 4 pi / 3 (r_{k+1}^3 - r_k^3) and N_pairs = N_a N_b
+    (a != b) or N_a (N_a - 1) / 2 (a = b): exact for an ideal gas, also under a changing cell; n[(a, b)] the running coordination
+    number of b around a at the upper edge of every bin, counts summed up over (N_a n_frames), twice that for a = b (a pair is
+    counted once and belongs to both).  Channels without pairs give zeros.  Pure numpy."""
+    c = np.asarray(counts).astype(np.float64)
+    N = np.asarray(type_counts, dtype=np.float64).reshape(-1)
+    n_types = len(N)
+    if c.ndim != 2 or c.shape[0] != n_types * (n_types + 1) // 2:
+        raise ValueError('counts must be (channels, n_bins) with %d channels, got %s' % (n_types * (n_types + 1) // 2, c.shape))
+    n_bins = c.shape[1]
+    edges = np.arange(n_bins + 1) * (float(r_max) / n_bins)
+    shell = 4.0 * np.pi / 3.0 * (edges[1:] ** 3 - edges[:-1] ** 3)
+    r = 0.5 * (edges[1:] + edges[:-1])
+    g, cn = {}, {}
+    for a in range(n_types):
+        for b in range(a, n_types):
+            row = c[rdf_channel(a, b, n_types)]
+            pairs = N[a] * N[b] if a != b else 0.5 * N[a] * (N[a] - 1.0)
+            norm = pairs * shell * float(sum_inv_volume)
+            g[(a, b)] = g[(b, a)] = row / norm if pairs > 0 and sum_inv_volume > 0 else np.zeros(n_bins)
+            cum = np.cumsum(row)
+            for x, y in ((a, b), (b, a)):
+                cn[(x, y)] = (2.0 if a == b else 1.0) * cum / (N[x] * n_frames) if N[x] > 0 and n_frames > 0 else np.zeros(n_bins)
+    return r, g, cn
+
+
+class RdfRecorder:
+    """Accumulates the typed pair-distance histogram of a run on the device: g_ab(r) and the coordination numbers without a host
+    read per frame.  `handle_owner` is any object with a handle (a calculator, a HarmonicBonded); no topology and no pair list are
+    needed.  `types` (ints, negative: not counted, at most 8 types) and `groups` (the labels of `groups_of`: pairs inside a group
+    are not counted; None: no exclusions) are fixed at construction; `r_max` (at most half of every perpendicular height of every
+    cell recorded) and `n_bins` fix the bins, channels x n_bins <= 16384.  `record` is one C call (admp_md_rdf) that adds the
+    frame's counts with integer atomics, so the counts are the same bit for bit from run to run; `counts()` is the one host read;
+    `force` (0 auto, 1 tiles, 2 cells) selects the kernel for tests and measurements."""
+
+    def __init__(self, handle_owner, types, r_max, n_bins, groups=None):
+        self._o = handle_owner
+        tags, self.n_types, self.type_counts = rdf_tags(types, groups)
+        self.n_atoms = len(tags)
+        self.channels = self.n_types * (self.n_types + 1) // 2
+        if int(n_bins) != n_bins or n_bins < 1:
+            raise ValueError('n_bins must be a positive integer')
+        self.n_bins, self.r_max = int(n_bins), float(r_max)
+        if not (np.isfinite(self.r_max) and self.r_max > 0):
+            raise ValueError('r_max must be positive and finite')
+        if self.channels * self.n_bins > RDF_MAX_COUNTERS:
+            raise ValueError('%d channels x %d bins exceed %d counters' % (self.channels, self.n_bins, RDF_MAX_COUNTERS))
+        self._tags = torch.as_tensor(tags).to(handle_owner._device)
+        self._hist = torch.zeros(self.channels * self.n_bins, dtype=torch.int64, device=handle_owner._device)
+        self._info = (ctypes.c_int64 * 4)()
+        self.force = 0
+        self.frames, self.sum_inv_volume = 0, 0.0
+
+    def record(self, positions, box):
+        """adds the frame's counts (positions: an (n, 3) device tensor of the handle's precision; box: 9 host values, rows) and
+        1 / V on the host; no host read.  ValueError for what the library refuses as an argument (r_max above half a height of
+        this cell, a singular box): nothing is counted then."""
+        o = self._o
+        _checked_as(o, (self.n_atoms, 3), positions=positions)
+        boxa, _ = o._harr('rdf_box', box, 9)
+        o._use_current_stream()
+        P = o._ptr
+        rc = o._L.admp_md_rdf(o._h, self.n_atoms, P(positions), boxa, P(self._tags), self.n_types, self.r_max, self.n_bins,
+                              P(self._hist), int(self.force), self._info)
+        if rc == _lib.E_ARG:
+            msg = o._L.admp_last_error(o._h)
+            raise ValueError('admp_md_rdf: %s' % (msg.decode() if msg else ''))
+        _lib.check(o._h, rc, 'admp_md_rdf')
+        h = np.frombuffer(boxa, dtype=np.float64).reshape(3, 3)
+        self.sum_inv_volume += 1.0 / abs(float(np.linalg.det(h)))
+        self.frames += 1
+
+    def counts(self):
+        """(host read) the pair counts so far, (channels, n_bins) uint64; row rdf_channel(a, b, n_types) is the type pair (a, b)"""
+        return self._hist.cpu().numpy().view(np.uint64).reshape(self.channels, self.n_bins)
+
+    def reset(self):
+        """zero counts (a memset on the current stream), no frames"""
+        self._hist.zero_()
+        self.frames, self.sum_inv_volume = 0, 0.0
+
+    def info(self):
+        """what the last record launched: form ('none', 'tiles', 'cells'), workgroups, tiles or cells, LDS bytes of a workgroup"""
+        w = [int(x) for x in self._info]
+        return {'form': RDF_FORMS[w[0]], 'workgroups': w[1], 'tiles' if w[0] != 2 else 'cells': w[2], 'lds_bytes': w[3]}
+
+    def rdf(self):
+        """(host read) r, g[(a, b)], n[(a, b)] of `rdf_normalise` over the frames recorded so far"""
+        return rdf_normalise(self.counts(), self.type_counts, self.r_max, self.frames, self.sum_inv_volume)

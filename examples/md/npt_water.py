@@ -10,7 +10,7 @@ the thermostat's generator): a run restarted at any step repeats it.
     python examples/md/npt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1]
                                     [--pressure 1] [--tau-p 1000] [--compress 4.5e-5] [--nbaro 10] [--pol] [--single] [--mesh K]
                                     [--molecular | --rigid [--bonds-only] [--tol T]]
-                                    [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N]
+                                    [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N] [--rdf N [--rdf-out FILE]]
 
 The other arguments are those of nve_water.py.  Without --molecular or --rigid: isotropic scaling of the atoms only (one rank).
 --molecular: the same flexible water, but whole molecules are scaled about their centres of mass and the pressure is the
@@ -106,6 +106,7 @@ def main():
             nbl.prune(pos)
         e123, grad = forces(pos, pairs)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
+        w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
         baro_now = (step + 1) % opt.nbaro == 0
         rec = baro_now and (step // opt.nbaro % max(opt.log // opt.nbaro, 1) == 0 or step + opt.nbaro >= opt.steps)
         if con is not None:
@@ -151,7 +152,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines():
+    for line in w.dipole_lines() + w.rdf_lines():
         print(line)
     if con is not None or opt.molecular:
         info = baro.plan_info()

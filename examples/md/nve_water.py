@@ -8,7 +8,7 @@ energies) and the achieved ns/day including neighbour rebuilds.  Per step the ho
 themselves do (each returns its energy as a number, like the reference's get_forces); the bonded and kinetic energies
 stay on the device until a line is logged.
 
-    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]] [--dipoles N]
+    python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]] [--dipoles N] [--rdf N [--rdf-out FILE]]
 
 --dipoles N records the molecular and cell dipoles every N steps on the device (admp_amd.md.DipoleRecorder) and prints, when the
 run ends, the mean molecular dipole in Debye, its permanent and induced shares, and the dielectric constant of the run.
@@ -57,6 +57,7 @@ def main():
             nbl.prune(pos)
         e123, grad = forces(pos, pairs)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
+        w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         vv.kick(pos, vel, grad, want_ekin=rec)                         # v(t + h)
         if rec:
@@ -72,7 +73,7 @@ def main():
         print('\n'.join(w.scf_lines()))
         # which form the library chose for every polarizable call (residual history, engine.hip pme()) and what wrong guesses cost
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines():
+    for line in w.dipole_lines() + w.rdf_lines():
         print(line)
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '
           'relative energy drift %.2e, T_final %.1f K' % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles',

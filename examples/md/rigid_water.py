@@ -8,7 +8,7 @@ nve_water.py launches, with the two half-step kernels replaced by the two constr
 the noise of --seed.  --bonds-only constrains the two O-H bonds only and keeps the harmonic angle (admp_amd.md.HarmonicBonded).
 
     python examples/md/rigid_water.py [--dt 2] [--bonds-only] [--friction 0] [--seed 1] [--tol T] [the arguments of nve_water.py]
-                                      [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N]
+                                      [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N] [--rdf N [--rdf-out FILE]]
 
 --thermostat vrescale keeps the friction at 0 and applies stochastic velocity rescaling (admp_amd.md.VRescale over the constrained
 degrees of freedom) after the RATTLE kick of every step: one factor for all velocities leaves them on the constraints.  The log
@@ -64,6 +64,7 @@ def main():
             nbl.prune(pos)
         e123, grad = gradient(pos, pairs_l)
         w.record_dipoles(step, pos)                                        # --dipoles: two small kernels, nothing read back
+        w.record_rdf(step, pos)                                            # --rdf: one C call, integer counters, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         integ.kick(pos, vel, grad, box, want_ekin=rec and not vr)          # B, RATTLE: one kernel
         if vr:
@@ -84,7 +85,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines():
+    for line in w.dipole_lines() + w.rdf_lines():
         print(line)
     info = con.plan_info()
     print('# constraints: %d tiles of at most %d atoms, %d B of LDS per workgroup, most sweeps of a cluster %d; '

@@ -53,6 +53,11 @@ def add_arguments(ap):
     ap.add_argument('--dipoles', type=int, default=0, metavar='N', help='record the molecular and cell dipoles every N steps (0: off; '
                     'admp_amd.md.DipoleRecorder: two small kernels per record, nothing read back until the run ends) and print the mean '
                     'molecular dipole, its permanent and induced shares and the dielectric constant of the run')
+    ap.add_argument('--rdf', type=int, default=0, metavar='N', help='add a frame to the radial distribution functions every N steps (0: '
+                    'off; admp_amd.md.RdfRecorder: one C call per frame, integer counters on the device, nothing read back until the run '
+                    'ends) to r_max = min(10 A, 0.49 x the smallest cell height) in bins of 0.05 A, and print the first g_OO peak, the '
+                    'minimum after it, the O-O coordination number up to there and the first intermolecular g_OH peak')
+    ap.add_argument('--rdf-out', default='', metavar='FILE', help='write r, g_OO, g_OH, g_HH of --rdf as text')
     start = ap.add_mutually_exclusive_group()
     start.add_argument('--aspc', type=int, default=-1, choices=(0, 1, 2, 3, 4), metavar='K', help='always-stable predictor-corrector dipoles '
                        'of order K in the library (ADMPPmeForce.set_aspc, switched on after the minimiser): after K + 2 warm-up steps '
@@ -242,11 +247,58 @@ def setup(opt):
                 'constant %.2f at %.1f K -- a few hundred steps do not converge the dielectric constant: the cell dipole relaxes over '
                 'tens of picoseconds' % (len(full), mean, perm, mean - perm, eps, opt.temp)]
 
+    rdf = {}
+
+    def record_rdf(step, p):
+        """--rdf N: every N steps the frame's O-O, O-H and H-H pair distances (pairs inside a molecule excluded) into the device
+        histogram: one C call on the calculator's stream; no host read.  r_max is fixed at the first frame; a cell that shrinks
+        below 2 r_max afterwards (NPT) is refused by the library"""
+        n_rec = getattr(opt, 'rdf', 0)
+        if not n_rec or step % n_rec:
+            return
+        if not rdf:
+            from admp_amd.md import RdfRecorder
+            h = np.asarray(box, dtype=np.float64).reshape(3, 3)
+            inv = np.linalg.inv(h)
+            r_max = min(10.0, 0.49 * float((1.0 / np.sqrt((inv * inv).sum(axis=0))).min()))
+            rdf['rec'] = RdfRecorder(pme, np.tile([0, 1, 1], n_mol), r_max, max(int(round(r_max / 0.05)), 1), groups=np.repeat(np.arange(n_mol), 3))
+        rdf['rec'].record(p, box)
+
+    def rdf_lines():
+        """the lines a --rdf run prints when it ends (the one host read of the recorder); writes --rdf-out"""
+        if not rdf:
+            return []
+        rec = rdf['rec']
+        r, g, n = rec.rdf()
+        goo, goh, ghh = g[(0, 0)], g[(0, 1)], g[(1, 1)]
+        if getattr(opt, 'rdf_out', ''):
+            np.savetxt(opt.rdf_out, np.stack([r, goo, goh, ghh], axis=1), header='r/A g_OO g_OH g_HH (%d frames)' % rec.frames)
+        info = rec.info()
+        out = ['# rdf over %d frames: r_max %.3f A, %d bins of %.4f A, %s form, %d workgroups' % (rec.frames, rec.r_max, rec.n_bins,
+                                                                                               rec.r_max / rec.n_bins, info['form'], info['workgroups'])]
+        # the first maximum: the highest bin below 3.6 A (the first O-O shell of water ends near 3.3 A); the minimum after it: the
+        # lowest bin between the peak and 1.6 x its position.  Bins of 0.05 A over a few frames are noisy: smoothed over 5 bins.
+        sm = np.convolve(goo, np.ones(5) / 5.0, mode='same')
+        first = r < 3.6
+        if first.any() and sm[first].max() > 0:
+            kp = int(np.argmax(np.where(first, sm, -1.0)))
+            after = (r > r[kp]) & (r <= 1.6 * r[kp])
+            km = int(np.argmin(np.where(after, sm, np.inf))) if after.any() else kp
+            out.append('# g_OO: first maximum %.3f at %.3f A, first minimum %.3f at %.3f A, O-O coordination number up to the minimum '
+                       '%.2f; g_OO is zero below %.3f A' % (sm[kp], r[kp], sm[km], r[km], n[(0, 0)][km],
+                                                          r[np.nonzero(goo)[0][0]] - 0.5 * rec.r_max / rec.n_bins))
+        smh = np.convolve(goh, np.ones(5) / 5.0, mode='same')
+        inter = (r > 1.3) & (r < 2.5)      # the hydrogen-bond peak: beyond the (excluded) bond length, before the second shell
+        if inter.any() and smh[inter].max() > 0:
+            kh = int(np.argmax(np.where(inter, smh, -1.0)))
+            out.append('# g_OH: first intermolecular maximum %.3f at %.3f A' % (smh[kh], r[kh]))
+        return out
+
     par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
                                  forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient,
                                  start_aspc=start_aspc, aspc_jump=aspc_jump, scf_lines=scf_lines, record_dipoles=record_dipoles,
-                                 dipole_lines=dipole_lines)
+                                 dipole_lines=dipole_lines, record_rdf=record_rdf, rdf_lines=rdf_lines)
 
 
 def minimize_fire(w, opt, pos, gradient=None, epot=None, constraints=None, label='minimize'):

@@ -496,6 +496,37 @@ int admp_md_vrescale(admp_handle* h, int n_atoms, void* velocities, const void* 
                      const void* inv_mass, double half_dt_acc, int64_t n_dof, double kT_acc, double c, uint64_t seed, uint64_t step,
                      uint64_t call, double* state16_dev);
 
+/* No counterpart in the reference: radial distribution functions -- the typed pair-distance counts of one frame, ADDED to a
+ * caller-owned device histogram (admp_amd/csrc/rdf_math.h, rdf_plan.h, rdf_kernels.hip).  Needs no topology and no pair list:
+ * the neighbour tables of the calculators stop at their cutoff, a g(r) runs to 8-12 A.
+ *   positions_dev  (n_atoms,3) real of the handle's precision, DEVICE pointer; atoms may lie outside the cell
+ *   box            9 HOST doubles, lattice vectors in rows
+ *   tags_dev       (n_atoms) int32, DEVICE pointer: type | group << 4.  type 0 .. n_types - 1 is a counted type, 15 means "not
+ *                  counted", and so does every other value (8 .. 14, and a type >= n_types); group is 0 .. 2^27 - 1.  A pair is
+ *                  counted when both types are counted and the groups differ (groups = molecules excludes the intramolecular
+ *                  pairs; "no exclusions" is every atom its own group).
+ *   n_types        1 .. 8; the unordered type pair (a <= b) is channel a n_types - a (a - 1) / 2 + (b - a), of
+ *                  n_types (n_types + 1) / 2 channels
+ *   r_max, n_bins  bin k of a channel counts the pairs with k r_max / n_bins <= r < (k + 1) r_max / n_bins, r the length of the
+ *                  minimum image of r_i - r_j in the handle's precision (the arithmetic of the pair kernels); pairs with
+ *                  r >= r_max are not counted.  channels * n_bins <= 16384 (the histogram of a workgroup is 64 KB of LDS).
+ *   hist_dev       (channels, n_bins) uint64, DEVICE pointer: the counts are ADDED; the caller zeroes it and reads it
+ *   force          0: the library chooses (up to 4096 atoms the tile form: one workgroup per pair of 256-atom tiles; above, the
+ *                  cell form: atoms binned at cell width >= r_max, one workgroup per home cell, half sweep); 1: tiles; 2: cells
+ *   info4          HOST, may be NULL: form (0 nothing launched, 1 tiles, 2 cells), workgroups, tiles or cells, LDS bytes of a
+ *                  workgroup
+ * Counters are integers and only integer atomics add to them (32-bit in LDS, flushed before one could wrap, 64-bit in hist_dev):
+ * the result does not depend on the order of anything and is the same bit for bit from run to run.  Runs on the handle's stream
+ * and makes no host synchronisation (the first call of the cell form, and one that needs more scratch, allocate): an MD loop
+ * records a frame every few steps and reads the histogram when the run ends.  n_atoms = 0 launches nothing.
+ * ADMP_E_STATE on a slab-decomposed handle.  ADMP_E_ARG, before anything is launched, for a NULL box or hist_dev, NULL positions
+ * or tags (unless n_atoms = 0: an empty device array has no address), n_atoms < 0, n_types outside 1 .. 8, n_bins < 1,
+ * channels * n_bins > 16384, r_max not finite, <= 0 or above half of any perpendicular height of the cell, a singular or
+ * non-finite box, force outside 0 .. 2. */
+int admp_md_rdf(admp_handle* h, int n_atoms, const void* positions_dev, const double* box /* 9 host */, const int32_t* tags_dev,
+                int n_types, double r_max, int n_bins, uint64_t* hist_dev /* channels * n_bins, ADDED to */,
+                int force /* 0 auto, 1 tiles, 2 cells */, int64_t* info4 /* host, may be NULL */);
+
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
  * the same admp_pme_energy_grad / admp_disp_energy_grad / admp_tt_energy_grad call with the same full input arrays.  Rank s
