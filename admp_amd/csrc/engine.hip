@@ -1,5 +1,6 @@
-// libadmp_hip: handle, device buffers, rocFFT plans, and the orchestration of one
-// get_energy / get_forces evaluation behind the C ABI of include/admp_hip.h.
+// libadmp_hip: handle, device buffers, and the orchestration of one get_energy / get_forces evaluation behind the C ABI of
+// include/admp_hip.h.  The k-space leg between spread and gather (rocFFT plans, tables, every transform path) is MeshConv,
+// mesh_conv.hip; the MD entries are md_driver.hip.
 //
 // Flow of admp_pme_energy_grad (reference call stack: admp/pme.py:58-86 get_energy ->
 // :111-143 optimize_Uind -> :176-254 energy_pme, gradient by jax.value_and_grad :108):
@@ -7,11 +8,10 @@
 //   (polarizable)   Jacobi SCF: pair_field + spread/r2c/kspace/c2r/gather_field + field_finish,
 //                   one host read of max|field| per cycle (the reference syncs there too, pme.py:136)
 //   pair_full       real-space energy, dE/dr, dE/dQ                                 [pair_kernels.hip]
-//   spread, r2c, kspace (energy + G multiply), c2r, gather                          [recip_kernels.hip + rocFFT]
+//   spread, r2c, kspace (energy + G multiply), c2r, gather                          [recip_kernels.hip; mesh_conv.hip]
 //   finish          self + penalty, frame adjoint, dE/dQ_local                      [atom_kernels.hip]
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <array>
@@ -27,12 +27,14 @@
 #include <vector>
 
 #include "../../include/admp_hip.h"
+#include "comm.h"
 #include "dev_buf.h"
 #include "dft_math.h"
 #include "dipole_math.h"
 #include "disp_plan.h"
 #include "handle.h"
 #include "launch.h"
+#include "mesh_conv.h"
 #include "rccl_comm.h"
 #include "scf_policy.h"
 #include "scf_aspc.h"
@@ -40,14 +42,6 @@
 using namespace admp;
 
 namespace {
-
-#define FFT_TRY(x)                                                                                       \
-  do {                                                                                                   \
-    rocfft_status s_ = (x);                                                                              \
-    if (s_ != rocfft_status_success) throw Err{ADMP_E_FFT, std::string(#x) + ": rocfft status " + std::to_string((int)s_)}; \
-  } while (0)
-
-std::once_flag g_fft_once;
 
 struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, srank, snranks, md (handle.h)
   virtual ~EngineBase() {}
@@ -57,39 +51,13 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   double kappa = 0;
   int K[3] = {0, 0, 0};
   int lmax = 2, lpol = 0;
-  admp_comm comm{};             // the caller's communicator of the x-slab decomposition (admp_set_comm); unused with one rank
-  bool have_comm = false;
-  // collectives of a decomposed evaluation: every rank makes the same calls in the same order
-  admp_rccl* rccl = nullptr;    // native communicator (admp_set_comm_rccl): the collectives go straight to RCCL on `stream`
-  void comm_fail(const char* what, int rc) {
-    if (rccl) throw Err{ADMP_E_COMM, std::string(what) + ": " + rccl_error()};
-    throw Err{ADMP_E_COMM, std::string("communicator callback ") + what + " returned " + std::to_string(rc)};
-  }
-  void c_all_reduce(void* buf, int64_t n, int dtype, int op, int tag) {
-    const int rc = rccl ? rccl_all_reduce(rccl, stream, buf, n, dtype, op, tag) : comm.all_reduce(comm.ctx, buf, n, dtype, op, tag);
-    if (rc != 0) comm_fail("all_reduce", rc);
-  }
-  void c_all_to_all_v(const void* send, const int64_t* sc, void* recv, const int64_t* rc_, int dtype, int tag) {
-    const int rc = rccl ? rccl_all_to_all_v(rccl, stream, send, sc, recv, rc_, dtype, tag)
-                        : comm.all_to_all_v(comm.ctx, send, sc, recv, rc_, dtype, tag);
-    if (rc != 0) comm_fail("all_to_all_v", rc);
-  }
-  void c_shift(const void* send, void* recv, int64_t n, int dtype, int to_next, int tag) {
-    const int rc = rccl ? rccl_shift(rccl, stream, send, recv, n, dtype, to_next, tag)
-                        : comm.shift(comm.ctx, send, recv, n, dtype, to_next, tag);
-    if (rc != 0) comm_fail("shift", rc);
-  }
+  Comm comm;                    // the collectives of a decomposed evaluation (comm.h)
   // how the polarizable calls of this handle were enqueued and how the guesses behind it turned out (admp_scf_stats):
   // [0] plain calls, [1] speculative calls, [2] ... whose first check failed (closing pass wasted), [3] chained calls,
   // [4] ... that needed more steps than enqueued (closing pass wasted), [5] ... that enqueued more steps than needed,
   // [6] increments that ran for nothing in those, [7] Jacobi steps in total
   int64_t scf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // x passes of the direct-DFT convolution of one mesh (admp_xpass_stats): [0] circulant form, [1] forward * G * inverse
-  int64_t xpass_stats[2] = {0, 0};
-  // launches of the plane kernels of the direct-DFT convolution (admp_plane_mfma_stats): [0] with a matrix-core share, [1] without
-  int64_t plane_mfma_stats[2] = {0, 0};
-  // the same launches by direction (admp_plane_mfma_stats4): forward with a share, forward vector, inverse with a share, inverse vector
-  int64_t plane_mfma_stats4[4] = {0, 0, 0, 0};
+  MeshStats mesh_stats;         // counters of the direct-DFT convolution (admp_xpass_stats, admp_plane_mfma_stats[4]); mesh_conv.h
   // closing pair kernels of polarizable calls (admp_pair_rider_stats): [0] rode in an x pass, [1] launched on their own
   int64_t pair_rider_stats[2] = {0, 0};
   // admp_scf_aspc: predictor-corrector dipoles for consecutive polarizable calls (scf_aspc.h).  The ring arithmetic lives
@@ -449,11 +417,10 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
 
 // decomposition state of one evaluation on a slab rank (snranks > 1; slab_kernels.hip)
 struct SlabState {
-  DevBuf owner, owner_prev, mig, bits, counts, totals, lists, imp, exp, mig_in, mig_out, sendb, recvb, ghost, pack, tbuf;
+  DevBuf owner, owner_prev, mig, bits, counts, totals, lists, imp, exp, mig_in, mig_out, sendb, recvb;
   int prev_na = -1;             // owner_prev holds the owners of this handle's previous decomposed evaluation of prev_na atoms
   int64_t min_cnt[kSlabMaxRanks], mout_cnt[kSlabMaxRanks];   // atoms taken over from / given away to every rank since then
   int n_min = 0, n_mout = 0;
-  int64_t tr_send[kSlabMaxRanks], tr_recv[kSlabMaxRanks];
   int64_t imp_cnt[kSlabMaxRanks], exp_cnt[kSlabMaxRanks];     // atoms imported from / exported to every rank
   int n_home = 0, n_act = 0, n_imp = 0, n_exp = 0;
   bool tracked = false;         // the last decomposition compared its owners with the previous one's (mig_in / mig_out are lists)
@@ -477,18 +444,11 @@ struct Engine : EngineBase {
   double* Ed_cur() { return energies_d.as<double>() + (size_t)ehalf * E_WORDS; }
   // staging for host-pointer calls
   DevBuf s_pos, s_Q, s_pol, s_thole, s_U, s_out, s_dQ, s_par;
-  // mesh
-  DevBuf mesh, spec, gtabs[4], fft_work, binv_d, bin_cells, bin_sorted, bin_scan, bin_cells_ind, bin_sorted_ind;   // gtabs: Ck_1, Ck_6, Ck_8, Ck_10
-  T* gtab_cur = nullptr;
+  // mesh: the real meshes belong to spread and gather as much as to the transform; everything of the k-space leg between
+  // them (plans, spectrum, G tables, slab bounds and transposes) is mc's (mesh_conv.h)
+  DevBuf mesh, bin_cells, bin_sorted, bin_scan, bin_cells_ind, bin_sorted_ind;
+  MeshConv<T> mc{this, &comm, &mesh_stats};
   BinScratch bins, bins_ind;   // brick lists of the site rows / of the compact rows of the SCF increments
-  rocfft_plan plan_f = nullptr, plan_b = nullptr, plan_xf = nullptr, plan_xb = nullptr;
-  // power-of-two x dimension on one rank: batched 2-D plans of the y-z planes around the fused x pass (fftx_kernels.hip)
-  rocfft_plan plan2_f = nullptr, plan2_b = nullptr;
-  int fx_khp = 0;              // row pitch (complex numbers) of the spectrum those plans write: K2/2+1 padded to whole lines
-  bool use_fx = false;
-  DevBuf fx_tw;
-  rocfft_execution_info info_f = nullptr;
-  int planK[3] = {0, 0, 0}, planR = 0, planRank = 0;
   DevBuf home_list;
   DevBuf act_tmp;
   DevBuf onehot_d, tcount_d;     // typed dispersion of small systems: (Na, n_types) one-hot weights; scratch of the type counts
@@ -511,28 +471,17 @@ struct Engine : EngineBase {
   long eval_seq = 0, ind_bins_eval = -1, ind_bins_gen = -1;   // evaluation counter; the evaluation / active set bins_ind was built for
   int ind_bins_n = -1;
   const int* ind_bins_at = nullptr;
-  DevBuf dft_tw;          // twiddle tables of the direct-DFT path
   DevBuf bases_d;         // int4 per atom: lowest stencil index on each mesh axis
-  bool use_dft = false;   // mesh convolution through dft_kernels.hip instead of rocFFT (single rank, a Bluestein dimension)
-  bool use_pfa = false;   // ... through pfa_kernels.hip: a Bluestein dimension too long for plain lines, split N = N1 * N2;
-  PfaPlan pfa;            //     spectrum and G tables then live in slot order with pfa.Khp z columns
-  DevBuf pfa_tw, pfa_fmap, pfa_ptab, gtab_nat;
-  // validity of the cached G table
-  struct TabKey { double box[9] = {0}, kappa = -1; int K[3] = {0, 0, 0}, Y0 = 0, ref = 0; bool pfa = false; } tabkey[4];
-  // circulant form of the x pass (dft_math.h): first columns of the G table of slot 0, rebuilt with it; xctab_ok: the table
-  // is even along x in every column (k_ctab's check, read back when the table is built)
-  DevBuf xctab, xctab_flag;
-  bool xctab_ok = false;
-  static bool xcirc_on() { static const bool on = env_flag("ADMP_DFT_XCIRC", true); return on; }
-  static int tab_slot(int which) { return which == 1 ? 0 : (which == 6 ? 1 : (which == 8 ? 2 : 3)); }
   static_assert(kScfChainSteps == E_CHAIN, "one residual word per chained Jacobi step");
   ScfHistory scf;             // residual history of the polarizable calls of this handle: picks the form of the next one
   bool mono_ok = false;       // this evaluation may use the charge-only pair forms (no dE/dQ_local requested)
 
   // Every DevBuf member frees itself after this body, so after the stream is gone: hipFree needs no stream, and admp_destroy
-  // has set the device and synchronised the stream before it deletes the handle.
+  // has set the device and synchronised the stream before it deletes the handle.  The rocFFT plans are mc's, but they go here,
+  // by a call at the head of this body, so that they are destroyed before the stream as they always were; mc's own
+  // destructor then finds none left.
   ~Engine() override {
-    destroy_plans();
+    mc.destroy_plans();
     free_topology();
     if (ind.end) (void)hipFree(ind.end);
     if (ind.col) (void)hipFree(ind.col);
@@ -546,25 +495,6 @@ struct Engine : EngineBase {
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 
-  void destroy_plans() {
-    if (plan_f) rocfft_plan_destroy(plan_f);
-    if (plan_b) rocfft_plan_destroy(plan_b);
-    if (plan_xf) rocfft_plan_destroy(plan_xf);
-    if (plan_xb) rocfft_plan_destroy(plan_xb);
-    if (plan2_f) rocfft_plan_destroy(plan2_f);
-    if (plan2_b) rocfft_plan_destroy(plan2_b);
-    for (int k = 0; k < 4; ++k) {
-      if (plan2n_f[k]) rocfft_plan_destroy(plan2n_f[k]);
-      if (plan2n_b[k]) rocfft_plan_destroy(plan2n_b[k]);
-      plan2n_f[k] = plan2n_b[k] = nullptr;
-    }
-    if (info_f) rocfft_execution_info_destroy(info_f);
-    plan_f = plan_b = plan_xf = plan_xb = plan2_f = plan2_b = nullptr;
-    use_fx = false;
-    info_f = nullptr;
-    planK[0] = planK[1] = planK[2] = 0;
-  }
-
   void set_ewald(double kappa_, int K1, int K2, int K3, int lmax_, int lpol_) override {
     ARG_CHECK(kappa_ > 0, "kappa must be positive");
     ARG_CHECK(K1 >= 2 && K2 >= 2 && K3 >= 2, "PME mesh must be at least 2 points per dimension");   // (spline users: make_geom)
@@ -575,34 +505,15 @@ struct Engine : EngineBase {
     if (!lpol) aspc_off();
   }
 
-  // ---- slab decomposition state (nranks == 1: the whole mesh is local) ---------------------------------
-  // rank s owns mesh planes [X0, X1) along x and, in the transposed (k-space) layout, rows [Y0, Y1) along y;
-  // the local real mesh additionally carries kGhost planes above X1 (stencil overhang / phi halo).
-  static constexpr int kGhost = 5;
-  int X0 = 0, X1 = 0, Y0 = 0, Y1 = 0;
-  void update_slab() {
-    X0 = (int)((long)srank * K[0] / snranks); X1 = (int)((long)(srank + 1) * K[0] / snranks);
-    Y0 = (int)((long)srank * K[1] / snranks); Y1 = (int)((long)(srank + 1) * K[1] / snranks);
-    if (snranks > 1) {
-      ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      const int64_t nh = K[2] / 2 + 1;
-      for (int s = 0; s < snranks; ++s) {
-        int w = (int)((long)(s + 1) * K[0] / snranks) - (int)((long)s * K[0] / snranks);
-        ARG_CHECK(w >= 6, "slab decomposition needs at least 6 mesh planes per rank along x");
-        int wy = (int)((long)(s + 1) * K[1] / snranks) - (int)((long)s * K[1] / snranks);
-        ARG_CHECK(wy >= 1, "slab decomposition needs at least 1 mesh row per rank along y");
-        // transposes: block (x in my slab) x (y in slab s) travels to rank s, block (x in slab s) x (my y rows) comes back
-        sl.tr_send[s] = (int64_t)(X1 - X0) * wy * nh * 2;
-        sl.tr_recv[s] = (int64_t)w * (Y1 - Y0) * nh * 2;
-      }
-    }
-  }
+  // ---- slab bounds: rank s owns mesh planes [X0, X1) along x, plus kGhost overhang planes above X1 (MeshConv::update_slab) ----
+  static constexpr int kGhost = MeshConv<T>::kGhost;
+  void update_slab() { mc.update_slab(K); }
   // ---- decomposition state of one evaluation (snranks > 1; slab_kernels.hip) ------------------------------------------
   SlabState sl;
   static constexpr int real_dtype() { return sizeof(T) == 4 ? ADMP_T_F32 : ADMP_T_F64; }
   // Who owns what in this evaluation, derived by every rank from the replicated inputs (no communication): home atoms, home
   // rows in pair-kernel order, polarizable home atoms, imports per owner, exports per reader.  One host read (the counts).
-  void decompose() { decompose(K[0], X0, X1, nbr.order, lpol != 0); }
+  void decompose() { decompose(K[0], mc.X0, mc.X1, nbr.order, lpol != 0); }
   // K0v / X0v / X1v: the planes the ownership rule works on (the PME mesh's; a handle without a mesh takes a virtual one);
   // order: the row order of the table to filter (nullptr: natural order); with_dipoles: the evaluation carries induced
   // dipoles from call to call (atoms that change hands take theirs along)
@@ -713,7 +624,7 @@ struct Engine : EngineBase {
     int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
     for (int t = 0; t < snranks; ++t) { sc[t] = 3 * sl.mout_cnt[t]; rc[t] = 3 * sl.min_cnt[t]; }
     launch_halo_u_pack<T>(stream, sl.n_mout, 0, sl.mig_out.as<int>(), ev.U, sites.as<Site<T>>(), sl.sendb.as<T>());
-    c_all_to_all_v(sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
+    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
     launch_halo_u_unpack<T>(stream, sl.n_min, 0, sl.mig_in.as<int>(), sl.recvb.as<T>(), ev.U, sites.as<Site<T>>());
   }
   // rows of width w of the halo atoms: owners -> readers (to_readers: exports out, imports in) or back (gradient contributions)
@@ -730,7 +641,7 @@ struct Engine : EngineBase {
     int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
     halo_counts(3, true, sc, rc);
     launch_halo_u_pack<T>(stream, sl.n_exp, what, sl.exp.as<int>(), ev.U, sites.as<Site<T>>(), sl.sendb.as<T>());
-    c_all_to_all_v(sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
+    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
     launch_halo_u_unpack<T>(stream, sl.n_imp, what, sl.imp.as<int>(), sl.recvb.as<T>(), ev.U, sites.as<Site<T>>());
   }
   // what the closing kernel added to atoms of other ranks (frame adjoint of molecules across a slab face) goes to the owners
@@ -739,7 +650,7 @@ struct Engine : EngineBase {
     int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
     halo_counts(3, false, sc, rc);
     launch_rows_gather<T>(stream, sl.n_imp, 3, sl.imp.as<int>(), grad_p, sl.sendb.as<T>());
-    c_all_to_all_v(sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_GRADIENT);
+    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_GRADIENT);
     launch_rows_scatter<T>(stream, 1, sl.n_exp, 3, sl.exp.as<int>(), sl.recvb.as<T>(), grad_p);
   }
   void slab_home(int32_t* out, int* n_home, int* n_import) override {
@@ -779,184 +690,21 @@ struct Engine : EngineBase {
   }
   // the residual word of an SCF check: maximum over the ranks (bit patterns of non-negative doubles are doubles)
   void reduce_check_word(unsigned long long* word) {
-    if (snranks > 1) { TIMED("comm_scf_max"); c_all_reduce(word, 1, ADMP_T_F64, ADMP_OP_MAX, ADMP_TAG_SCF_MAX); }
+    if (snranks > 1) { TIMED("comm_scf_max"); comm.all_reduce(stream, word, 1, ADMP_T_F64, ADMP_OP_MAX, ADMP_TAG_SCF_MAX); }
   }
-  int nloc0() const { return snranks > 1 ? (X1 - X0) + kGhost : K[0]; }
-  int nxown() const { return snranks > 1 ? (X1 - X0) : K[0]; }
-  int nyown() const { return snranks > 1 ? (Y1 - Y0) : K[1]; }
+  int nloc0() const { return mc.nloc0(); }
 
-  // batched 2-D r2c / c2r plans over `batch` y-z planes stored back to back: real rows of K2 words, spectrum rows padded to
-  // fx_khp complex numbers (ensure_mesh: whole 128-byte lines on the fused-x path and on a slab rank, K2/2+1 otherwise)
-  void make_yz_plans(size_t batch, rocfft_plan* fwd, rocfft_plan* bwd) {
-    const rocfft_precision pr = sizeof(T) == 4 ? rocfft_precision_single : rocfft_precision_double;
-    const size_t len2[2] = {(size_t)K[2], (size_t)K[1]};
-    const size_t rs[2] = {1, (size_t)K[2]}, cs[2] = {1, (size_t)fx_khp};
-    const size_t rdist = (size_t)K[1] * K[2], cdist = (size_t)K[1] * fx_khp;
-    rocfft_plan_description df = nullptr, db = nullptr;
-    FFT_TRY(rocfft_plan_description_create(&df));
-    FFT_TRY(rocfft_plan_description_set_data_layout(df, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                    nullptr, 2, rs, rdist, 2, cs, cdist));
-    FFT_TRY(rocfft_plan_description_create(&db));
-    FFT_TRY(rocfft_plan_description_set_data_layout(db, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                                                    nullptr, 2, cs, cdist, 2, rs, rdist));
-    FFT_TRY(rocfft_plan_create(fwd, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 2, len2, batch, df));
-    FFT_TRY(rocfft_plan_create(bwd, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 2, len2, batch, db));
-    rocfft_plan_description_destroy(df);
-    rocfft_plan_description_destroy(db);
-  }
-  // twiddles of the fused x pass (fftx_kernels.hip): cos, sin of 2 pi m / K0 for the first half turn
-  void upload_fx_twiddles() {
-    std::vector<T> tw((size_t)K[0]);
-    for (int m = 0; m < K[0] / 2; ++m) {
-      const double th = 2.0 * M_PI * (double)m / (double)K[0];
-      tw[2 * m] = (T)std::cos(th);
-      tw[2 * m + 1] = (T)std::sin(th);
-    }
-    fx_tw.need(tw.size() * sizeof(T));
-    HIP_TRY(hipMemcpy(fx_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
-    use_fx = true;
-  }
-
+  // plans, spectrum and tables of the k-space leg (mc), then the local real mesh
   void ensure_mesh() {
-    update_slab();
-    const size_t K2h = (size_t)(K[2] / 2 + 1);
-    const size_t nreal = (size_t)nloc0() * K[1] * K[2];
-    size_t nspec = (size_t)nxown() * K[1] * K2h;
-    const size_t nspec_t = (size_t)K[0] * nyown() * K2h;
-    if (nspec_t > nspec) nspec = nspec_t;
-    // fused-x path: the kz rows of the spectrum are padded to whole 128-byte lines.  With K2/2+1 = 129 complex numbers per row
-    // every row of a tile straddles two lines; padded to 144, rocFFT's batched 2-D r2c / c2r of the 256^3 f32 mesh take
-    // 61 / 64 us instead of 88 / 91 (tools/ubench/rocfft_yz_layouts.cpp).
-    static const bool fx_off = !env_flag("ADMP_FUSED_X", true);
-    const bool want_fx = snranks == 1 && !fx_off && fftx_usable(K[0]);
-    const size_t per_line = 128 / (2 * sizeof(T));
-    // (a slab rank pads the rows of its batched 2-D transforms the same way; the transposes carry the unpadded rows)
-    const int khp = (want_fx || snranks > 1) ? (int)((K2h + per_line - 1) / per_line * per_line) : (int)K2h;
-    if ((size_t)nxown() * K[1] * khp > nspec) nspec = (size_t)nxown() * K[1] * khp;
-    mesh.need(nreal * sizeof(T));
-    spec.need(nspec * 2 * sizeof(T));
-    binv_d.need(9 * sizeof(double));
-    if (planK[0] == K[0] && planK[1] == K[1] && planK[2] == K[2] && planR == snranks && planRank == srank && plan_f) return;
-    fx_khp = khp;
-    destroy_plans();
-    std::call_once(g_fft_once, [] { rocfft_setup(); });
-    const rocfft_precision pr = sizeof(T) == 4 ? rocfft_precision_single : rocfft_precision_double;
-    size_t wmax = 0, w = 0;
-    if (snranks == 1) {
-      const size_t len[3] = {(size_t)K[2], (size_t)K[1], (size_t)K[0]};   // rocFFT: fastest dimension first
-      FFT_TRY(rocfft_plan_create(&plan_f, rocfft_placement_notinplace, rocfft_transform_type_real_forward, pr, 3, len, 1, nullptr));
-      FFT_TRY(rocfft_plan_create(&plan_b, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, pr, 3, len, 1, nullptr));
-      if (want_fx) {
-        make_yz_plans((size_t)K[0], &plan2_f, &plan2_b);
-        FFT_TRY(rocfft_plan_get_work_buffer_size(plan2_f, &w)); if (w > wmax) wmax = w;
-        FFT_TRY(rocfft_plan_get_work_buffer_size(plan2_b, &w)); if (w > wmax) wmax = w;
-        upload_fx_twiddles();
-      }
-    } else {
-      // distributed transform = batched 2-D r2c over the owned planes, all-to-all transpose (done by the caller over
-      // RCCL), batched strided 1-D c2c along x
-      make_yz_plans((size_t)nxown(), &plan_f, &plan_b);
-      const size_t len1[1] = {(size_t)K[0]};
-      const size_t stride[1] = {(size_t)nyown() * K2h};
-      const size_t batch = (size_t)nyown() * K2h;
-      for (int dir = 0; dir < 2; ++dir) {
-        rocfft_plan_description desc = nullptr;
-        FFT_TRY(rocfft_plan_description_create(&desc));
-        FFT_TRY(rocfft_plan_description_set_data_layout(desc, rocfft_array_type_complex_interleaved,
-                                                        rocfft_array_type_complex_interleaved, nullptr, nullptr, 1, stride, 1,
-                                                        1, stride, 1));
-        FFT_TRY(rocfft_plan_create(dir == 0 ? &plan_xf : &plan_xb, rocfft_placement_inplace,
-                                   dir == 0 ? rocfft_transform_type_complex_forward : rocfft_transform_type_complex_inverse,
-                                   pr, 1, len1, batch, desc));
-        FFT_TRY(rocfft_plan_description_destroy(desc));
-      }
-      FFT_TRY(rocfft_plan_get_work_buffer_size(plan_xf, &w)); if (w > wmax) wmax = w;
-      FFT_TRY(rocfft_plan_get_work_buffer_size(plan_xb, &w)); if (w > wmax) wmax = w;
-      if (!fx_off && fftx_usable(K[0])) upload_fx_twiddles();   // the fused x pass works on the transposed layout [K0][ny][K2/2+1] as well
-    }
-    FFT_TRY(rocfft_plan_get_work_buffer_size(plan_f, &w)); if (w > wmax) wmax = w;
-    FFT_TRY(rocfft_plan_get_work_buffer_size(plan_b, &w)); if (w > wmax) wmax = w;
-    fft_work.need(wmax + 16);
-    FFT_TRY(rocfft_execution_info_create(&info_f));
-    if (wmax) FFT_TRY(rocfft_execution_info_set_work_buffer(info_f, fft_work.p, wmax));
-    planK[0] = K[0]; planK[1] = K[1]; planK[2] = K[2]; planR = snranks; planRank = srank;
-    for (auto& k : tabkey) k.kappa = -1;   // mesh changed: tables stale
-    setup_dft();
+    mc.ensure(K);
+    mesh.need(mc.nreal_local() * sizeof(T));
   }
-
-  // Direct-DFT convolution (dft_kernels.hip) when rocFFT would need Bluestein for some dimension (largest prime factor
-  // above 13) and the mesh is small enough for O(N^2) lines.  ADMP_DFT=0 disables it, ADMP_DFT=1 forces it for any mesh
-  // with all dimensions <= 160 (tests).
-  void setup_dft() {
-    use_dft = use_pfa = false;
-    if (snranks != 1) return;
-    const int mode = env_int("ADMP_DFT", -1);      // (read at every set-up)
-    if (mode == 0) return;
-    bool small = true, hard = false;
-    for (int d = 0; d < 3; ++d) {
-      small = small && K[d] >= 2 && K[d] <= 160;
-      hard = hard || largest_prime_factor(K[d]) > 13;
-    }
-    if (mode == 2 && setup_pfa()) return;                 // tests: the split form for any mesh it can take
-    if (!small && hard && setup_pfa()) return;
-    if (!small || !(hard || mode == 1 || mode == 2)) return;
-    std::vector<T> tw(2 * (size_t)(K[0] + K[1] + K[2]));
-    size_t o = 0;
-    for (int d = 0; d < 3; ++d)
-      for (int m = 0; m < K[d]; ++m) {
-        const double th = 2.0 * M_PI * (double)m / (double)K[d];
-        tw[o++] = (T)std::cos(th);
-        tw[o++] = (T)std::sin(th);
-      }
-    dft_tw.need(tw.size() * sizeof(T));
-    HIP_TRY(hipMemcpy(dft_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
-    use_dft = true;
-  }
-  // Two-level direct DFT (pfa_kernels.hip): every dimension either fits the plain lines (<= 160) or splits into a smooth
-  // cofactor N1 <= 32 and a prime power N2 <= 160.  ADMP_DFT=2 forces it for any mesh it can split (tests); ADMP_PFA=0 off.
-  bool setup_pfa() {
-    static const bool off = !env_flag("ADMP_PFA", true);
-    if (off) return false;
-    for (int d = 0; d < 3; ++d)
-      if (!pfa_split(K[d], &pfa.ax[d])) return false;
-    pfa.Khp = pfa.ax[2].N1 * (pfa.ax[2].N2 / 2 + 1);
-    std::vector<T> tw;
-    for (int d = 0; d < 3; ++d) {
-      pfa.tw_off[d] = (int)(tw.size() / 2);
-      for (int n : {pfa.ax[d].N2, pfa.ax[d].N1})
-        for (int m = 0; m < n; ++m) {
-          const double th = 2.0 * M_PI * (double)m / (double)n;
-          tw.push_back((T)std::cos(th));
-          tw.push_back((T)std::sin(th));
-        }
-    }
-    pfa_tw.need(tw.size() * sizeof(T));
-    HIP_TRY(hipMemcpy(pfa_tw.p, tw.data(), tw.size() * sizeof(T), hipMemcpyHostToDevice));
-    std::vector<int> fm((size_t)K[0] + K[1] + pfa.Khp);
-    pfa_freq_of_slot(pfa.ax[0], fm.data());
-    pfa_freq_of_slot(pfa.ax[1], fm.data() + K[0]);
-    pfa_freq_of_zcolumn(pfa.ax[2], fm.data() + K[0] + K[1]);
-    pfa_fmap.need(fm.size() * sizeof(int));
-    HIP_TRY(hipMemcpy(pfa_fmap.p, fm.data(), fm.size() * sizeof(int), hipMemcpyHostToDevice));
-    std::vector<int> pt((size_t)K[0] + K[1] + K[2]);
-    pfa_index_table(pfa.ax[0], pt.data());
-    pfa_index_table(pfa.ax[1], pt.data() + K[0]);
-    pfa_index_table(pfa.ax[2], pt.data() + K[0] + K[1]);
-    pfa_ptab.need(pt.size() * sizeof(int));
-    HIP_TRY(hipMemcpy(pfa_ptab.p, pt.data(), pt.size() * sizeof(int), hipMemcpyHostToDevice));
-    pfa.ptab[0] = pfa_ptab.as<int>(); pfa.ptab[1] = pfa.ptab[0] + K[0]; pfa.ptab[2] = pfa.ptab[1] + K[1];
-    spec.need((size_t)K[0] * K[1] * pfa.Khp * 2 * sizeof(T));
-    use_pfa = true;
-    return true;
-  }
-  // mesh <- IFFT( G * FFT(mesh) ), energies[slot] += sum w G |S|^2 : the whole k-space leg of one reciprocal pass
-  // accum (optional): a second mesh the result is to be ADDED to; returns true when the last pass did that itself (the direct
-  // DFT writes every word once anyway), false when the caller still has to add
-  // out (optional, rocFFT paths): phi is written there instead of over mesh_p
-  // sp: the forward transform builds its planes from these sites (no spread kernel ran, mesh_p holds nothing yet): small
-  // double-precision systems on the direct-DFT plane kernels (spread_fused())
+  // the G table of `which` for this cell and the handle's kappa, left in mc.gtab_cur
+  void ensure_gtab(const double* box, const double* inv, double vol, int which) { mc.ensure_gtab(box, inv, vol, which, kappa, ref_korder); }
+  // sp of MeshConv::convolve: the forward transform builds its planes from the sites (no spread kernel ran): small
+  // double-precision systems on the direct-DFT plane kernels
   bool spread_fused(int n) const {
-    return use_dft && !use_pfa && snranks == 1 && !ev.home && dft_zy_spread_fits<T>(K, n);
+    return mc.can_take_riders() && !ev.home && dft_zy_spread_fits<T>(K, n);
   }
   PlaneSpread<T> plane_spread(int n, const Site<T>* rows, int lp, const int4* bases) const {
     PlaneSpread<T> sp;
@@ -966,7 +714,7 @@ struct Engine : EngineBase {
   // rider: an SCF field kernel whose workgroups run inside the x pass (pair_kernels.hip k_xconv_pair; direct-DFT meshes only)
   bool rider_ok() const {
     static const bool on = env_flag("ADMP_FIELD_RIDER", true);
-    return on && use_dft && !use_pfa && snranks == 1 && !overlap_ok();
+    return on && mc.can_take_riders() && !overlap_ok();
   }
   // pair rider: the closing pair kernel in the x pass (k_xconv_pair_full: small polarizable f64 systems).  ADMP_PAIR_RIDER=0
   // restores the launch of its own (read per call: the parity test runs both forms in one process); so does
@@ -974,167 +722,6 @@ struct Engine : EngineBase {
   bool pair_rider_ok() const {
     return lpol && side_stream_on && rider_ok() && env_flag("ADMP_PAIR_RIDER", true);
   }
-  // The distributed convolution of an x-slab rank around its x pass.  The stencils of the home atoms overhang into kGhost
-  // planes of the next rank (added there before the transform), the 3-D transform is batched 2-D r2c on the owned planes ->
-  // transpose (all-to-all over the ranks: every GPU exchanges a block with each of the others) -> xpass(tbuf, ny, nh): the x
-  // lines forward * G * inverse on the ny y rows this rank owns, nh complex numbers each -> transpose back -> 2-D c2r into
-  // mesh_o, and the gather needs the next rank's first planes of phi as its ghost planes.  Every rank makes the same
-  // collective calls in the same order.
-  template <class XPass>
-  void slab_convolve(T* mesh_p, T* spec_p, T* mesh_o, XPass&& xpass) {
-    const size_t plane = (size_t)K[1] * K[2];
-    const int nx = nxown(), ny = nyown(), nh = K[2] / 2 + 1;
-    sl.ghost.need(kGhost * plane * sizeof(T));
-    sl.pack.need((size_t)nx * K[1] * nh * 2 * sizeof(T));
-    sl.tbuf.need((size_t)K[0] * ny * nh * 2 * sizeof(T));
-    { TIMED("comm_ghost"); c_shift(mesh_p + (size_t)nx * plane, sl.ghost.p, (int64_t)(kGhost * plane), real_dtype(), 1, ADMP_TAG_GHOST); }
-    { TIMED("mesh_add"); launch_mesh_add<T>(stream, (long)(kGhost * plane), mesh_p, sl.ghost.as<T>()); }
-    fft_forward(mesh_p, spec_p);
-    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 0, spec_p, sl.pack.as<T>()); }
-    { TIMED("comm_transpose"); c_all_to_all_v(sl.pack.p, sl.tr_send, sl.tbuf.p, sl.tr_recv, real_dtype(), ADMP_TAG_TRANSPOSE); }
-    xpass(sl.tbuf.as<T>(), ny, nh);
-    { TIMED("comm_transpose"); c_all_to_all_v(sl.tbuf.p, sl.tr_recv, sl.pack.p, sl.tr_send, real_dtype(), ADMP_TAG_TRANSPOSE); }
-    { TIMED("transpose_pack"); launch_transpose_pack<T>(stream, nx, K[1], nh, fx_khp, snranks, 1, spec_p, sl.pack.as<T>()); }
-    fft_inverse(spec_p, mesh_o);
-    { TIMED("comm_ghost"); c_shift(mesh_o, mesh_o + (size_t)nx * plane, (int64_t)(kGhost * plane), real_dtype(), 0, ADMP_TAG_GHOST); }
-  }
-  bool convolve(T* mesh_p, T* spec_p, const T* gtab, int slot, T* accum = nullptr, T* out = nullptr,
-                const PlaneSpread<T>* sp = nullptr, const PairFieldArgs<T>* rider = nullptr, const PairFullArgs<T>* prider = nullptr) {
-    double* Ed = Ed_cur();
-    T* mesh_o = out ? out : mesh_p;
-    ARG_CHECK(!sp || (use_dft && !use_pfa && snranks == 1), "internal: plane spread on a transform path without it");
-    ARG_CHECK(!(rider && rider->kind) || (use_dft && !use_pfa && snranks == 1), "internal: field rider on a transform path without it");
-    ARG_CHECK(!(prider && prider->on) || (use_dft && !use_pfa && snranks == 1 && !(rider && rider->kind == 1)),
-              "internal: pair rider on a transform path without it");
-    if (snranks > 1) {
-      slab_convolve(mesh_p, spec_p, mesh_o, [&](T* tbuf, int ny, int nh) {
-        if (use_fx) {
-          TIMED("fftx_kspace");
-          launch_fftx_conv<T>(stream, K, fx_tw.as<T>(), tbuf, gtab, Ed, slot, nh, ny);
-        } else {
-          fft_x(tbuf, 0);
-          { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, tbuf, Ed, slot); }
-          fft_x(tbuf, 1);
-        }
-      });
-      (void)accum;
-      return false;
-    }
-    if (use_pfa) {
-      const T* tw = pfa_tw.as<T>();
-      { TIMED("dft_z_r2c"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 0); }
-      { TIMED("dft_y_fwd"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 0); }
-      DftTabs<T> tabs;
-      tabs.p[0] = gtab;
-      { TIMED("dft_x_kspace"); launch_pfa_x_conv<T>(stream, pfa, tw, spec_p, tabs, Ed, slot); }
-      { TIMED("dft_y_inv"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 1); }
-      { TIMED("dft_z_c2r"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 1); }
-      return false;
-    }
-    if (use_dft) {
-      const T* tw = dft_tw.as<T>();
-      const bool planes = dft_zy_fits<T>(K);         // z and y lines of a plane in one workgroup (dft_kernels.hip)
-      ARG_CHECK(!sp || planes, "internal: plane spread without the plane kernels");
-      int mf = 0;
-      if (planes && sp) { TIMED("dft_spread_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, sp, &mf); }
-      else if (planes) { TIMED("dft_zy_fwd"); launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 0, 1, 0, 0, nullptr, nullptr, &mf); }
-      if (planes) { ++plane_mfma_stats[mf ? 0 : 1]; ++plane_mfma_stats4[mf ? 0 : 1]; }
-      else {
-        { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 0); }
-        { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec_p, 0); }
-      }
-      DftTabs<T> tabs;
-      tabs.p[0] = gtab;
-      // G table of slot 0 even along x (every orthorhombic cell): one circulant product per line instead of two transforms
-      const T* ct = xctab_ok && gtab == gtabs[0].template as<T>() ? xctab.template as<T>() : nullptr;
-      ++xpass_stats[ct ? 0 : 1];
-      { TIMED("dft_x_kspace"); launch_dft_x_pass<T>(stream, K, tw, spec_p, tabs, Ed, slot, ct, rider, prider); }
-      bool added;
-      if (planes) {
-        TIMED("dft_yz_inv");
-        added = launch_dft_zy<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum, nullptr, &mf);
-        ++plane_mfma_stats[1];                       // (word [1] counts the inverse launches of either form)
-        ++plane_mfma_stats4[mf ? 2 : 3];
-      }
-      else {
-        { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec_p, 1); }
-        { TIMED("dft_z_c2r"); added = launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 1, 1, 0, 0, accum); }
-      }
-      return added;
-    }
-    if (use_fx) {      // rocFFT for the y-z planes, one fused kernel for x forward * G * x inverse
-      run_plan("rocfft_r2c_yz", plan2_f, mesh_p, spec_p);
-      { TIMED("fftx_kspace"); launch_fftx_conv<T>(stream, K, fx_tw.as<T>(), spec_p, gtab, Ed, slot, fx_khp); }
-      run_plan("rocfft_c2r_yz", plan2_b, spec_p, mesh_o);
-      return false;
-    }
-    fft_forward(mesh_p, spec_p);
-    { TIMED("kspace"); launch_kspace<T>(stream, K, nyown(), gtab, spec_p, Ed, slot); }
-    fft_inverse(spec_p, mesh_o);
-    return false;
-  }
-
-  // Batched y-z plans of the fused-x path for nb meshes at once (dispersion PME: C6 / C8 / C10): the same 2-D r2c / c2r
-  // plans with batch nb * K0 over meshes / spectra stored back to back -- two rocFFT executions per call instead of 2 nb.
-  rocfft_plan plan2n_f[4] = {nullptr, nullptr, nullptr, nullptr}, plan2n_b[4] = {nullptr, nullptr, nullptr, nullptr};
-  void ensure_batched_plans(int nb) {
-    ARG_CHECK(nb >= 2 && nb <= 3 && use_fx && snranks == 1, "internal: batched y-z plans");
-    if (plan2n_f[nb]) return;
-    make_yz_plans((size_t)nb * K[0], &plan2n_f[nb], &plan2n_b[nb]);
-    size_t w = 0, wmax = 0;
-    FFT_TRY(rocfft_plan_get_work_buffer_size(plan2n_f[nb], &w)); if (w > wmax) wmax = w;
-    FFT_TRY(rocfft_plan_get_work_buffer_size(plan2n_b[nb], &w)); if (w > wmax) wmax = w;
-    if (wmax + 16 > fft_work.bytes) {
-      HIP_TRY(hipStreamSynchronize(stream));
-      fft_work.need(wmax + 16);
-    }
-    if (fft_work.bytes > 16) FFT_TRY(rocfft_execution_info_set_work_buffer(info_f, fft_work.p, fft_work.bytes - 16));
-  }
-  // nb meshes at mesh_p + b * nreal -> phi_b in place; energies of all channels summed into energies[slot]
-  void convolve_batch(T* mesh_p, T* spec_p, const DftTabs<T>& tabs, int nb, size_t nreal, size_t nspec, int slot) {
-    ensure_batched_plans(nb);
-    run_plan("rocfft_r2c_yz", plan2n_f[nb], mesh_p, spec_p);
-    { TIMED("fftx_kspace");
-      launch_fftx_conv_batch<T>(stream, K, fx_tw.as<T>(), spec_p, tabs, nb, (long)nspec, Ed_cur(), slot, fx_khp); }
-    run_plan("rocfft_c2r_yz", plan2n_b[nb], spec_p, mesh_p);
-    (void)nreal;
-  }
-  // The same on a direct-DFT mesh (plain or two-level lines): five launches for the batch instead of five per mesh.  mix
-  // (plain lines only): the nb meshes are type meshes, the x pass forms the powers from them at every k (k_dft_x_mix).
-  void convolve_dft_batch(T* mesh_p, T* spec_p, const DftTabs<T>& tabs, int nb, size_t nreal, size_t nspec, int slot,
-                          const MixTab* mix = nullptr) {
-    double* Ed = Ed_cur();
-    if (use_pfa) {
-      const T* tw = pfa_tw.as<T>();
-      { TIMED("dft_z_r2c"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 0, nb, (long)nreal, (long)nspec); }
-      { TIMED("dft_y_fwd"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 0, nb, (long)nspec); }
-      { TIMED("dft_x_kspace"); launch_pfa_x_conv<T>(stream, pfa, tw, spec_p, tabs, Ed, slot, nb, (long)nspec); }
-      { TIMED("dft_y_inv"); launch_pfa_y<T>(stream, pfa, tw, spec_p, 1, nb, (long)nspec); }
-      { TIMED("dft_z_c2r"); launch_pfa_z<T>(stream, pfa, tw, mesh_p, spec_p, 1, nb, (long)nreal, (long)nspec); }
-      return;
-    }
-    const T* tw = dft_tw.as<T>();
-    { TIMED("dft_z_r2c"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 0, nb, (long)nreal, (long)nspec); }
-    { TIMED("dft_y_fwd"); launch_dft_y<T>(stream, K, tw, spec_p, 0, nb, (long)nspec); }
-    { TIMED("dft_x_kspace");
-      if (mix) launch_dft_x_mix<T>(stream, K, tw, spec_p, tabs, *mix, (long)nspec, Ed, slot);
-      else launch_dft_x_conv<T>(stream, K, tw, spec_p, tabs, Ed, slot, nb, (long)nspec); }
-    { TIMED("dft_y_inv"); launch_dft_y<T>(stream, K, tw, spec_p, 1, nb, (long)nspec); }
-    { TIMED("dft_z_c2r"); launch_dft_z<T>(stream, K, tw, mesh_p, spec_p, 1, nb, (long)nreal, (long)nspec); }
-  }
-
-  void run_plan(const char* label, rocfft_plan plan, void* in, void* out) {
-    TIMED(label);
-    FFT_TRY(rocfft_execution_info_set_stream(info_f, stream));
-    void* i[1] = {in};
-    void* o[1] = {out};
-    FFT_TRY(rocfft_execute(plan, i, o, info_f));
-  }
-  // real mesh (owned planes) <-> half spectrum in `spec`: full 3-D transform (1 rank) or its y-z part (slabs)
-  void fft_forward(T* mesh_p, T* spec_p) { run_plan("rocfft_r2c", plan_f, mesh_p, spec_p); }
-  void fft_inverse(T* spec_p, T* mesh_p) { run_plan("rocfft_c2r", plan_b, spec_p, mesh_p); }
-  void fft_x(T* buf, int inverse) { run_plan(inverse ? "rocfft_x_inv" : "rocfft_x_fwd", inverse ? plan_xb : plan_xf, buf, buf); }
-
   Box<T> make_box(const double* h, double* inv, double* vol) { return admp::make_box<T>(h, inv, vol); }
 
   RecipGeom<T> make_geom(const double* inv) {
@@ -1149,108 +736,47 @@ struct Engine : EngineBase {
         g.Jac[3 * i + j] = (T)(-(double)K[j] * inv[3 * i + j]);   // d u_j / d x_i     (admp/recip.py:75-77)
       }
     g.whole_mesh();
-    if (snranks > 1) { g.xoff = X0; g.nloc0 = nloc0(); g.wrap0 = 1 << 30; }
+    if (snranks > 1) { g.xoff = mc.X0; g.nloc0 = nloc0(); g.wrap0 = 1 << 30; }
     return g;
   }
 
-  void ensure_gtab(const double* box, const double* inv, double vol, int which) {
-    const int slot = tab_slot(which);
-    TabKey& key = tabkey[slot];
-    DevBuf& buf = gtabs[slot];
-    const size_t nspec_t = (size_t)K[0] * nyown() * (use_pfa ? pfa.Khp : K[2] / 2 + 1);
-    buf.need(nspec_t * sizeof(T));
-    gtab_cur = buf.template as<T>();
-    bool same = key.kappa == kappa && key.K[0] == K[0] && key.K[1] == K[1] && key.K[2] == K[2] &&
-                key.Y0 == (snranks > 1 ? Y0 : 0) && key.ref == ref_korder && key.pfa == use_pfa;
-    for (int k = 0; k < 9 && same; ++k) same = key.box[k] == box[k];
-    if (same) return;
-    HIP_TRY(hipMemcpyAsync(binv_d.p, inv, 9 * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));   // `inv` is a caller stack array
-    {
-      TIMED("gtab");
-      launch_gtab<T>(stream, K, snranks > 1 ? Y0 : 0, nyown(), binv_d.as<double>(), std::fabs(vol), kappa, which, gtab_cur, ref_korder,
-                     use_pfa ? pfa_fmap.as<int>() : nullptr, use_pfa ? pfa.Khp : 0);
-    }
-    std::memcpy(key.box, box, sizeof(key.box));
-    key.kappa = kappa; key.K[0] = K[0]; key.K[1] = K[1]; key.K[2] = K[2]; key.Y0 = snranks > 1 ? Y0 : 0; key.ref = ref_korder;
-    key.pfa = use_pfa;
-    if (slot == 0) {
-      xctab_ok = false;
-      if (use_dft && !use_pfa && snranks == 1 && xcirc_on()) {
-        xctab.need((size_t)(K[0] / 2 + 1) * K[1] * (K[2] / 2 + 1) * sizeof(T));
-        xctab_flag.need(sizeof(int));
-        HIP_TRY(hipMemsetAsync(xctab_flag.p, 0, sizeof(int), stream));
-        { TIMED("xcirc_table"); launch_ctab<T>(stream, K, gtab_cur, xctab.as<T>(), xctab_flag.as<int>()); }
-        int uneven = 1;
-        HIP_TRY(hipMemcpyAsync(&uneven, xctab_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        xctab_ok = uneven == 0;
-      }
-    }
-  }
-
-  // admp_mesh_convolve: the k-space leg alone on a mesh of the caller's -- ensure_mesh, the handle's own G table, convolve():
+  // admp_mesh_convolve: the k-space leg alone on a mesh of the caller's -- ensure_mesh, the handle's own G table, mc.convolve():
   // what an evaluation runs between its spread and its gather, without riders or plane spread (tests feed it meshes)
   void mesh_convolve(const double* box, int which, void* data_, int on_device, double* E_out, int32_t* info) override {
-    ARG_CHECK(have_ewald, "admp_set_ewald first");
-    ARG_CHECK(snranks == 1, "admp_mesh_convolve works on a single rank only (slab-decomposed handle)");
-    ARG_CHECK(box && data_ && E_out && info, "null argument");
-    ARG_CHECK(which == 1 || which == 6 || which == 8 || which == 10, "which must be 1, 6, 8 or 10");
-    double inv[9], vol;
-    make_box(box, inv, &vol);
-    ensure_mesh();
-    ensure_gtab(box, inv, vol, which);
-    const size_t nreal = (size_t)K[0] * K[1] * K[2];
-    T* m = on_device ? reinterpret_cast<T*>(data_) : mesh.as<T>();
-    if (!on_device) HIP_TRY(hipMemcpyAsync(m, data_, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
-    energies_d.need(2 * E_WORDS * sizeof(double));
-    ehalf = 0; other_clean = false;
-    HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
-    const int64_t circ0 = xpass_stats[0];
-    convolve(m, spec.as<T>(), gtab_cur, E_RECIP);
-    if (!on_device) HIP_TRY(hipMemcpyAsync(data_, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(E_out, Ed_cur() + E_RECIP, sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (int k = 0; k < ADMP_MESH_INFO_WORDS; ++k) info[k] = 0;
-    if (use_pfa) {
-      info[0] = ADMP_MESH_PATH_TWO_LEVEL;
-      int forms[9];
-      pfa_forms(pfa, sizeof(T), forms);
-      for (int d = 0; d < 3; ++d) { info[2 + d] = pfa.ax[d].N1; info[5 + d] = pfa.ax[d].N2; info[12 + d] = forms[3 * d + 1]; }
-      info[8] = forms[0]; info[9] = forms[3]; info[10] = forms[6]; info[11] = forms[8];
-    } else if (use_dft) {
-      info[0] = dft_zy_fits<T>(K) ? ADMP_MESH_PATH_DIRECT_PLANES : ADMP_MESH_PATH_DIRECT_LINES;
-      info[1] = xpass_stats[0] > circ0 ? 1 : 2;
-    } else {
-      info[0] = use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT;
-    }
+    mesh_convolve_on(snranks == 1, "admp_mesh_convolve works on a single rank only (slab-decomposed handle)", box, which, data_,
+                     on_device, E_out, info);
   }
-
   // admp_slab_mesh_convolve: the same leg on a slab rank -- its local mesh as an evaluation holds it between spread and gather
-  // (own planes, then the kGhost overhang planes meant for the next rank), through ensure_mesh, ensure_gtab and convolve(),
-  // which is slab_convolve with the x pass this handle takes; every rank of the communicator makes the call
+  // (own planes, then the kGhost overhang planes meant for the next rank); mc.convolve() is then the distributed convolution
+  // with the x pass this handle takes; every rank of the communicator makes the call
   void slab_mesh_convolve(const double* box, int which, void* data_, int on_device, double* E_out, int32_t* info) override {
+    mesh_convolve_on(snranks > 1, "admp_slab_mesh_convolve works on a slab-decomposed handle only (single rank: admp_mesh_convolve)",
+                     box, which, data_, on_device, E_out, info);
+  }
+  void mesh_convolve_on(bool right_handle, const char* wrong_handle, const double* box, int which, void* data_, int on_device,
+                        double* E_out, int32_t* info) {
     ARG_CHECK(have_ewald, "admp_set_ewald first");
-    ARG_CHECK(snranks > 1, "admp_slab_mesh_convolve works on a slab-decomposed handle only (single rank: admp_mesh_convolve)");
+    ARG_CHECK(right_handle, wrong_handle);
     ARG_CHECK(box && data_ && E_out && info, "null argument");
     ARG_CHECK(which == 1 || which == 6 || which == 8 || which == 10, "which must be 1, 6, 8 or 10");
     double inv[9], vol;
     make_box(box, inv, &vol);
     ensure_mesh();
     ensure_gtab(box, inv, vol, which);
-    const size_t nreal = (size_t)nloc0() * K[1] * K[2];
+    const size_t nreal = nreal_local();
     T* m = on_device ? reinterpret_cast<T*>(data_) : mesh.as<T>();
     if (!on_device) HIP_TRY(hipMemcpyAsync(m, data_, nreal * sizeof(T), hipMemcpyHostToDevice, stream));
     energies_d.need(2 * E_WORDS * sizeof(double));
     ehalf = 0; other_clean = false;
     HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
-    convolve(m, spec.as<T>(), gtab_cur, E_RECIP);
+    const int64_t circ0 = mesh_stats.xpass[0];
+    mc.convolve(m, mc.gtab_cur, Ed_cur(), E_RECIP);
     if (!on_device) HIP_TRY(hipMemcpyAsync(data_, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(E_out, Ed_cur() + E_RECIP, sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (int k = 0; k < ADMP_MESH_INFO_WORDS; ++k) info[k] = 0;
-    info[0] = use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT;
-    info[2] = X0; info[3] = X1; info[4] = Y0; info[5] = Y1; info[6] = fx_khp; info[7] = K[2] / 2 + 1;
+    mc.fill_info(info);      // the path; two-level: split and forms; slab rank: its bounds
+    if (mc.direct()) info[1] = mesh_stats.xpass[0] > circ0 ? 1 : 2;
   }
 
   ScaleTab<T> make_tab(int ns, const double* mS, const double* pS) {
@@ -1759,7 +1285,7 @@ struct Engine : EngineBase {
     }
     reduce_check_word(word);
   }
-  size_t nreal_local() const { return (size_t)nloc0() * K[1] * K[2]; }
+  size_t nreal_local() const { return mc.nreal_local(); }
   // check_word: the zero word the check after this increment writes (its residual then rides in the field gather)
   // extra_side: more work for the side stream of this increment (the closing pair kernel of a chained call, whose dipoles are final)
   // field_from_total_phi: do not gather the increment's field -- the caller's next kernel is a full gather of the accumulated
@@ -1814,7 +1340,7 @@ struct Engine : EngineBase {
     const PlaneSpread<T> sp = plane_spread(n_act, isites.as<Site<T>>(), 1, nullptr);
     PairFullArgs<T> pr;
     const bool full_rides = full_grad && pair_full_rider(pr, full_grad);
-    const bool added = convolve(mesh2.as<T>(), spec.as<T>(), gtab_cur, E_SCRATCH, mesh.as<T>(), nullptr, fused ? &sp : nullptr,
+    const bool added = mc.convolve(mesh2.as<T>(), mc.gtab_cur, Ed_cur(), E_SCRATCH, mesh.as<T>(), nullptr, fused ? &sp : nullptr,
                                 ride ? &fr : nullptr, full_rides ? &pr : nullptr);
     join_side();
     if (!field_from_total_phi && !no_field) {
@@ -1833,7 +1359,7 @@ struct Engine : EngineBase {
     if (summed) {
       TIMED("comm_energies");
       launch_energy_pack(stream, Ed_cur(), recip_slot, Ed_cur() + E_RED);
-      c_all_reduce(Ed_cur() + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
+      comm.all_reduce(stream, Ed_cur() + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
     }
     HIP_TRY(hipMemcpyAsync(Eh, Ed_cur(), E_WORDS * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1878,7 +1404,7 @@ struct Engine : EngineBase {
     if (!slot_clean[slot]) HIP_TRY(hipMemsetAsync(Ed_cur() + slot, 0, sizeof(double), stream));
     slot_clean[slot] = false;
     const PlaneSpread<T> sp = plane_spread(ev.n_home, sites.as<Site<T>>(), lpol, ev.bases);
-    convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, slot, nullptr, nullptr, fused ? &sp : nullptr, rider, prider);
+    mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), slot, nullptr, nullptr, fused ? &sp : nullptr, rider, prider);
   }
   // reciprocal pass + closing pair kernel (gradient rows grad_p; fld_out: its dE/dU as well): in the x pass, or next to
   // the mesh chain on the side stream / ahead of it on this one
@@ -2302,41 +1828,22 @@ struct Engine : EngineBase {
         out[3 * a + b] = v;
       }
   }
-  // spread -> r2c -> k-tensor sums -> G multiply (+energy) -> c2r, always through rocFFT (the fused direct-DFT x pass
-  // never holds the bare spectrum)
+  // spread -> r2c -> k-tensor sums -> G multiply (+energy) -> c2r, always through rocFFT (MeshConv::convolve_virial: the
+  // fused direct-DFT x pass never holds the bare spectrum)
   void recip_pass_virial(int slot, int which, double vol, double* acc, int reuse_bins = 0, int lpol_sites = -1) {
     need_eval_or_disp();
     { TIMED("spread"); spread_sites(vs_n, vs_sites, lpol_sites < 0 ? lpol : lpol_sites, vs_g, mesh.as<T>(), nullptr, 1, reuse_bins); }
-    fft_forward(mesh.as<T>(), spec.as<T>());
-    launch_kspace_virial<T>(stream, K, binv_d.as<double>(), std::fabs(vol), kappa, which, ref_korder, spec.as<T>(), acc + V_TK);
-    const T* gt = gtab_cur;
-    if (use_pfa) {   // this pass goes through rocFFT: it needs the table in the natural layout, not the slot-ordered one
-      gtab_nat.need((size_t)K[0] * K[1] * (K[2] / 2 + 1) * sizeof(T));
-      launch_gtab<T>(stream, K, 0, K[1], binv_d.as<double>(), std::fabs(vol), kappa, which, gtab_nat.as<T>(), ref_korder);
-      gt = gtab_nat.as<T>();
-    }
-    { TIMED("kspace"); launch_kspace<T>(stream, K, nyown(), gt, spec.as<T>(), Ed_cur(), slot); }
-    fft_inverse(spec.as<T>(), mesh.as<T>());
+    mc.convolve_virial(mesh.as<T>(), mc.gtab_cur, Ed_cur(), slot, which, vol, kappa, ref_korder, acc + V_TK);
   }
   int vs_n = 0; const Site<T>* vs_sites = nullptr; RecipGeom<T> vs_g;
   void need_eval_or_disp() { ARG_CHECK(vs_sites != nullptr, "internal: virial pass without sites"); }
-  void upload_binv(const double* inv) {
-    HIP_TRY(hipMemcpyAsync(binv_d.p, inv, 9 * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));   // `inv` is a caller stack array
-  }
-
+  void upload_binv(const double* inv) { mc.upload_binv(inv); }
   // The same on a slab rank (round 4): the pair / gather / frame sums run over the rank's home rows and atoms, the k-tensor
   // sums over the y rows it holds of the transposed spectrum (between the x transforms of the distributed convolution, which
   // therefore takes the unfused x passes here), and the 24 device words are summed over the ranks before the host folds
   // them -- every rank returns the full dE/dbox.
-  void convolve_slab_virial(T* mesh_p, T* spec_p, const T* gtab, int slot, int which, double vol, double* acc) {
-    double* Ed = Ed_cur();
-    slab_convolve(mesh_p, spec_p, mesh_p, [&](T* tbuf, int ny, int) {
-      fft_x(tbuf, 0);
-      launch_kspace_virial<T>(stream, K, binv_d.as<double>(), std::fabs(vol), kappa, which, ref_korder, tbuf, acc + V_TK, Y0, ny);
-      { TIMED("kspace"); launch_kspace<T>(stream, K, ny, gtab, tbuf, Ed, slot); }
-      fft_x(tbuf, 1);
-    });
+  void convolve_slab_virial(T* mesh_p, int which, double vol, double* acc) {
+    mc.convolve_slab_virial(mesh_p, mc.gtab_cur, Ed_cur(), E_RECIP, which, vol, kappa, ref_korder, acc + V_TK);
   }
   void pme_box_grad(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
                     const double* mS, const double* pS, const void* U_, double* E, double* dbox) override {
@@ -2359,7 +1866,7 @@ struct Engine : EngineBase {
     else { vs_n = na; vs_sites = sites.as<Site<T>>(); vs_g = ev.g; }
     if (!slot_clean[E_RECIP]) HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
     slot_clean[E_RECIP] = false;
-    if (slab) convolve_slab_virial(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP, 1, vol, acc);
+    if (slab) convolve_slab_virial(mesh.as<T>(), 1, vol, acc);
     else recip_pass_virial(E_RECIP, 1, vol, acc);
     // (one rank: ev.home is null and ev.n_home the atom count)
     stage_gather(mesh.as<T>(), gbuf);
@@ -2371,7 +1878,7 @@ struct Engine : EngineBase {
     // by the kernel itself)
     stage_finish(nullptr, nullptr, E_RECIP, E);
     vs_sites = nullptr;
-    if (slab) { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
+    if (slab) { TIMED("comm_energies"); comm.all_reduce(stream, acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     vir_assemble(inv, E[1], dbox);
     scf.forget();
   }
@@ -2389,7 +1896,7 @@ struct Engine : EngineBase {
     ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
     double* acc = vir_begin();
     cls_sites_na = slab_sites_na = -1;
-    const ScalarRows sr = scalar_rows(pos, g, K[0], X0, X1, true);
+    const ScalarRows sr = scalar_rows(pos, g, K[0], mc.X0, mc.X1, true);
     launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, sr.rows, sr.n, cutoff);
     launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff, sr.rows, sr.n);
     const int nch = (pmax - 4) / 2;
@@ -2402,13 +1909,13 @@ struct Engine : EngineBase {
     for (int c = 0; c < nch; ++c) {
       ensure_gtab(box, sc.inv, sc.vol, 6 + 2 * c);
       upload_binv(sc.inv);
-      convolve_slab_virial(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP, 6 + 2 * c, sc.vol, acc);
+      convolve_slab_virial(mesh.as<T>() + c * nreal, 6 + 2 * c, sc.vol, acc);
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, 0.0, sites.as<Site<T>>(), scratchE);
       launch_gather_virial<T>(stream, sr.n, sites.as<Site<T>>(), 0, g, mesh.as<T>() + c * nreal, acc + V_XW, acc + V_Y, sr.home);
     }
     launch_scalar_self<T>(stream, nch, sr.n, cl, 3, sr.home, disp_kp().data(), Ed);
     read_scalar_energies(Ed, E, 3);
-    { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
+    { TIMED("comm_energies"); comm.all_reduce(stream, acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     vir_assemble(sc.inv, E[1], dbox);
   }
 
@@ -2462,7 +1969,7 @@ struct Engine : EngineBase {
     launch_tt_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff);
     launch_scalar_pair_virial<T>(stream, 1, na, nbr, sc.pos, sc.par, sc.bx, sc.tab, T(0), 0, acc + V_XW, cutoff, sr.rows, sr.n);
     read_scalar_energies(sc.Ed, E, 1);
-    if (snranks > 1) { TIMED("comm_energies"); c_all_reduce(acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
+    if (snranks > 1) { TIMED("comm_energies"); comm.all_reduce(stream, acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     vir_assemble(sc.inv, 0.0, dbox);      // only the xw sums are non-zero here
   }
 
@@ -2545,11 +2052,11 @@ struct Engine : EngineBase {
     // the search then costs the rank its share of the box, not the box.  ADMP_SLAB_ROWS=0: every row on every rank.
     RowFilter rf;
     static const bool rows_on = env_flag("ADMP_SLAB_ROWS", true);
-    if (rows_on && snranks > 1 && have_ewald && have_comm) {
+    if (rows_on && snranks > 1 && have_ewald && comm.have) {
       update_slab();
       const int mp = (int)std::ceil(0.5 * rc / (heights[0] / K[0])) + 4;
-      const int width = (X1 - X0) + 2 * mp;
-      if (width < K[0]) { rf.on = 1; rf.K0 = K[0]; rf.lo = ((X0 - mp) % K[0] + K[0]) % K[0]; rf.width = width; }
+      const int width = (mc.X1 - mc.X0) + 2 * mp;
+      if (width < K[0]) { rf.on = 1; rf.K0 = K[0]; rf.lo = ((mc.X0 - mp) % K[0] + K[0]) % K[0]; rf.width = width; }
     }
     TIMED("neighbor_table");
     int r = cell_build_table<T>(stream, top, reinterpret_cast<const T*>(pos), b, heights, rc, cells, nbr, rf);
@@ -2563,7 +2070,7 @@ struct Engine : EngineBase {
   void slab_info(int64_t* o) override {
     ARG_CHECK(have_ewald, "admp_set_ewald first");
     update_slab();
-    o[0] = X0; o[1] = X1; o[2] = Y0; o[3] = Y1; o[4] = nloc0(); o[5] = kGhost; o[6] = K[0]; o[7] = K[1]; o[8] = K[2] / 2 + 1;
+    o[0] = mc.X0; o[1] = mc.X1; o[2] = mc.Y0; o[3] = mc.Y1; o[4] = nloc0(); o[5] = kGhost; o[6] = K[0]; o[7] = K[1]; o[8] = K[2] / 2 + 1;
     o[9] = srank; o[10] = snranks;
   }
   DevBuf srow_d;      // packed (position, parameters) rows of the scalar pair kernels, rebuilt per call
@@ -2578,7 +2085,7 @@ struct Engine : EngineBase {
     if (snranks > 1) {
       TIMED("comm_energies");
       launch_energy_pack(stream, Ed, E_RECIP, Ed + E_RED);
-      c_all_reduce(Ed + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
+      comm.all_reduce(stream, Ed + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
     }
     HIP_TRY(hipMemcpyAsync(Eh2, Ed, sizeof(Eh2), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -2605,7 +2112,7 @@ struct Engine : EngineBase {
   }
   // ... of a pair potential on a slab rank: it has no mesh, so ownership goes by x-slabs of a virtual one of 64 planes per rank
   ScalarRows virtual_slab_rows(const T* pos, const double* inv) {
-    ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
+    ARG_CHECK(comm.have, "slab-decomposed handle without a communicator (admp_set_comm)");
     RecipGeom<T> g;
     const int Kv = 64 * snranks;
     g.K[0] = Kv; g.K[1] = g.K[2] = 32;
@@ -2670,7 +2177,7 @@ struct Engine : EngineBase {
   // the G tables of the first nch powers
   DftTabs<T> disp_tabs(const double* box, const double* inv, double vol, int nch) {
     DftTabs<T> tabs;
-    for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = gtab_cur; }
+    for (int c = 0; c < nch; ++c) { ensure_gtab(box, inv, vol, 6 + 2 * c); tabs.p[c] = mc.gtab_cur; }
     return tabs;
   }
   // ONE binning and ONE spread of nmesh meshes straight from the caller's arrays (disp_kernels.hip): one mesh per power from
@@ -2730,19 +2237,15 @@ struct Engine : EngineBase {
   // ONE gather per atom
   void disp_bricks_typed(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
     const int nt = disp_nt;
-    const size_t nreal = nreal_local(), nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
+    const size_t nreal = nreal_local(), nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
     ensure_bins(std::max(sr.n, 1));
     const MixTab mix = disp_mix(nch);
     launch_types_check<T>(stream, top.na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
     mesh.need((size_t)std::max(nt, nch) * nreal * sizeof(T));
-    spec.need((size_t)nt * nspec * sizeof(T));
+    mc.need_spectrum((size_t)nt * nspec * sizeof(T));
     { TIMED("spread"); spread_bricks(sr, g, nt, sc.pos, nullptr, disp_types); }
     const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
-    if (nt >= 2) ensure_batched_plans(nt);
-    run_plan("rocfft_r2c_yz", nt >= 2 ? plan2n_f[nt] : plan2_f, mesh.p, spec.p);
-    { TIMED("fftx_kspace");
-      launch_fftx_mix<T>(stream, K, fx_tw.as<T>(), spec.as<T>(), tabs, mix, (long)nspec, sc.Ed, E_RECIP, fx_khp); }
-    run_plan("rocfft_c2r_yz", nt >= 2 ? plan2n_b[nt] : plan2_b, spec.p, mesh.p);
+    mc.convolve_mix(mesh.as<T>(), tabs, mix, nt, nspec, sc.Ed, E_RECIP);
     { TIMED("gather_field");
       launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par, 3, g, mesh.as<T>(), (long)nreal, sc.dpos, sr.home, 0, disp_types); }
   }
@@ -2760,18 +2263,18 @@ struct Engine : EngineBase {
     ensure_bins(std::max(sr.n, 1));
     { TIMED("spread"); spread_bricks(sr, g, nch, sc.pos, sc.par, nullptr); }
     if (batched) {
-      const size_t nspec = 2 * (size_t)K[0] * K[1] * fx_khp;
-      spec.need(nch * nspec * sizeof(T));
+      const size_t nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
+      mc.need_spectrum(nch * nspec * sizeof(T));
       mesh2.need(nch * nreal * sizeof(T));
       const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
-      convolve_batch(mesh.as<T>(), spec.as<T>(), tabs, nch, nreal, nspec, E_RECIP);
+      mc.convolve_batch(mesh.as<T>(), tabs, nch, nspec, Ed_cur(), E_RECIP);
       { TIMED("interleave"); launch_interleave<T>(stream, nch, (long)nreal, mesh.as<T>(), (long)nreal, mesh2.as<T>()); }
       { TIMED("gather_field");
         launch_gather_scalar<T>(stream, nch, sr.n, sc.pos, sc.par, 3, g, mesh2.as<T>(), (long)nreal, sc.dpos, sr.home, 1); }
     } else
     for (int c = 0; c < nch; ++c) {
       ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
-      convolve(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP);
+      mc.convolve(mesh.as<T>() + c * nreal, mc.gtab_cur, Ed_cur(), E_RECIP);
       TIMED("gather_field");
       launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par + c, 3, g, mesh.as<T>() + c * nreal, (long)nreal, sc.dpos, sr.home);
     }
@@ -2797,7 +2300,7 @@ struct Engine : EngineBase {
     launch_types_check<T>(stream, na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
     const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (K[2] / 2 + 1);
     mesh.need(nt * nreal * sizeof(T));
-    spec.need(nt * nspec * sizeof(T));
+    mc.need_spectrum(nt * nspec * sizeof(T));
     onehot_d.need((size_t)na * nt * sizeof(T));
     bases_d.need(sizeof(int4) * (size_t)na);
     const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
@@ -2810,7 +2313,7 @@ struct Engine : EngineBase {
       launch_scalar_sites_batch<T>(stream, na, sc.pos, onehot_d.as<T>(), nt, nt, no_self, sites.as<Site<T>>(), sc.Ed, &g,
                                    bases_d.as<int4>()); }
     { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), nt); }
-    convolve_dft_batch(mesh.as<T>(), spec.as<T>(), tabs, nt, nreal, nspec, E_RECIP, &mix);
+    mc.convolve_dft_batch(mesh.as<T>(), tabs, nt, nreal, nspec, Ed_cur(), E_RECIP, &mix);
     { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nt); }
     { TIMED("scale_add"); launch_scale_add<T>(stream, na, onehot_d.as<T>(), nt, 0, fld_recip.as<T>(), sc.dpos, nt); }
   }
@@ -2820,9 +2323,9 @@ struct Engine : EngineBase {
     const int na = top.na;
     const std::array<double, 3> kp = disp_kp();
     const RecipGeom<T> gj = disp_site_rows(g, nch);
-    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (use_pfa ? pfa.Khp : K[2] / 2 + 1);
+    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_columns();
     mesh.need(nch * nreal * sizeof(T));
-    spec.need(nch * nspec * sizeof(T));
+    mc.need_spectrum(nch * nspec * sizeof(T));
     const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
     if (!spread_uses_bricks(na, g)) {        // the scan-spread regime takes the powers as a batch
       // the stencil records ride along: every (brick, power) workgroup of the scan spread reads them instead of
@@ -2839,7 +2342,7 @@ struct Engine : EngineBase {
         spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>() + c * nreal, nullptr, 1, c > 0);
       }
     }
-    convolve_dft_batch(mesh.as<T>(), spec.as<T>(), tabs, nch, nreal, nspec, E_RECIP);
+    mc.convolve_dft_batch(mesh.as<T>(), tabs, nch, nreal, nspec, Ed_cur(), E_RECIP);
     // the site rows hold the positions (only the charge slot differs per power): one gather over the batch of meshes
     { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nch); }
     { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, 0, fld_recip.as<T>(), sc.dpos, nch); }
@@ -2853,7 +2356,7 @@ struct Engine : EngineBase {
       ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
       { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, sc.pos, sc.par, 3, c, kp[c], sites.as<Site<T>>(), sc.Ed); }
       { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0); }
-      convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP);
+      mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), E_RECIP);
       { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr); }
       { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, c, fld_recip.as<T>(), sc.dpos); }
     }
@@ -2871,7 +2374,7 @@ struct Engine : EngineBase {
     const int nch = (pmax - 4) / 2;
     cls_sites_na = slab_sites_na = -1;   // other rows than an electrostatics evaluation's
     DispPathIn in;
-    in.snranks = snranks; in.use_dft = use_dft; in.use_pfa = use_pfa; in.use_fx = use_fx;
+    in.snranks = snranks; in.use_dft = mc.direct(); in.use_pfa = mc.path() == MeshPath::TwoLevel; in.use_fx = mc.fused_x();
     in.bricks = spread_uses_bricks(na, g);
     in.single_precision = sizeof(T) == 4;
     in.nch = nch; in.disp_nt = disp_nt; in.have_types = disp_types != nullptr;
@@ -2880,7 +2383,7 @@ struct Engine : EngineBase {
     const bool bricks = path == DispPath::BricksTyped || path == DispPath::BricksBatched || path == DispPath::BricksPerPower;
     const bool typed = path == DispPath::BricksTyped || path == DispPath::DftTyped;
     if (snranks > 1) ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
-    const ScalarRows sr = scalar_rows(sc.pos, g, K[0], X0, X1, bricks);
+    const ScalarRows sr = scalar_rows(sc.pos, g, K[0], mc.X0, mc.X1, bricks);
     { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
     switch (path) {
       case DispPath::BricksTyped: disp_bricks_typed(sc, g, sr, nch); break;
@@ -2948,7 +2451,7 @@ struct Engine : EngineBase {
     if (snranks > 1) {      // slab rank (round 4): pair sums over its home rows, the channels' mesh potentials at its home atoms
       ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
       cls_sites_na = slab_sites_na = -1;
-      const ScalarRows sr = scalar_rows(pos, g, K[0], X0, X1, true);
+      const ScalarRows sr = scalar_rows(pos, g, K[0], mc.X0, mc.X1, true);
       launch_scalar_pair_pgrad<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, out, cutoff, sr.rows, sr.n);
       const size_t nreal = nreal_local();
       mesh.need(nch * nreal * sizeof(T));
@@ -2956,7 +2459,7 @@ struct Engine : EngineBase {
       spread_bricks(sr, g, nch, pos, cl, nullptr);
       for (int c = 0; c < nch; ++c) {
         ensure_gtab(box, inv, vol, 6 + 2 * c);
-        convolve(mesh.as<T>() + c * nreal, spec.as<T>(), gtab_cur, E_RECIP);
+        mc.convolve(mesh.as<T>() + c * nreal, mc.gtab_cur, Ed_cur(), E_RECIP);
         launch_gather_value<T>(stream, sr.n, pos, cl, 3, c, g, mesh.as<T>() + c * nreal, 2.0 * kp[c], out, sr.home);
       }
       HIP_TRY(hipStreamSynchronize(stream));
@@ -2970,7 +2473,7 @@ struct Engine : EngineBase {
       ensure_gtab(box, inv, vol, 6 + 2 * c);
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed);
       spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0);
-      convolve(mesh.as<T>(), spec.as<T>(), gtab_cur, E_RECIP);
+      mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), E_RECIP);
       launch_gather_value<T>(stream, na, pos, cl, 3, c, g, mesh.as<T>(), 2.0 * kp[c], out);
     }
     HIP_TRY(hipStreamSynchronize(stream));
@@ -3156,7 +2659,7 @@ struct Engine : EngineBase {
     ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
     ensure_mesh();
     if (which == 1)
-      ARG_CHECK(use_dft && !use_pfa && dft_zy_spread_fits<T>(K, top.na),
+      ARG_CHECK(mc.direct() && dft_zy_spread_fits<T>(K, top.na),
                 "which = 1: this handle's evaluations do not spread in the forward plane kernel (type, atom count or mesh path)");
     mesh_begin(in, box);
     const size_t nreal = (size_t)K[0] * K[1] * K[2];
@@ -3179,11 +2682,9 @@ struct Engine : EngineBase {
       HIP_TRY(hipMemsetAsync(Ed_cur() + E_RECIP, 0, sizeof(double), stream));
       slot_clean[E_RECIP] = false;
       const PlaneSpread<T> sp = plane_spread(ev.n_home, sites.as<Site<T>>(), lpol, recs);
-      convolve(m, spec.as<T>(), gtab_cur, E_RECIP, nullptr, nullptr, &sp);
+      mc.convolve(m, mc.gtab_cur, Ed_cur(), E_RECIP, nullptr, nullptr, &sp);
       info[0] = ADMP_SPREAD_FORM_PLANE_KERNEL;
-      info[5] = use_pfa ? ADMP_MESH_PATH_TWO_LEVEL                      // the handle's path, as admp_mesh_convolve reports it
-                : use_dft ? (dft_zy_fits<T>(K) ? ADMP_MESH_PATH_DIRECT_PLANES : ADMP_MESH_PATH_DIRECT_LINES)
-                          : (use_fx ? ADMP_MESH_PATH_FUSED_X : ADMP_MESH_PATH_ROCFFT);
+      info[5] = mc.path_word();      // the handle's path, as admp_mesh_convolve reports it
     }
     for (int d = 0; d < 3; ++d) info[1 + d] = c[1 + d];
     info[6] = recs ? 1 : 0;
@@ -3355,7 +2856,7 @@ struct Engine : EngineBase {
     HIP_TRY(hipMemsetAsync(cls, 0, 16 * sizeof(double), stream));
     { TIMED("pscale_grad"); launch_pscale_sums<T>(stream, top.na, wnbr(), sites.as<Site<T>>(), ev.bx, ev.tab, cls,
                                                   snranks > 1 ? pair_rows() : nullptr, ev.n_home); }
-    if (snranks > 1) { TIMED("comm_energies"); c_all_reduce(cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
+    if (snranks > 1) { TIMED("comm_energies"); comm.all_reduce(stream, cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     ev.active = false;
     double h16[16];
     HIP_TRY(hipMemcpyAsync(h16, cls, sizeof(h16), hipMemcpyDeviceToHost, stream));
@@ -3392,13 +2893,13 @@ struct Engine : EngineBase {
     }
     ScalarRows sr{nullptr, na, nullptr};
     if (snranks > 1) {      // the class sums of the rank's home rows, added over the ranks
-      ARG_CHECK(have_comm, "slab-decomposed handle without a communicator (admp_set_comm)");
-      if (have_ewald) { update_slab(); sr = scalar_rows(pos, make_geom(inv), K[0], X0, X1, true); }
+      ARG_CHECK(comm.have, "slab-decomposed handle without a communicator (admp_set_comm)");
+      if (have_ewald) { update_slab(); sr = scalar_rows(pos, make_geom(inv), K[0], mc.X0, mc.X1, true); }
       else sr = virtual_slab_rows(pos, inv);      // a pair potential has no mesh, as in tt()
     }
     { TIMED("mscale_grad"); launch_mscale_sums<T>(stream, kind, na, nbr, sites.as<Site<T>>(), pos, par, bx, pmax, cls, cutoff,
                                                   sr.rows, sr.n); }
-    if (snranks > 1) { TIMED("comm_energies"); c_all_reduce(cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
+    if (snranks > 1) { TIMED("comm_energies"); comm.all_reduce(stream, cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     double h16[16];
     HIP_TRY(hipMemcpyAsync(h16, cls, sizeof(h16), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -3675,21 +3176,21 @@ int admp_slab_info(admp_handle* h, int64_t* out11) {
 }
 int admp_set_comm(admp_handle* h, const admp_comm* comm) {
   return guarded(h, [&](EngineBase& e) {
-    if (!comm) { e.have_comm = false; e.comm = admp_comm{}; return; }
+    if (!comm) { e.comm.have = false; e.comm.cb = admp_comm{}; return; }
     ARG_CHECK(comm->all_reduce && comm->all_to_all_v && comm->shift, "communicator with a missing callback");
-    e.comm = *comm;
-    e.have_comm = true;
+    e.comm.cb = *comm;
+    e.comm.have = true;
   });
 }
 int admp_set_comm_rccl(admp_handle* h, admp_rccl* c) {
   return guarded(h, [&](EngineBase& e) {
-    if (!c) { e.rccl = nullptr; if (!e.comm.all_reduce) e.have_comm = false; return; }
+    if (!c) { e.comm.rccl = nullptr; if (!e.comm.cb.all_reduce) e.comm.have = false; return; }
     ARG_CHECK(rccl_device(c) == e.device, "the communicator was created on another device");
     ARG_CHECK(rccl_nranks(c) <= kSlabMaxRanks, "at most 28 slab ranks");
-    e.rccl = c;
+    e.comm.rccl = c;
     e.srank = rccl_rank(c); e.snranks = rccl_nranks(c);
     if (e.snranks > 1) e.aspc_off();
-    e.have_comm = true;
+    e.comm.have = true;
   });
 }
 int admp_set_dipole_source(admp_handle* h, const void* U_init) {
@@ -3736,19 +3237,19 @@ int admp_scf_stats(admp_handle* h, int64_t* out8, int reset) {
 int admp_xpass_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out2, "null");
-    for (int k = 0; k < 2; ++k) { out2[k] = e.xpass_stats[k]; if (reset) e.xpass_stats[k] = 0; }
+    for (int k = 0; k < 2; ++k) { out2[k] = e.mesh_stats.xpass[k]; if (reset) e.mesh_stats.xpass[k] = 0; }
   });
 }
 int admp_plane_mfma_stats(admp_handle* h, int64_t* out2, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out2, "null");
-    for (int k = 0; k < 2; ++k) { out2[k] = e.plane_mfma_stats[k]; if (reset) e.plane_mfma_stats[k] = 0; }
+    for (int k = 0; k < 2; ++k) { out2[k] = e.mesh_stats.plane_mfma[k]; if (reset) e.mesh_stats.plane_mfma[k] = 0; }
   });
 }
 int admp_plane_mfma_stats4(admp_handle* h, int64_t* out4, int reset) {
   return guarded(h, [&](EngineBase& e) {
     ARG_CHECK(out4, "null");
-    for (int k = 0; k < 4; ++k) { out4[k] = e.plane_mfma_stats4[k]; if (reset) e.plane_mfma_stats4[k] = 0; }
+    for (int k = 0; k < 4; ++k) { out4[k] = e.mesh_stats.plane_mfma4[k]; if (reset) e.mesh_stats.plane_mfma4[k] = 0; }
   });
 }
 int admp_mesh_convolve(admp_handle* h, const double* box, int which, void* mesh_inout, int on_device, double* E_out,

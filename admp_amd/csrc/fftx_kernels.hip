@@ -1,7 +1,7 @@
 // Fused x pass of the mesh convolution for power-of-two meshes: x lines forward, times G (+ the reciprocal energy), x lines
 // inverse -- ONE sweep over the half spectrum where rocFFT's 3-D plans + k_kspace make three (the x pass of the r2c plan,
 // the G multiply, the x pass of the c2r plan; 58 + 43 + 58 us at 256^3 f32).  rocFFT keeps the y-z planes (batched 2-D
-// r2c / c2r plans, engine.hip); replaces fftn / ifftn + the k-space product of admp/recip.py:395-426 exactly like they do
+// r2c / c2r plans, mesh_conv.hip); replaces fftn / ifftn + the k-space product of admp/recip.py:395-426 exactly like they do
 // (unnormalised both ways).
 //
 // A workgroup holds NC neighbouring columns (y, kz) of all N x positions in LDS.  Forward: radix-2 decimation in frequency,
@@ -352,7 +352,7 @@ void launch_fftx_mix(hipStream_t st, const int K[3], const T* tw, T* spec, const
 
 bool fftx_usable(int N) { return N >= 32 && N <= 1024 && (N & (N - 1)) == 0; }
 
-// spec = [K0][K1][khp] complex (khp >= K2/2+1: rows padded to whole 128-byte lines, engine.hip) after the batched 2-D r2c of
+// spec = [K0][K1][khp] complex (khp >= K2/2+1: rows padded to whole 128-byte lines, mesh_conv.hip) after the batched 2-D r2c of
 // the y-z planes; gtab = [K0][K1][K2/2+1]; tw = (cos, sin)(2 pi k / K0), k < K0 / 2
 template <class T>
 void launch_fftx_conv(hipStream_t st, const int K[3], const T* tw, T* spec, const T* gtab, double* energies, int slot, int khp,

@@ -1,4 +1,4 @@
-// Host helpers shared by the translation units behind the C ABI (engine.hip, md_driver.hip): the error type and its macros
+// Host helpers shared by the translation units behind the C ABI (engine.hip, mesh_conv.hip, md_driver.hip): the error type and its macros
 // (err.h), the per-label profiler, and the box handed to the kernels.
 #pragma once
 #include <hip/hip_runtime.h>

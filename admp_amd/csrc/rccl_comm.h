@@ -1,4 +1,4 @@
-// Internal interface between engine.hip and the native RCCL communicator (rccl_comm.hip).
+// Internal interface between the collectives of comm.h and the native RCCL communicator (rccl_comm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // Reciprocal-space kernels (reference admp/recip.py:21-431): B-spline spread of the multipoles onto
 // the K1 x K2 x K3 mesh, the k-space multiply with the cached table G_k = 2 D C_k / theta_k^2, and the
 // gather that produces dE/dQ and dE/dr from phi = c2r(G S) (the adjoint the reference leaves to jax.grad).
-// The 3-D transforms themselves are rocFFT r2c / c2r plans driven from engine.hip.
+// The 3-D transforms themselves are rocFFT r2c / c2r plans driven from mesh_conv.hip.
 #include <cstdlib>
 #include <cstring>
 #include <hipcub/hipcub.hpp>

@@ -17,7 +17,7 @@
 
 namespace admp {
 
-// slab owner of global mesh plane gx: the s with floor(s K / N) <= gx < floor((s + 1) K / N)  (engine.hip update_slab)
+// slab owner of global mesh plane gx: the s with floor(s K / N) <= gx < floor((s + 1) K / N)  (mesh_conv.hip MeshConv::update_slab)
 __device__ __forceinline__ int slab_owner(int gx, int K0, int N) {
   int s = (int)(((long)gx * N) / K0);
   while ((int)(((long)s * K0) / N) > gx) --s;

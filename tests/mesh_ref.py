@@ -242,7 +242,7 @@ def site_kinds(Qt):
 
 
 def direct_dft_by_default(K):
-    """Engine::setup_dft without ADMP_DFT: every axis at most 160 points and one of them with a prime factor above 13"""
+    """mesh_path (csrc/mesh_path.h) without ADMP_DFT: every axis at most 160 points and one of them with a prime factor above 13"""
     def lpf(n):
         f, p = 1, 2
         while n > 1:

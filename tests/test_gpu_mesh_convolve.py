@@ -1,5 +1,5 @@
 """The k-space leg  mesh <- IFFT(G * FFT(mesh))  and its energy word, bin by bin, on every transform path of
-Engine::convolve (admp_mesh_convolve) against numpy.fft in float64 with G built from the oracle alone.
+MeshConv::convolve (admp_mesh_convolve) against numpy.fft in float64 with G built from the oracle alone.
 
 Why: the end-to-end tests run at the production Ewald parameters, where G spans 55 decades and 80-99 % of the bins lie below
 their tolerances.  Here the same meshes also run at a FLAT kappa, chosen per mesh from the oracle's table so that

@@ -238,7 +238,7 @@ print('BRICK-OK')
 
 
 def test_direct_dft_convolution_vs_rocfft(tmp_path):
-    """Meshes with a Bluestein dimension go through dft_kernels.hip / pfa_kernels.hip instead of rocFFT (engine.hip setup_dft).
+    """Meshes with a Bluestein dimension go through dft_kernels.hip / pfa_kernels.hip instead of rocFFT (csrc/mesh_path.h mesh_path).
     The k-space legs must agree to round-off: polarizable PME and dispersion PME, even / odd / prime dimensions, both
     precisions; ADMP_DFT is read per handle, the child processes only keep the runs independent."""
     import subprocess

@@ -1,4 +1,4 @@
-"""The k-space leg of the SLAB ranks, bin by bin: Engine::slab_convolve with either x pass (admp_slab_mesh_convolve) against
+"""The k-space leg of the SLAB ranks, bin by bin: MeshConv::slab_convolve with either x pass (admp_slab_mesh_convolve) against
 numpy.fft in float64 -- the reference, the inputs and every bound of tests/test_gpu_mesh_convolve.py, unchanged (the passes run
 in the same order z, y, x, x, y, z; what is new is where the words live while they run).
 

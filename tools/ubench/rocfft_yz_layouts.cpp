@@ -1,4 +1,4 @@
-// Which output layout makes rocFFT's batched 2-D r2c / c2r of the y-z planes fastest?  (engine.hip plan2_f / plan2_b: 256^3 f32,
+// Which output layout makes rocFFT's batched 2-D r2c / c2r of the y-z planes fastest?  (mesh_conv.hip plan2_f / plan2_b: 256^3 f32,
 // one plane per x; the fused x pass that follows only needs a fixed stride between x planes.)
 //   A: default -- spectrum [x][y][kz], kz fastest
 //   C: transposed -- spectrum [x][kz][y], y fastest (out strides {K1, 1})
