@@ -1,6 +1,8 @@
 // libadmp_hip: handle, device buffers, and the orchestration of one get_energy / get_forces evaluation behind the C ABI of
 // include/admp_hip.h.  The k-space leg between spread and gather (rocFFT plans, tables, every transform path) is MeshConv,
-// mesh_conv.hip; the MD entries are md_driver.hip.
+// mesh_conv.hip; the neighbour table between two evaluations (builds, site classes, inner lists, loans) and the cell-list search
+// are PairList, pair_list.hip; what a topology implies for the closing kernels is topology_plan.h; the MD entries are
+// md_driver.hip.
 //
 // Flow of admp_pme_energy_grad (reference call stack: admp/pme.py:58-86 get_energy ->
 // :111-143 optimize_Uind -> :176-254 energy_pme, gradient by jax.value_and_grad :108):
@@ -20,8 +22,6 @@
 #include <cstring>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <functional>
 #include <vector>
@@ -35,19 +35,40 @@
 #include "handle.h"
 #include "launch.h"
 #include "mesh_conv.h"
+#include "pair_list.h"
 #include "rccl_comm.h"
 #include "scf_policy.h"
 #include "scf_aspc.h"
+#include "topology_plan.h"
 
 using namespace admp;
 
 namespace {
 
+static_assert(kTopoZBisect == ZBisect && kTopoThreeFold == ThreeFold && kTopoZonly == Zonly && kTopoNoAxis == NoAxisType,
+              "topology_plan.h restates the axis rules of frame_math.h");
+
+// the device arrays behind the Topology view the kernels take
+struct TopologyStore {
+  DevBuf axis_type, axis_idx, excl_ptr, excl_col, excl_nb, inv_ptr, inv_idx, grp_ptr, rows_blk, grp_of, gath_blk;
+  // n words of src in b (at least one word is allocated, so that an empty array has an address too)
+  static int* put(DevBuf& b, const int32_t* src, size_t n) {
+    b.need(sizeof(int) * std::max<size_t>(n, 1));
+    if (n > 0) HIP_TRY(hipMemcpy(b.p, src, sizeof(int) * n, hipMemcpyHostToDevice));
+    return b.as<int>();
+  }
+  void release() {
+    for (DevBuf* b : {&axis_type, &axis_idx, &excl_ptr, &excl_col, &excl_nb, &inv_ptr, &inv_idx, &grp_ptr, &rows_blk, &grp_of, &gath_blk})
+      b->release();
+  }
+};
+
 struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, srank, snranks, md (handle.h)
   virtual ~EngineBase() {}
-  Topology top;
-  NbrTable nbr;
-  bool have_top = false, have_ewald = false, have_pairs = false;
+  Topology top;                 // a view of top_d
+  TopologyStore top_d;
+  PairList pl{this};            // the neighbour table and all that happens to it between evaluations (pair_list.h)
+  bool have_top = false, have_ewald = false;
   double kappa = 0;
   int K[3] = {0, 0, 0};
   int lmax = 2, lpol = 0;
@@ -77,61 +98,14 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   int side_stream_on = 1;       // ADMP_OPT_SIDE_STREAM: 0 keeps every kernel on the handle's stream (clean per-kernel event times)
   // a call that failed half way: whatever it left on a helper stream is waited for before the error is reported
   virtual void after_error() {}
-  long nbr_gen = 0;             // bumped whenever the neighbour table is rebuilt
-  // admp_prune_pairs: `nbr` is an INNER table (the entries of the table as built, nbr_full, below a shorter cutoff; own rowptr /
-  // col, everything else shared with nbr_full) until the next prune, list build, class compile or admp_unprune.  Whatever frees
-  // or rebuilds `nbr` calls unprune() first.
-  NbrTable nbr_full;
-  bool pruned = false;
-  void unprune() {
-    if (!pruned) return;
-    nbr = nbr_full;
-    nbr_full = NbrTable();
-    pruned = false;
-    ++nbr_gen;
-  }
-  // Neighbour table borrowed from another handle (admp_share_neighbors): the calculators of one system walk ONE compiled
-  // table instead of compiling the same pair list once each.  `nbr` is then a copy of the lender's struct, refreshed at
-  // the start of every call (adopt_shared), never freed or modified here.
-  EngineBase* nbr_src = nullptr;
-  long nbr_src_gen = -1;
-  static std::set<EngineBase*>& live() { static std::set<EngineBase*> s; return s; }
-  static std::mutex& live_mu() { static std::mutex m; return m; }
-  static bool is_live(EngineBase* e) { std::lock_guard<std::mutex> g(live_mu()); return live().count(e) != 0; }
-  void detach_shared() {
-    if (!nbr_src) return;
-    nbr = NbrTable();            // forget the lender's pointers
-    nbr_src = nullptr; nbr_src_gen = -1;
-    have_pairs = false;
-    ++nbr_gen;
-  }
-  void adopt_shared() {
-    if (!nbr_src) return;
-    if (!is_live(nbr_src)) { nbr = NbrTable(); nbr_src = nullptr; have_pairs = false; throw Err{ADMP_E_ARG, "the handle the neighbour table was borrowed from has been destroyed"}; }
-    if (!nbr_src->have_pairs || nbr_src->top.na != top.na) { nbr = NbrTable(); have_pairs = false; return; }
-    if (nbr_src_gen != nbr_src->nbr_gen || nbr.col != nbr_src->nbr.col || nbr.order != nbr_src->nbr.order ||
-        nbr.order_plain != nbr_src->nbr.order_plain) {
-      if (nbr_src->stream != stream) HIP_TRY(hipStreamSynchronize(nbr_src->stream));   // built / ordered on the lender's stream
-      nbr = nbr_src->nbr;
-      nbr_src_gen = nbr_src->nbr_gen;
-      ++nbr_gen;
-    }
-    have_pairs = true;
-  }
+  // admp_share_neighbors: the calculators of one system walk ONE compiled table instead of compiling the same pair list once each
   void share_neighbors(EngineBase* src) {
     ARG_CHECK(have_top, "admp_set_topology must precede admp_share_neighbors");
-    if (!src) { detach_shared(); return; }
-    ARG_CHECK(src != this && !src->nbr_src, "the lender must own its neighbour table");
+    if (!src) { pl.end_loan(); return; }
+    ARG_CHECK(src != this && src->pl.owned(), "the lender must own its neighbour table");
     ARG_CHECK(src->have_top && src->top.na == top.na && src->device == device, "handles of different systems / devices");
-    unprune();
-    if (!nbr_src) nbr.free_all();   // drop the table this handle owns
-    nbr = NbrTable();
-    nbr_src = src; nbr_src_gen = -1;
-    have_pairs = false;
-    adopt_shared();
+    pl.borrow(&src->pl, top.na);
   }
-  DevBuf scan_scratch;
-  size_t scan_bytes = 0;
 
   virtual void set_ewald(double kappa_, int K1, int K2, int K3, int lmax_, int lpol_) = 0;
   virtual void pme(const void* pos, const double* box, const void* Ql, const void* pol, const void* thole, int ns,
@@ -225,61 +199,14 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
                           int32_t* imp, int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts) = 0;
 
   void free_topology() {
-    if (top.axis_type) (void)hipFree(top.axis_type);
-    if (top.axis_idx) (void)hipFree(top.axis_idx);
-    if (top.excl_ptr) (void)hipFree(top.excl_ptr);
-    if (top.excl_col) (void)hipFree(top.excl_col);
-    if (top.excl_nb) (void)hipFree(top.excl_nb);
-    if (top.inv_ptr) (void)hipFree(top.inv_ptr);
-    if (top.inv_idx) (void)hipFree(top.inv_idx);
-    if (top.grp_ptr) (void)hipFree(top.grp_ptr);
-    if (top.rows_blk) (void)hipFree(top.rows_blk);
-    if (top.grp_of) (void)hipFree(top.grp_of);
-    if (top.gath_blk) (void)hipFree(top.gath_blk);
+    top_d.release();
     top = Topology();
-    unprune();
-    if (!nbr_src) nbr.free_all();
-    nbr_src = nullptr; nbr_src_gen = -1;
-    nbr = NbrTable();
-    cls_pending = false; cls_quiet = 1 << 20;
+    pl.drop();
     slab_sites_na = -1;
-    have_top = have_pairs = false;
-    ++nbr_gen;
+    have_top = false;
   }
-
-  // row order of the freshly built table (see launch_row_order); ADMP_PAIR_SORT=0 keeps the natural order
-  void order_rows() {
-    static const bool off = !env_flag("ADMP_PAIR_SORT", true);
-    if (off) {
-      if (nbr.order) { (void)hipFree(nbr.order); nbr.order = nullptr; }
-      if (nbr.order_plain) { (void)hipFree(nbr.order_plain); nbr.order_plain = nullptr; }
-      return;
-    }
-    if (!nbr.order) HIP_TRY(hipMalloc(&nbr.order, sizeof(int) * (size_t)top.na));
-    launch_row_order(stream, top.na, nbr.rowptr, nbr.order, nbr.cls);
-    if (nbr.cls) {
-      if (!nbr.order_plain) HIP_TRY(hipMalloc(&nbr.order_plain, sizeof(int) * (size_t)top.na));
-      launch_row_order(stream, top.na, nbr.rowptr, nbr.order_plain, nullptr);
-    }
-  }
-  // Site classes of the neighbour table (NbrTable::cls).  k_prepare_sites compares them with the sites of every evaluation
-  // and leaves CLS_STALE / CLS_BETTER next to E_NACT; read_energies hands the word to cls_seen, and the next evaluation
-  // recompiles the table (part the rows, regroup the row order) before it starts.  A table that is merely not as good as
-  // it could be (CLS_BETTER) is left alone for a while after a CLS_STALE, so that a caller alternating between parameter
-  // sets does not pay a recompilation per call.
-  bool cls_pending = false;
-  int cls_quiet = 1 << 20;      // evaluations since the last CLS_STALE
   int slab_sites_na = -1;       // slab rank: every row of the site table (at slab_sites_ptr) has been prepared at least once
   const void* slab_sites_ptr = nullptr;   //     for a system of this many atoms (Engine::stage_begin)
-  void cls_seen(int flags) {
-    if (flags & CLS_STALE) { cls_pending = true; cls_quiet = 0; }
-    else if ((flags & CLS_BETTER) && cls_quiet > 8) cls_pending = true;
-  }
-  void apply_classes() {        // after a table build: part the fresh rows by the classes already known
-    if (!nbr.cls) return;
-    int rc = launch_class_partition(stream, top.na, nbr);
-    if (rc != 0) throw Err{ADMP_E_HIP, std::string("class partition: ") + hipGetErrorString((hipError_t)rc)};
-  }
 
   void set_topology(int na, const int32_t* atype, const int32_t* aidx, const int32_t* eptr, const int32_t* ecol,
                     const int32_t* enb) {
@@ -294,124 +221,37 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
       ARG_CHECK(at[i] >= 0 && at[i] <= 5, "axis_type outside 0..5");
       for (int k = 0; k < 3; ++k) ARG_CHECK(ai[3 * i + k] >= -1 && ai[3 * i + k] < na, "axis index out of range");
     }
-    HIP_TRY(hipMalloc(&top.axis_type, sizeof(int) * na));
-    HIP_TRY(hipMalloc(&top.axis_idx, sizeof(int) * 3 * na));
-    HIP_TRY(hipMemcpy(top.axis_type, at, sizeof(int) * na, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(top.axis_idx, ai, sizeof(int) * 3 * na, hipMemcpyHostToDevice));
+    top.axis_type = TopologyStore::put(top_d.axis_type, at, (size_t)na);
+    top.axis_idx = TopologyStore::put(top_d.axis_idx, ai, 3 * (size_t)na);
     if (eptr) {
       int nnz = eptr[na];
       ARG_CHECK(nnz >= 0, "bad exclusion rowptr");
       for (int k = 0; k < nnz; ++k) ARG_CHECK(ecol[k] >= 0 && ecol[k] < na && enb[k] >= 0 && enb[k] <= kNbMask,
                                                 "bad exclusion entry (atom index out of range, or nbonds outside 0..7)");
-      HIP_TRY(hipMalloc(&top.excl_ptr, sizeof(int) * (na + 1)));
-      HIP_TRY(hipMalloc(&top.excl_col, sizeof(int) * (nnz > 0 ? nnz : 1)));
-      HIP_TRY(hipMalloc(&top.excl_nb, sizeof(int) * (nnz > 0 ? nnz : 1)));
-      HIP_TRY(hipMemcpy(top.excl_ptr, eptr, sizeof(int) * (na + 1), hipMemcpyHostToDevice));
-      if (nnz > 0) {
-        HIP_TRY(hipMemcpy(top.excl_col, ecol, sizeof(int) * nnz, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(top.excl_nb, enb, sizeof(int) * nnz, hipMemcpyHostToDevice));
-      }
+      top.excl_ptr = TopologyStore::put(top_d.excl_ptr, eptr, (size_t)na + 1);
+      top.excl_col = TopologyStore::put(top_d.excl_col, ecol, (size_t)nnz);
+      top.excl_nb = TopologyStore::put(top_d.excl_nb, enb, (size_t)nnz);
     }
-    {   // inverse frame map for the atomics-free closing kernel
-      std::vector<std::vector<int>> inv(na);
-      for (int i = 0; i < na; ++i) {
-        if (at[i] == NoAxisType || ai[3 * i] < 0) { inv[i].push_back(i); continue; }
-        int mem[4] = {i, ai[3 * i], at[i] != Zonly ? ai[3 * i + 1] : -1,
-                      (at[i] == ZBisect || at[i] == ThreeFold) ? ai[3 * i + 2] : -1};
-        for (int m = 0; m < 4; ++m) {
-          if (mem[m] < 0) continue;
-          bool dup = false;
-          for (int q = 0; q < m; ++q) dup = dup || mem[q] == mem[m];
-          if (!dup) inv[mem[m]].push_back(i);
-        }
-      }
-      std::vector<int> ptr(na + 1, 0), idx;
-      for (int a = 0; a < na; ++a) { ptr[a + 1] = ptr[a] + (int)inv[a].size(); idx.insert(idx.end(), inv[a].begin(), inv[a].end()); }
-      HIP_TRY(hipMalloc(&top.inv_ptr, sizeof(int) * (na + 1)));
-      HIP_TRY(hipMalloc(&top.inv_idx, sizeof(int) * (idx.empty() ? 1 : idx.size())));
-      HIP_TRY(hipMemcpy(top.inv_ptr, ptr.data(), sizeof(int) * (na + 1), hipMemcpyHostToDevice));
-      if (!idx.empty()) HIP_TRY(hipMemcpy(top.inv_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
-    }
-    {   // frame groups (see Topology): union-find over "site i uses atom m in its frame"
-      std::vector<int> parent(na);
-      for (int i = 0; i < na; ++i) parent[i] = i;
-      auto find = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
-      for (int i = 0; i < na; ++i) {
-        if (at[i] == NoAxisType || ai[3 * i] < 0) continue;
-        const int mem[3] = {ai[3 * i], at[i] != Zonly ? ai[3 * i + 1] : -1,
-                            (at[i] == ZBisect || at[i] == ThreeFold) ? ai[3 * i + 2] : -1};
-        for (int m = 0; m < 3; ++m)
-          if (mem[m] >= 0) { const int a = find(i), b = find(mem[m]); if (a != b) parent[std::max(a, b)] = std::min(a, b); }
-      }
-      // the root of a component is its lowest atom: components are runs of consecutive atoms iff root(i) is
-      // non-decreasing in i and every run is short enough
-      std::vector<int> gp;
-      bool ok = true;
-      int prev_root = -1;
-      for (int i = 0; i < na && ok; ++i) {
-        const int r = find(i);
-        if (r != prev_root) {
-          if (r != i) ok = false;                      // joins an earlier, already closed run
-          gp.push_back(i);
-          prev_root = r;
-        } else if (i - r >= kMaxGroup) ok = false;
-      }
-      gp.push_back(na);
-      static const bool off = !env_flag("ADMP_FINISH_GROUPS", true);
-      if (ok && !off) {
-        HIP_TRY(hipMalloc(&top.grp_ptr, sizeof(int) * gp.size()));
-        HIP_TRY(hipMemcpy(top.grp_ptr, gp.data(), sizeof(int) * gp.size(), hipMemcpyHostToDevice));
-        top.ngroups = (int)gp.size() - 1;
-        // row form: workgroups of whole groups (greedy runs of at most kFinishBlock atoms), group record per atom
-        std::vector<int> blk(1, 0), gof((size_t)na);
-        for (int gi = 0; gi < top.ngroups; ++gi) {
-          const int a0 = gp[gi], n = gp[gi + 1] - a0;
-          if (gp[gi + 1] - blk.back() > kFinishBlock) blk.push_back(a0);
-          for (int m = 0; m < n; ++m) gof[(size_t)a0 + m] = (a0 << 2) | (n - 1);
-        }
-        blk.push_back(na);
-        {   // runs of at most kGatherRun atoms for the gather with the closing epilogue
-          std::vector<int> gb(1, 0);
-          for (int gi = 0; gi < top.ngroups; ++gi)
-            if (gp[gi + 1] - gb.back() > kGatherRun) gb.push_back(gp[gi]);
-          gb.push_back(na);
-          HIP_TRY(hipMalloc(&top.gath_blk, sizeof(int) * gb.size()));
-          HIP_TRY(hipMemcpy(top.gath_blk, gb.data(), sizeof(int) * gb.size(), hipMemcpyHostToDevice));
-          top.ngathblk = (int)gb.size() - 1;
-        }
-        HIP_TRY(hipMalloc(&top.rows_blk, sizeof(int) * blk.size()));
-        HIP_TRY(hipMemcpy(top.rows_blk, blk.data(), sizeof(int) * blk.size(), hipMemcpyHostToDevice));
-        top.nrowblk = (int)blk.size() - 1;
-        HIP_TRY(hipMalloc(&top.grp_of, sizeof(int) * (size_t)na));
-        HIP_TRY(hipMemcpy(top.grp_of, gof.data(), sizeof(int) * (size_t)na, hipMemcpyHostToDevice));
-      }
+    // the inverse frame map for the atomics-free closing kernel and, where the frames allow them, the frame groups (topology_plan.h)
+    static const bool groups_on = env_flag("ADMP_FINISH_GROUPS", true);
+    const TopologyPlan p = topology_plan(na, at, ai, kMaxGroup, kFinishBlock, kGatherRun, groups_on);
+    top.inv_ptr = TopologyStore::put(top_d.inv_ptr, p.inv_ptr.data(), p.inv_ptr.size());
+    top.inv_idx = TopologyStore::put(top_d.inv_idx, p.inv_idx.data(), p.inv_idx.size());
+    if (!p.grp_ptr.empty()) {
+      top.grp_ptr = TopologyStore::put(top_d.grp_ptr, p.grp_ptr.data(), p.grp_ptr.size());
+      top.ngroups = (int)p.grp_ptr.size() - 1;
+      top.gath_blk = TopologyStore::put(top_d.gath_blk, p.gath_blk.data(), p.gath_blk.size());
+      top.ngathblk = (int)p.gath_blk.size() - 1;
+      top.rows_blk = TopologyStore::put(top_d.rows_blk, p.rows_blk.data(), p.rows_blk.size());
+      top.nrowblk = (int)p.rows_blk.size() - 1;
+      top.grp_of = TopologyStore::put(top_d.grp_of, p.grp_of.data(), p.grp_of.size());
     }
     have_top = true;
   }
 
   void set_pairs(int64_t n_rows, const int32_t* pairs, int on_device) {
-    unprune();
     ARG_CHECK(have_top, "admp_set_topology must precede admp_set_pairs");
-    ARG_CHECK(n_rows >= 0, "negative pair count");
-    detach_shared();             // a pair list of its own ends a borrowed table
-    DevBuf staged;
-    const int* dev = pairs;
-    if (!on_device && n_rows > 0) {
-      staged.need(sizeof(int) * 2 * (size_t)n_rows);
-      HIP_TRY(hipMemcpyAsync(staged.p, pairs, sizeof(int) * 2 * (size_t)n_rows, hipMemcpyHostToDevice, stream));
-      dev = staged.as<int>();
-    }
-    {
-      TIMED("nbr_build");
-      if (nbr.built) { (void)hipFree(nbr.built); nbr.built = nullptr; }      // (a table from an explicit list holds every row)
-      int rc = build_neighbour_table(stream, top, n_rows, dev, nbr, &scan_scratch.p, &scan_bytes);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_neighbour_table: ") + hipGetErrorString((hipError_t)rc)};
-      apply_classes();
-      order_rows();
-    }
-    HIP_TRY(hipStreamSynchronize(stream));      // `staged` is freed on the way out, and on the way out of a throw above
-    have_pairs = true;
-    ++nbr_gen;
+    pl.set_pairs(top, n_rows, pairs, on_device);
   }
 };
 
@@ -450,19 +290,20 @@ struct Engine : EngineBase {
   MeshConv<T> mc{this, &comm, &mesh_stats};
   BinScratch bins, bins_ind;   // brick lists of the site rows / of the compact rows of the SCF increments
   DevBuf home_list;
-  DevBuf act_tmp;
+  DevBuf act_tmp, sort_scratch;  // sort_scratch: hipcub's, grown by sort_ints (sort_bytes)
+  size_t sort_bytes = 0;
   DevBuf onehot_d, tcount_d;     // typed dispersion of small systems: (Na, n_types) one-hot weights; scratch of the type counts
   void* onehot_for = nullptr;    // ... built in this allocation
   DevBuf act_d, isites, mesh2;   // incremental SCF: polarizable-site list, their compact delta rows, the increment's mesh
   IndTable ind;                  // ... and the polarizable-polarizable part of the neighbour table
   // admp_set_cutoff (a Verlet list with a skin): each evaluation with a cutoff first writes the inner table of the table it walks
-  // (nbr: owned, borrowed or pruned) at its own site rows, and all its multipolar pair passes walk that copy (build_cut_table).
-  // Allocated on the first such evaluation; cutoff 0 walks nbr / ind as before.
+  // (pl.table(), whichever it is) at its own site rows, and all its multipolar pair passes walk that copy (build_cut_table).
+  // Allocated on the first such evaluation; cutoff 0 walks pl.table() / ind as before.
   DevBuf cut_end, cut_col, cut_iend, cut_icol;
   NbrTable cut_nbr;
   IndTable cut_ind;
   bool cut_on = false;           // this evaluation walks cut_nbr / cut_ind
-  const NbrTable& wnbr() const { return cut_on ? cut_nbr : nbr; }
+  const NbrTable& wnbr() const { return cut_on ? cut_nbr : pl.table(); }
   const IndTable& wind() const { return cut_on ? cut_ind : ind; }
   long act_gen = 0, act_top_na = -1;   // act_gen: bumped when the list is rebuilt; the list belongs to a topology of act_top_na atoms
   int act_n = -1;                // its length once the host has seen it (-1: not yet)
@@ -483,9 +324,8 @@ struct Engine : EngineBase {
   ~Engine() override {
     mc.destroy_plans();
     free_topology();
-    if (ind.end) (void)hipFree(ind.end);
+    if (ind.end) (void)hipFree(ind.end);      // (grown by build_ind_table with hipMalloc into the plain struct the kernels take)
     if (ind.col) (void)hipFree(ind.col);
-    cells.release();
     free_programs();
     if (Eh) (void)hipHostFree(Eh);
     prof.destroy();
@@ -513,7 +353,7 @@ struct Engine : EngineBase {
   static constexpr int real_dtype() { return sizeof(T) == 4 ? ADMP_T_F32 : ADMP_T_F64; }
   // Who owns what in this evaluation, derived by every rank from the replicated inputs (no communication): home atoms, home
   // rows in pair-kernel order, polarizable home atoms, imports per owner, exports per reader.  One host read (the counts).
-  void decompose() { decompose(K[0], mc.X0, mc.X1, nbr.order, lpol != 0); }
+  void decompose() { decompose(K[0], mc.X0, mc.X1, pl.table().order, lpol != 0); }
   // K0v / X0v / X1v: the planes the ownership rule works on (the PME mesh's; a handle without a mesh takes a virtual one);
   // order: the row order of the table to filter (nullptr: natural order); with_dipoles: the evaluation carries induced
   // dipoles from call to call (atoms that change hands take theirs along)
@@ -561,7 +401,7 @@ struct Engine : EngineBase {
     sl.lists.need(sizeof(int) * (size_t)cs.ncols * (size_t)na);
     {
       TIMED("slab_decompose");
-      int rc = launch_slab_decompose(stream, na, nbr, top, ev.bases, ev.pol, (int)sizeof(T), X1v - X0v, K0v, X0v, N, me,
+      int rc = launch_slab_decompose(stream, na, pl.table(), top, ev.bases, ev.pol, (int)sizeof(T), X1v - X0v, K0v, X0v, N, me,
                                      sl.owner.as<int>(), sl.bits.as<int>(), cs, sb, sl.counts.as<int>(), sl.totals.as<int>(),
                                      sl.lists.as<int>(), track ? sl.owner_prev.as<int>() : nullptr, track ? sl.mig.as<int>() : nullptr);
       if (rc != 0) throw Err{ADMP_E_HIP, std::string("slab decomposition: ") + hipGetErrorString((hipError_t)rc)};
@@ -835,11 +675,11 @@ struct Engine : EngineBase {
     const int4* bases = nullptr;                 // stencil base indices per atom (written by prepare_sites)
     bool active = false;
   } ev;
-  const int* pair_rows() const { return snranks > 1 ? sl.rows : nbr.order; }      // row order of the pair kernels
+  const int* pair_rows() const { return snranks > 1 ? sl.rows : pl.table().order; }      // row order of the pair kernels
 
   int stage_begin(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
                   const double* mS, const double* pS, void* U_) {
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(pos_ && box && Ql_, "null argument");
     if (lpol) ARG_CHECK(pol_ && thole_ && U_ && pS, "polarizable handle needs pol, tholes, pScales and U_inout");
     const int na = top.na;
@@ -885,11 +725,11 @@ struct Engine : EngineBase {
     // buffer, and evaluations that recompile the table's site classes, take the all-atom pass below, so that every row of
     // `sites` has held valid data at least once (the class compilation reads all of them).  ADMP_SLAB_SUBSET=0: always all.
     static const bool subset_on = env_flag("ADMP_SLAB_SUBSET", true);
-    if (snranks > 1 && subset_on && slab_sites_na == na && slab_sites_ptr == sites.p && !cls_pending && have_pairs) {
+    if (snranks > 1 && subset_on && slab_sites_na == na && slab_sites_ptr == sites.p && !pl.classes_pending() && pl.have()) {
       { TIMED("atom_bases"); launch_atom_bases<T>(stream, na, ev.pos, ev.g, bases_d.as<int4>()); }
       ev.bases = bases_d.as<int4>();
       cls_sites_na = na;
-      ++cls_quiet;
+      pl.evaluation_begins();
       const bool tracked = lpol && sl.prev_na == na;
       decompose();
       {
@@ -899,7 +739,7 @@ struct Engine : EngineBase {
         for (int k = 0; k < 2; ++k)
           launch_prepare_sites<T>(stream, top, ev.pos, ev.Ql, U_first, ev.pol, ev.thole, ev.bx, sites.as<Site<T>>(),
                                   k == 0 ? energies_d.as<double>() + (size_t)(ehalf ^ 1) * E_WORDS : nullptr, ev.g, nullptr,
-                                  nullptr, nullptr, nbr.cls, cls_flags_dev(), rq_p(), U_first != ev.U ? ev.U : nullptr, lists[k],
+                                  nullptr, nullptr, pl.table().cls, cls_flags_dev(), rq_p(), U_first != ev.U ? ev.U : nullptr, lists[k],
                                   counts[k]);
       }
       other_clean = true;
@@ -918,34 +758,23 @@ struct Engine : EngineBase {
       const bool want_act = lpol && snranks == 1 && !(keep_pol_sites && have_list);
       act_fresh = want_act;
       if (want_act) { act_d.need(sizeof(int) * (size_t)na); act_n = -1; act_top_na = na; ++act_gen; }
-      if (cls_pending && have_pairs && cls_sites_na == na && !nbr_src) {   // `sites` still holds the last evaluation's
-        unprune();                                                        // (classes are compiled into the table as built)
-        if (!nbr.cls) HIP_TRY(hipMalloc(&nbr.cls, sizeof(int) * (size_t)na));
-        launch_site_classes<T>(stream, na, sites.as<Site<T>>(), nbr.cls);
-        apply_classes();
-        order_rows();
-      }
-      cls_pending = false;
+      if (pl.classes_pending() && cls_sites_na == na)      // `sites` still holds the last evaluation's
+        pl.compile_classes<T>(na, sites.as<Site<T>>());
+      pl.evaluation_begins();
       cls_sites_na = na;
-      ++cls_quiet;
       launch_prepare_sites<T>(stream, top, ev.pos, ev.Ql, U_first, ev.pol, ev.thole, ev.bx, sites.as<Site<T>>(),
                               energies_d.as<double>() + (size_t)(ehalf ^ 1) * E_WORDS, ev.g, bases_d.as<int4>(),
-                              want_act ? act_d.as<int>() : nullptr, want_act ? nact_dev() : nullptr, nbr.cls,
+                              want_act ? act_d.as<int>() : nullptr, want_act ? nact_dev() : nullptr, pl.table().cls,
                               cls_flags_dev(), rq_p(), U_first != ev.U ? ev.U : nullptr);
       ev.bases = bases_d.as<int4>();
       // First evaluation on a table compiled without classes: look at the flags right away (one extra host read, once) so
       // that this call already walks the parted rows -- a caller who evaluates once gets the reduced forms too.
-      if (!nbr.cls && have_pairs && !nbr_src && !cls_first_done) {
-        cls_first_done = true;
+      if (pl.first_look()) {
         int flags = 0;
         HIP_TRY(hipMemcpyAsync(&flags, cls_flags_dev(), sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (flags & CLS_BETTER) {
-          unprune();
-          HIP_TRY(hipMalloc(&nbr.cls, sizeof(int) * (size_t)na));
-          launch_site_classes<T>(stream, na, sites.as<Site<T>>(), nbr.cls);
-          apply_classes();
-          order_rows();
+          pl.compile_classes<T>(na, sites.as<Site<T>>());
           HIP_TRY(hipMemsetAsync(cls_flags_dev(), 0, sizeof(int), stream));   // the table now agrees with these sites
         }
       }
@@ -969,6 +798,7 @@ struct Engine : EngineBase {
   void cut_pass() {
     cut_on = cutoff > 0.0;
     if (!cut_on) return;
+    const NbrTable& nbr = pl.table();
     const size_t na = (size_t)top.na, entries = (size_t)std::max<int64_t>(nbr.cap, 1);
     cut_end.need(sizeof(int) * na);
     cut_col.need(sizeof(int) * entries);
@@ -1182,7 +1012,6 @@ struct Engine : EngineBase {
   }
   int* cls_flags_dev() { return nact_dev() + 1; }   // the other half of that word: CLS_* of this evaluation (k_prepare_sites)
   int cls_sites_na = -1;                            // `sites` holds an evaluation of this many atoms
-  bool cls_first_done = false;                      // the flags of the first evaluation have been looked at
   // the polarizable rows of this evaluation: all polarizable atoms (one rank), or the rank's polarizable home atoms
   const int* act_list() const { return snranks > 1 ? sl.act : act_d.as<int>(); }
   // device-side count for the kernels of the first cycle when the list is fresh (nullptr: the host knows it)
@@ -1199,7 +1028,7 @@ struct Engine : EngineBase {
     // workgroups (and XCDs) of the pair kernels work on are neighbours in space again (measured HBM traffic of the field
     // pass over the list at 1M atoms: 1.42 GB unsorted -- more than the full pair kernel's 0.44 GB).
     act_tmp.need(sizeof(int) * (size_t)(n > 0 ? n : 1));
-    int rc = sort_ints(stream, act_d.as<int>(), act_tmp.as<int>(), n, &scan_scratch.p, &scan_bytes);
+    int rc = sort_ints(stream, act_d.as<int>(), act_tmp.as<int>(), n, &sort_scratch.p, &sort_bytes);
     if (rc != 0) throw Err{ADMP_E_HIP, std::string("sort_ints: ") + hipGetErrorString((hipError_t)rc)};
   }
   // the SCF field kernels over the polarizable rows: real-space dE/dU from all partners (k_pair_field), and its increment
@@ -1294,6 +1123,15 @@ struct Engine : EngineBase {
   // final; returns whether it did
   // no_field: nobody reads the field of the new dipoles (last corrector of a fixed-form call): phi alone is brought up to
   // date, the real-space increment and the field gather are not run
+  // the polarizable sub-table of the walked table, rebuilt when the neighbour table or the polarizable set changed (cut_ind is
+  // written by every evaluation instead)
+  void ensure_ind_table() {
+    if (cut_on || (ind_nbr_gen == pl.gen() && ind_act_gen == act_gen)) return;
+    TIMED("ind_table");
+    int rc = build_ind_table<T>(stream, top.na, pl.table(), sites.as<Site<T>>(), ind);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
+    ind_nbr_gen = pl.gen(); ind_act_gen = act_gen;
+  }
   bool scf_increment(int n_act, unsigned long long* check_word = nullptr,   // fld_pair / fld_recip / phi <- their values for the dipoles after scf_jacobi
                      const std::function<void()>& extra_side = nullptr, bool field_from_total_phi = false,
                      T* full_grad = nullptr, bool no_field = false) {
@@ -1312,13 +1150,7 @@ struct Engine : EngineBase {
         });
       if (extra_side) on_side(extra_side);
     };
-    if (!cut_on && (ind_nbr_gen != nbr_gen || ind_act_gen != act_gen)) {   // neighbour table or polarizable set changed
-                                                                          // (cut_ind is written by every evaluation)
-      TIMED("ind_table");
-      int rc = build_ind_table<T>(stream, top.na, nbr, sites.as<Site<T>>(), ind);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
-      ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
-    }
+    ensure_ind_table();
     fr = pair_field_ind_args(n_act);
     ride = !no_field && rider_ok() && field_rider<T>(fr);
     if (first) side_work();
@@ -1366,7 +1198,7 @@ struct Engine : EngineBase {
     {
       int w[2];
       std::memcpy(w, &Eh[E_NACT], sizeof(w));
-      cls_seen(w[1]);
+      pl.classes_seen(w[1]);
     }
     if (summed) {
       for (int k = 0; k < 4; ++k) E[k] = Eh[E_RED + k];
@@ -1702,7 +1534,7 @@ struct Engine : EngineBase {
     const PmeIo io = stage_pme_io(pos_, box, Ql_, pol_, thole_, U_, E, dpos_, dQl_, on_device);
     // admp_scf_aspc with a full history: the call starts from the predicted dipoles, whatever the caller passed
     const bool aspc_on = lpol && aspc.on() && !aspc_hold && snranks == 1;
-    const bool predicted = aspc_on && aspc.full() && max_cycle >= 1 && have_top && have_ewald && have_pairs;
+    const bool predicted = aspc_on && aspc.full() && max_cycle >= 1 && have_top && have_ewald && pl.have();
     if (predicted) aspc_predict();
     stage_begin(io.pos, box, io.Ql, io.pol, io.thole, ns, mS, pS, io.U);
     ScfRun run;
@@ -1897,8 +1729,8 @@ struct Engine : EngineBase {
     double* acc = vir_begin();
     cls_sites_na = slab_sites_na = -1;
     const ScalarRows sr = scalar_rows(pos, g, K[0], mc.X0, mc.X1, true);
-    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, sr.rows, sr.n, cutoff);
-    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff, sr.rows, sr.n);
+    launch_disp_pair<T>(stream, na, pl.table(), pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, sr.rows, sr.n, cutoff);
+    launch_scalar_pair_virial<T>(stream, 0, na, pl.table(), pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff, sr.rows, sr.n);
     const int nch = (pmax - 4) / 2;
     const size_t nreal = nreal_local();
     mesh.need(nch * nreal * sizeof(T));
@@ -1921,7 +1753,7 @@ struct Engine : EngineBase {
 
   void disp_box_grad(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
                      double* dbox) override {
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(pos_ && box && clist_ && E && dbox, "null argument");
     ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
     if (snranks > 1) {
@@ -1934,8 +1766,8 @@ struct Engine : EngineBase {
     const T* pos = sc.pos; const T* cl = sc.par;
     double* Ed = sc.Ed;
     double* acc = vir_begin();
-    launch_disp_pair<T>(stream, na, nbr, pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, nullptr, 0, cutoff);
-    launch_scalar_pair_virial<T>(stream, 0, na, nbr, pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff);
+    launch_disp_pair<T>(stream, na, pl.table(), pack_srows(pos, cl, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, Ed, nullptr, 0, cutoff);
+    launch_scalar_pair_virial<T>(stream, 0, na, pl.table(), pos, cl, sc.bx, sc.tab, (T)kappa, pmax, acc + V_XW, cutoff);
     cls_sites_na = slab_sites_na = -1;   // other rows than an electrostatics evaluation's
     sites.need(sizeof(Site<T>) * (size_t)na);
     ensure_bins(na);
@@ -1959,94 +1791,45 @@ struct Engine : EngineBase {
 
   void tt_box_grad(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, double* E,
                    double* dbox) override {
-    ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
+    ARG_CHECK(have_top && pl.have(), "topology and pairs must be set first");
     ARG_CHECK(pos_ && box && abqc_ && E && dbox, "null argument");
     const int na = top.na;
     const ScalarCall sc = scalar_begin(box, ns, mS, pos_, abqc_, 4, nullptr, 1, E_WORDS);
     double* acc = vir_begin();
     ScalarRows sr{nullptr, na, nullptr};
     if (snranks > 1) sr = virtual_slab_rows(sc.pos, sc.inv);     // as in tt(); the sums are added over the ranks
-    launch_tt_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff);
-    launch_scalar_pair_virial<T>(stream, 1, na, nbr, sc.pos, sc.par, sc.bx, sc.tab, T(0), 0, acc + V_XW, cutoff, sr.rows, sr.n);
+    launch_tt_pair<T>(stream, na, pl.table(), pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff);
+    launch_scalar_pair_virial<T>(stream, 1, na, pl.table(), sc.pos, sc.par, sc.bx, sc.tab, T(0), 0, acc + V_XW, cutoff, sr.rows, sr.n);
     read_scalar_energies(sc.Ed, E, 1);
     if (snranks > 1) { TIMED("comm_energies"); comm.all_reduce(stream, acc, V_WORDS, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     vir_assemble(sc.inv, 0.0, dbox);      // only the xw sums are non-zero here
   }
 
-  // ---- neighbour search (cell list) ------------------------------------------------------------------
-  CellScratch cells;
-  int nb_na = 0; const T* nb_pos = nullptr; Box<T> nb_box; double nb_rc = 0;
-  long long nb_found = 0;      // pairs the pending count reported
+  // ---- neighbour search and table builds: the arguments checked and turned into a box here, the work in pl (pair_list.h) ----
   void nbr_count(int na, const void* pos, const double* box, double rc, int64_t* n_pairs) override {
     ARG_CHECK(na > 0 && pos && box && rc > 0 && n_pairs, "bad argument");
-    double inv[9], vol;
-    nb_box = make_box(box, inv, &vol);
-    double heights[3];
-    for (int d = 0; d < 3; ++d)   // perpendicular height along lattice direction d = 1 / |column d of box^-1|
-      heights[d] = 1.0 / std::sqrt(inv[0 + d] * inv[0 + d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
-    for (int d = 0; d < 3; ++d) ARG_CHECK(rc <= 0.5 * heights[d] * (1 + 1e-12), "rc exceeds half the box height (minimum image)");
-    nb_na = na; nb_pos = reinterpret_cast<const T*>(pos); nb_rc = rc;
-    long long n = 0;
-    TIMED("neighbor_count");
-    int r = cell_count_pairs<T>(stream, na, nb_pos, nb_box, heights, rc, cells, &n);
-    if (r != 0) throw Err{ADMP_E_HIP, std::string("cell_count_pairs: ") + hipGetErrorString((hipError_t)r)};
-    nb_found = n;
-    *n_pairs = (int64_t)n;
+    double inv[9], vol, heights[3];
+    const Box<T> b = make_box(box, inv, &vol);
+    cell_heights_within(inv, heights, rc);
+    pl.count<T>(na, reinterpret_cast<const T*>(pos), b, heights, rc, n_pairs);
   }
-  void nbr_fill(int32_t* pairs) override {
-    ARG_CHECK(nb_pos, "admp_neighbor_count must precede admp_neighbor_fill");
-    // no pair within rc (one atom, a dilute gas) is a valid answer: nothing to write, the output may be NULL
-    ARG_CHECK(pairs || nb_found == 0, "null output for a non-empty pair list");
-    const T* pos = nb_pos;
-    nb_pos = nullptr;                            // the pending count is spent, whatever the fill returns
-    if (nb_found == 0) return;
-    TIMED("neighbor_fill");
-    int r = cell_fill_pairs<T>(stream, nb_na, pos, nb_box, nb_rc, cells, pairs);
-    if (r != 0) throw Err{ADMP_E_HIP, std::string("cell_fill_pairs: ") + hipGetErrorString((hipError_t)r)};
-  }
+  void nbr_fill(int32_t* pairs) override { pl.fill<T>(pairs); }
 
-  // admp_prune_pairs: from now on the calculators walk the entries of the current table that lie below rc (see EngineBase::pruned)
-  DevBuf prune_rowptr, prune_cnt, prune_col;
+  // admp_prune_pairs: from now on the calculators walk the entries of the current table that lie below rc (PairList::prune)
   void prune_pairs(const void* pos, const double* box, double rc) override {
-    ARG_CHECK(have_top && have_pairs, "a pair list must be set before it can be pruned");
-    ARG_CHECK(!nbr_src, "prune the lender's table: a borrowed one follows it");
+    pl.require_own_table();
     ARG_CHECK(snranks == 1, "admp_prune_pairs: single-rank handles only");
     ARG_CHECK(pos && box, "null argument");
-    if (rc <= 0) { unprune(); return; }
-    unprune();                                   // (always from the table as built)
-    const int na = top.na;
     double inv[9], vol;
     const Box<T> b = make_box(box, inv, &vol);
-    const size_t entries = 2 * (size_t)nbr.n_half;
-    prune_rowptr.need(sizeof(int) * ((size_t)na + 1));
-    prune_cnt.need(sizeof(int) * ((size_t)na + 1));
-    prune_col.need(sizeof(int) * (entries + 1));
-    int64_t total = 0;
-    TIMED("prune_pairs");
-    const int r = prune_table<T>(stream, na, nbr, reinterpret_cast<const T*>(pos), b, rc, prune_rowptr.as<int>(),
-                                 prune_cnt.as<int>(), prune_col.as<int>(), &scan_scratch.p, &scan_bytes, &total);
-    if (r != 0) throw Err{ADMP_E_HIP, std::string("prune_table: ") + hipGetErrorString((hipError_t)r)};
-    nbr_full = nbr;
-    nbr.rowptr = prune_rowptr.as<int>();
-    nbr.col = prune_col.as<int>();
-    nbr.n_half = total / 2;
-    nbr.cap = (int64_t)entries + 1;
-    nbr.col_alt = nullptr; nbr.cap_alt = 0;      // (build scratch of the full table: not this one's)
-    nbr.deg = nullptr; nbr.deg_na = 0;
-    pruned = true;
-    ++nbr_gen;
+    pl.prune<T>(top.na, reinterpret_cast<const T*>(pos), b, rc);
   }
   void nbr_table(const void* pos, const double* box, double rc) override {
     ARG_CHECK(have_top, "admp_set_topology must precede admp_set_pairs_from_positions");
     ARG_CHECK(pos && box && rc > 0, "bad argument");
-    unprune();
-    detach_shared();
-    double inv[9], vol;
-    Box<T> b = make_box(box, inv, &vol);
-    double heights[3];
-    for (int d = 0; d < 3; ++d)
-      heights[d] = 1.0 / std::sqrt(inv[0 + d] * inv[0 + d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
-    for (int d = 0; d < 3; ++d) ARG_CHECK(rc <= 0.5 * heights[d] * (1 + 1e-12), "rc exceeds half the box height (minimum image)");
+    double inv[9], vol, heights[3];
+    const Box<T> b = make_box(box, inv, &vol);
+    cell_heights_within(inv, heights, rc);
     // Slab rank with a mesh (round 4): only the rows of the atoms whose stencil base plane lies within the rank's slab plus a
     // margin -- half the list cutoff (far more than half a skin) plus 4 planes for the pair potentials' slab rule -- are built:
     // the search then costs the rank its share of the box, not the box.  ADMP_SLAB_ROWS=0: every row on every rank.
@@ -2058,13 +1841,7 @@ struct Engine : EngineBase {
       const int width = (mc.X1 - mc.X0) + 2 * mp;
       if (width < K[0]) { rf.on = 1; rf.K0 = K[0]; rf.lo = ((mc.X0 - mp) % K[0] + K[0]) % K[0]; rf.width = width; }
     }
-    TIMED("neighbor_table");
-    int r = cell_build_table<T>(stream, top, reinterpret_cast<const T*>(pos), b, heights, rc, cells, nbr, rf);
-    if (r != 0) throw Err{ADMP_E_HIP, std::string("cell_build_table: ") + hipGetErrorString((hipError_t)r)};
-    apply_classes();
-    order_rows();
-    have_pairs = true;
-    ++nbr_gen;
+    pl.build_from_positions<T>(top, reinterpret_cast<const T*>(pos), b, heights, rc, rf);
   }
 
   void slab_info(int64_t* o) override {
@@ -2099,7 +1876,7 @@ struct Engine : EngineBase {
   struct ScalarRows { const int* rows; int n; const int* home; };
   ScalarRows scalar_rows(const T* pos, const RecipGeom<T>& g, int K0v, int X0v, int X1v, bool need_bases) {
     const int na = top.na;
-    const int* order = nbr.order_plain ? nbr.order_plain : nbr.order;
+    const int* order = pl.table().order_plain ? pl.table().order_plain : pl.table().order;
     if (snranks > 1 || need_bases) {
       bases_d.need(sizeof(int4) * (size_t)na);
       TIMED("atom_bases");
@@ -2363,7 +2140,7 @@ struct Engine : EngineBase {
   }
   void disp(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
             void* dpos_, int on_device) override {
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(snranks == 1 || on_device, "a slab-decomposed handle takes device pointers");
     ARG_CHECK(pos_ && box && clist_ && E, "null argument");
     ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
@@ -2384,7 +2161,7 @@ struct Engine : EngineBase {
     const bool typed = path == DispPath::BricksTyped || path == DispPath::DftTyped;
     if (snranks > 1) ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
     const ScalarRows sr = scalar_rows(sc.pos, g, K[0], mc.X0, mc.X1, bricks);
-    { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
+    { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, pl.table(), pack_srows(sc.pos, sc.par, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
     switch (path) {
       case DispPath::BricksTyped: disp_bricks_typed(sc, g, sr, nch); break;
       case DispPath::BricksBatched: disp_bricks(sc, g, sr, nch, true); break;
@@ -2411,7 +2188,7 @@ struct Engine : EngineBase {
 
   void tt(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, double* E, void* dpos_,
           int on_device) override {
-    ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
+    ARG_CHECK(have_top && pl.have(), "topology and pairs must be set first");
     ARG_CHECK(snranks == 1 || on_device, "a slab-decomposed handle takes device pointers");
     ARG_CHECK(pos_ && box && abqc_ && E, "null argument");
     const int na = top.na;
@@ -2419,7 +2196,7 @@ struct Engine : EngineBase {
     const ScalarCall sc = scalar_begin(box, ns, mS, pos_, abqc_, 4, dpos_, on_device, E_WORDS);
     ScalarRows sr{nullptr, na, nullptr};
     if (snranks > 1) sr = virtual_slab_rows(sc.pos, sc.inv);
-    { TIMED("tt_pair"); launch_tt_pair<T>(stream, na, nbr, pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
+    { TIMED("tt_pair"); launch_tt_pair<T>(stream, na, pl.table(), pack_srows(sc.pos, sc.par, 4), sc.bx, sc.tab, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
     read_scalar_energies(sc.Ed, E, 1);
     scalar_return_grad(sc, dpos_, on_device);
   }
@@ -2429,7 +2206,7 @@ struct Engine : EngineBase {
   // a quadratic form of the channel's coefficients), the self part 2 kp c.  Device pointers; on request only.
   void disp_param_grad(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS,
                        void* out_) override {
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(pos_ && box && clist_ && out_, "null argument");
     ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
     const int na = top.na;
@@ -2452,7 +2229,7 @@ struct Engine : EngineBase {
       ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
       cls_sites_na = slab_sites_na = -1;
       const ScalarRows sr = scalar_rows(pos, g, K[0], mc.X0, mc.X1, true);
-      launch_scalar_pair_pgrad<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, out, cutoff, sr.rows, sr.n);
+      launch_scalar_pair_pgrad<T>(stream, 0, na, pl.table(), pos, cl, bx, tab, (T)kappa, pmax, out, cutoff, sr.rows, sr.n);
       const size_t nreal = nreal_local();
       mesh.need(nch * nreal * sizeof(T));
       ensure_bins(std::max(sr.n, 1));
@@ -2465,7 +2242,7 @@ struct Engine : EngineBase {
       HIP_TRY(hipStreamSynchronize(stream));
       return;
     }
-    launch_scalar_pair_pgrad<T>(stream, 0, na, nbr, pos, cl, bx, tab, (T)kappa, pmax, out, cutoff);
+    launch_scalar_pair_pgrad<T>(stream, 0, na, pl.table(), pos, cl, bx, tab, (T)kappa, pmax, out, cutoff);
     cls_sites_na = slab_sites_na = -1;
     sites.need(sizeof(Site<T>) * (size_t)na);
     ensure_bins(na);
@@ -2480,7 +2257,7 @@ struct Engine : EngineBase {
   }
   // dE/d(a, b, q, c6) (Na,4) of the Tang-Toennies pair term (admp/pairwise.py:94-113).  Device pointers; on request only.
   void tt_param_grad(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, void* out_) override {
-    ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
+    ARG_CHECK(have_top && pl.have(), "topology and pairs must be set first");
     ARG_CHECK(pos_ && box && abqc_ && out_, "null argument");
     double inv[9], vol;
     Box<T> bx = make_box(box, inv, &vol);
@@ -2488,7 +2265,7 @@ struct Engine : EngineBase {
     const T* pos = reinterpret_cast<const T*>(pos_);
     ScalarRows sr{nullptr, top.na, nullptr};
     if (snranks > 1) sr = virtual_slab_rows(pos, inv);      // (per-atom outputs: the home rows are this rank's results)
-    launch_scalar_pair_pgrad<T>(stream, 1, top.na, nbr, pos, reinterpret_cast<const T*>(abqc_), bx,
+    launch_scalar_pair_pgrad<T>(stream, 1, top.na, pl.table(), pos, reinterpret_cast<const T*>(abqc_), bx,
                                 tab, T(0), 0, reinterpret_cast<T*>(out_), cutoff, sr.rows, sr.n);
     HIP_TRY(hipStreamSynchronize(stream));
   }
@@ -2497,7 +2274,7 @@ struct Engine : EngineBase {
   DevBuf prog_consts;
   void pair_program_eval(int id, const void* pos_, const double* box, const void* par_, int ns, const double* mS, double* E,
                          void* dpos_, int on_device) override {
-    ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
+    ARG_CHECK(have_top && pl.have(), "topology and pairs must be set first");
     ARG_CHECK(id >= 0 && id < (int)programs.size(), "unknown pair program");
     ARG_CHECK(pos_ && box && E && ns >= 1 && mS, "null argument");
     const PairProgram& pg = programs[id];
@@ -2516,7 +2293,7 @@ struct Engine : EngineBase {
     const T* boxd = prog_consts.as<T>();
     const T* mtab = boxd + 18;
     int na_arg = na;
-    const int* rowptr = nbr.rowptr; const int* colp = nbr.col; const int* order = nbr.order;
+    const int* rowptr = pl.table().rowptr; const int* colp = pl.table().col; const int* order = pl.table().order;
     T* gradp = dpos_ ? dpos : nullptr;
     double* eptr = Ed + E_REAL;
     void* args[] = {&na_arg, &rowptr, &colp, &order, &pos, &par, &boxd, &mtab, &gradp, &eptr};
@@ -2556,7 +2333,7 @@ struct Engine : EngineBase {
                  const double* mS, const double* pS, const void* U_, const void* F_, int which, int flags, int on_device,
                  double* E_out, void* grad_, void* pot_, void* fld_, int32_t* info) override {
     ARG_CHECK(snranks == 1, "admp_pair_real works on a single rank only (slab-decomposed handle)");
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(which >= 0 && which <= 2, "which must be 0 (closing pair kernel), 1 (SCF field kernel) or 2 (its increment)");
     ARG_CHECK(which == 0 || lpol, "the field kernels need a polarizable handle");
     ARG_CHECK(pos_ && box && Ql_ && E_out && info, "null argument");
@@ -2594,17 +2371,12 @@ struct Engine : EngineBase {
       n_rows = nact_known();
       HIP_TRY(hipMemcpyAsync(field.p, F_, 3 * na * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
       HIP_TRY(hipMemsetAsync(fld_pair.p, 0, 3 * na * sizeof(T), stream));
-      if (!cut_on && (ind_nbr_gen != nbr_gen || ind_act_gen != act_gen)) {      // the sub-table, as scf_increment keeps it
-        TIMED("ind_table");
-        int rc = build_ind_table<T>(stream, top.na, nbr, sites.as<Site<T>>(), ind);
-        if (rc != 0) throw Err{ADMP_E_HIP, std::string("build_ind_table: ") + hipGetErrorString((hipError_t)rc)};
-        ind_nbr_gen = nbr_gen; ind_act_gen = act_gen;
-      }
+      ensure_ind_table();      // the sub-table, as scf_increment keeps it
       scf_jacobi(n_rows);
       if (n_rows > 0) { TIMED("pair_field_ind"); launch_pair_field_ind<T>(stream, pair_field_ind_args(n_rows)); }
     }
     ev.active = false;
-    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach the pair list as in an evaluation)
     nact_seen();
     int w[2];
     std::memcpy(w, &Eh[E_NACT], sizeof(w));
@@ -2633,7 +2405,7 @@ struct Engine : EngineBase {
   MeshIn mesh_stage(const char* who, const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_,
                     const void* U_, int on_device) {
     if (snranks != 1) throw Err{ADMP_E_ARG, std::string(who) + " works on a single rank only (slab-decomposed handle)"};
-    ARG_CHECK(have_top && have_ewald && have_pairs, "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
     ARG_CHECK(pos_ && box && Ql_, "null argument");
     if (lpol) ARG_CHECK(pol_ && thole_ && U_, "polarizable handle needs pol, tholes and U");
     const size_t na = (size_t)top.na;
@@ -2691,7 +2463,7 @@ struct Engine : EngineBase {
     ev.active = false;
     if (!on_device) HIP_TRY(hipMemcpyAsync(mesh_out, m, nreal * sizeof(T), hipMemcpyDeviceToHost, stream));
     double E[4];
-    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    read_energies(E_RECIP, E);      // (one synchronisation; the class flags of this call reach the pair list as in an evaluation)
     nact_seen();
     scf.forget();
   }
@@ -2760,7 +2532,7 @@ struct Engine : EngineBase {
     mesh_begin(in, box);
     ev.active = false;
     double E[4];
-    read_energies(E_RECIP, E);       // (one synchronisation; the class flags of this call reach cls_seen as in an evaluation)
+    read_energies(E_RECIP, E);       // (one synchronisation; the class flags of this call reach the pair list as in an evaluation)
     int w[2];
     std::memcpy(w, &Eh[E_NACT], sizeof(w));
     const int n_act = lpol ? w[0] : 0;
@@ -2869,7 +2641,7 @@ struct Engine : EngineBase {
   // negative-index wrap for non-bonded pairs) of the class sums produced by launch_mscale_sums
   void mscale_grad(int kind, const void* pos_, const double* box, const void* par_, int pmax, int ns, double* out,
                    int on_device) override {
-    ARG_CHECK(have_top && have_pairs, "topology and pairs must be set first");
+    ARG_CHECK(have_top && pl.have(), "topology and pairs must be set first");
     ARG_CHECK(pos_ && box && par_ && out && ns >= 1 && ns <= 16, "bad argument");
     ARG_CHECK(kind >= 0 && kind <= 2, "kind must be 0 (multipolar PME), 1 (dispersion) or 2 (Tang-Toennies)");
     ARG_CHECK(snranks == 1 || on_device, "a slab-decomposed handle takes device pointers");
@@ -2897,7 +2669,7 @@ struct Engine : EngineBase {
       if (have_ewald) { update_slab(); sr = scalar_rows(pos, make_geom(inv), K[0], mc.X0, mc.X1, true); }
       else sr = virtual_slab_rows(pos, inv);      // a pair potential has no mesh, as in tt()
     }
-    { TIMED("mscale_grad"); launch_mscale_sums<T>(stream, kind, na, nbr, sites.as<Site<T>>(), pos, par, bx, pmax, cls, cutoff,
+    { TIMED("mscale_grad"); launch_mscale_sums<T>(stream, kind, na, pl.table(), sites.as<Site<T>>(), pos, par, bx, pmax, cls, cutoff,
                                                   sr.rows, sr.n); }
     if (snranks > 1) { TIMED("comm_energies"); comm.all_reduce(stream, cls, 16, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES); }
     double h16[16];
@@ -2923,7 +2695,7 @@ static int guarded(admp_handle* h, F&& f) {
   try {
     (void)hipSetDevice(h->eng->device);
     (void)hipGetLastError();                 // drop anything stale from other users of this thread
-    h->eng->adopt_shared();
+    h->eng->pl.adopt(h->eng->top.na);
     f(*h->eng);
     // a bad launch configuration (too much LDS, too many registers after a flag change, ...) is reported by neither the
     // launch statement nor hipStreamSynchronize: every <<<>>> of this call is covered by one check here
@@ -2967,7 +2739,7 @@ int admp_create(admp_handle** out, int device, int precision) {
     e->own_stream = true;
     admp_handle* h = new admp_handle();
     h->eng = std::move(e);
-    { std::lock_guard<std::mutex> g(EngineBase::live_mu()); EngineBase::live().insert(h->eng.get()); }
+    PairList::register_live(&h->eng->pl);
     *out = h;
     return ADMP_OK;
   } catch (const Err& e) {
@@ -2981,7 +2753,7 @@ int admp_destroy(admp_handle* h) {
   if (h->eng) {
     (void)hipSetDevice(h->eng->device);
     (void)hipStreamSynchronize(h->eng->stream);
-    { std::lock_guard<std::mutex> g(EngineBase::live_mu()); EngineBase::live().erase(h->eng.get()); }
+    PairList::unregister_live(&h->eng->pl);
   }
   delete h;
   return ADMP_OK;
@@ -3031,7 +2803,7 @@ int admp_share_neighbors(admp_handle* h, admp_handle* lender) {
   });
 }
 
-int64_t admp_num_pairs(const admp_handle* h) { return (h && h->eng) ? h->eng->nbr.n_half : -1; }
+int64_t admp_num_pairs(const admp_handle* h) { return (h && h->eng) ? h->eng->pl.num_pairs() : -1; }
 
 int admp_pme_energy_grad(admp_handle* h, const void* positions, const double* box, const void* Q_local,
                          const void* pol, const void* tholes, int n_scales, const double* mScales,

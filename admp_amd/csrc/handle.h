@@ -1,6 +1,6 @@
 // The least a translation unit outside engine.hip needs from a handle: where it runs, how it is timed, and a slot for state of
-// its own that dies with the handle.  EngineBase (engine.hip) derives from HandleCtx; md_driver.hip and mesh_conv.hip see a
-// handle through it.
+// its own that dies with the handle.  EngineBase (engine.hip) derives from HandleCtx; md_driver.hip, mesh_conv.hip and pair_list.hip see
+// a handle through it.
 #pragma once
 #include <memory>
 #include <type_traits>

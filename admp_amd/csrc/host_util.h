@@ -1,5 +1,5 @@
-// Host helpers shared by the translation units behind the C ABI (engine.hip, mesh_conv.hip, md_driver.hip): the error type and its macros
-// (err.h), the per-label profiler, and the box handed to the kernels.
+// Host helpers shared by the translation units behind the C ABI (engine.hip, mesh_conv.hip, pair_list.hip, md_driver.hip): the error type and its macros
+// (err.h), the per-label profiler, the box handed to the kernels and its heights.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,6 +93,16 @@ Box<T> make_box(const double* h, double* inv, double* vol) {
   ARG_CHECK(std::fabs(*vol) > 1e-12, "singular box");
   for (int k = 0; k < 9; ++k) { b.h[k] = (T)h[k]; b.hinv[k] = (T)inv[k]; }
   return b;
+}
+
+// perpendicular heights of the cell along its lattice directions: h[d] = 1 / |column d of box^-1|
+inline void cell_heights(const double* inv, double* h) {
+  for (int d = 0; d < 3; ++d) h[d] = 1.0 / std::sqrt(inv[0 + d] * inv[0 + d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
+}
+// ... for a minimum-image cutoff rc, which must not exceed half of any of them
+inline void cell_heights_within(const double* inv, double* h, double rc) {
+  cell_heights(inv, h);
+  for (int d = 0; d < 3; ++d) ARG_CHECK(rc <= 0.5 * h[d] * (1 + 1e-12), "rc exceeds half the box height (minimum image)");
 }
 
 }  // namespace admp

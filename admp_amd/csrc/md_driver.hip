@@ -393,7 +393,7 @@ struct MdDriver : HandleExt {
     const Box<T> bx = finite_box(box);
     double inv[9], vol, heights[3];
     invert3(box, inv, &vol);
-    for (int d = 0; d < 3; ++d) heights[d] = 1.0 / std::sqrt(inv[0 + d] * inv[0 + d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
+    cell_heights(inv, heights);
     const RdfPlan p = rdf_make_plan(n, heights, r_max, n_types, n_bins, sizeof(T), force);
     if (p.error) throw Err{ADMP_E_ARG, p.error};
     if (info4) {

@@ -62,7 +62,8 @@ def used_slots(at):
 
 
 def group_layout(at, ai):
-    """What admp_set_topology derives (engine.hip): the inverse frame map and, when every connected component of "site i uses
+    """What admp_set_topology derives (admp_amd/csrc/topology_plan.h `topology_plan`, restated here; compared array for array
+    by tests/test_topology_plan_cpu.py): the inverse frame map and, when every connected component of "site i uses
     atom m" is a run of at most 4 consecutive atoms, the frame groups and their runs.  Returns dict(inv, groups, rows_blk,
     gath_blk); groups is None when the topology is not made of groups."""
     at, ai = np.asarray(at), np.asarray(ai)

@@ -90,6 +90,44 @@ def test_pair_list_refusals(precision):
     assert L.admp_neighbor_fill(h, None) != 0                      # the pending count was spent
 
 
+def test_a_refused_build_leaves_the_list_as_it_was(precision):
+    """A list build or a count that is refused for its arguments changes nothing: the inner list stays in force, a loan goes
+    on, the pending count still belongs to its own box."""
+    import torch
+    from admp_amd import _lib
+    from tests.test_gpu_pair_list_states import R1, below, handle, system
+    from tests.test_gpu_pme_cutoff import RC, SKIN
+    settings.PRECISION = 'double'
+    A = system(216, 36)
+    w = dict(box=A['box'])
+    n_skin, n1 = below(A, RC + SKIN), below(A, R1)
+    too_far = 0.5 * A['box'][0, 0] * 1.01
+    f, b = handle(w, A), handle(w, A)
+    f.update_neighbors(A['pos'], A['box'], rc=RC + SKIN)
+    f.prune_neighbors(A['pos'], A['box'], R1)
+    b.share_neighbors(f)
+    assert f.n_pairs == n1 < n_skin and b.n_pairs == n1
+    for g in (f, b):
+        with pytest.raises(_lib.AdmpHipError, match='half the box height'):
+            g.update_neighbors(A['pos'], A['box'], rc=too_far)
+        assert g._L.admp_set_pairs(g._h, -1, None, 1) == _lib.E_ARG and b'negative pair count' in g._L.admp_last_error(g._h)
+        assert g.n_pairs == n1
+    f.prune_neighbors(A['pos'], A['box'], 0.0)
+    assert f._L.admp_synchronize(b._h) == 0 and b.n_pairs == n_skin      # (any call of the borrower: it still follows f)
+    # a refused count leaves the pending one alone
+    L, h = f._L, f._h
+    pos = torch.as_tensor(A['pos'], device='cuda')
+    box = _lib.darr(np.asarray(A['box'], dtype=np.float64).reshape(-1))
+    n, m = ctypes.c_int64(0), ctypes.c_int64(0)
+    assert L.admp_neighbor_count(h, A['na'], pos.data_ptr(), box, RC, ctypes.byref(n)) == 0 and n.value == len(A['exact'])
+    assert L.admp_neighbor_count(h, A['na'], pos.data_ptr(), box, too_far, ctypes.byref(m)) == _lib.E_ARG
+    out = torch.full((n.value, 2), -1, dtype=torch.int32, device='cuda')
+    assert L.admp_neighbor_fill(h, out.data_ptr()) == 0
+    torch.cuda.synchronize()
+    got = np.sort(out.cpu().numpy(), axis=1)
+    assert np.array_equal(got[np.lexsort((got[:, 1], got[:, 0]))], A['exact'])
+
+
 # ---- (b), (c): the Tang-Toennies observable ------------------------------------------------------------------------------------
 def tt_calculator(s):
     from admp_amd.pairwise import generate_pairwise_interaction, TT_damping_qq_c6_kernel
