@@ -1,8 +1,8 @@
 // libadmp_hip: handle, device buffers, and the orchestration of one get_energy / get_forces evaluation behind the C ABI of
 // include/admp_hip.h.  The k-space leg between spread and gather (rocFFT plans, tables, every transform path) is MeshConv,
 // mesh_conv.hip; the neighbour table between two evaluations (builds, site classes, inner lists, loans) and the cell-list search
-// are PairList, pair_list.hip; what a topology implies for the closing kernels is topology_plan.h; the MD entries are
-// md_driver.hip.
+// are PairList, pair_list.hip; what a topology implies for the closing kernels is topology_plan.h; the decomposition of a slab
+// rank and its halo exchanges are SlabDecomp, slab_decomp.hip; the MD entries are md_driver.hip.
 //
 // Flow of admp_pme_energy_grad (reference call stack: admp/pme.py:58-86 get_energy ->
 // :111-143 optimize_Uind -> :176-254 energy_pme, gradient by jax.value_and_grad :108):
@@ -39,6 +39,7 @@
 #include "rccl_comm.h"
 #include "scf_policy.h"
 #include "scf_aspc.h"
+#include "slab_decomp.h"
 #include "topology_plan.h"
 
 using namespace admp;
@@ -98,6 +99,8 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
   int side_stream_on = 1;       // ADMP_OPT_SIDE_STREAM: 0 keeps every kernel on the handle's stream (clean per-kernel event times)
   // a call that failed half way: whatever it left on a helper stream is waited for before the error is reported
   virtual void after_error() {}
+  // the topology is being replaced or freed: whatever the engine remembers of the atoms it described goes too
+  virtual void topology_gone() {}
   // admp_share_neighbors: the calculators of one system walk ONE compiled table instead of compiling the same pair list once each
   void share_neighbors(EngineBase* src) {
     ARG_CHECK(have_top, "admp_set_topology must precede admp_share_neighbors");
@@ -202,6 +205,7 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
     top_d.release();
     top = Topology();
     pl.drop();
+    topology_gone();
     slab_sites_na = -1;
     have_top = false;
   }
@@ -253,20 +257,6 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
     ARG_CHECK(have_top, "admp_set_topology must precede admp_set_pairs");
     pl.set_pairs(top, n_rows, pairs, on_device);
   }
-};
-
-// decomposition state of one evaluation on a slab rank (snranks > 1; slab_kernels.hip)
-struct SlabState {
-  DevBuf owner, owner_prev, mig, bits, counts, totals, lists, imp, exp, mig_in, mig_out, sendb, recvb;
-  int prev_na = -1;             // owner_prev holds the owners of this handle's previous decomposed evaluation of prev_na atoms
-  int64_t min_cnt[kSlabMaxRanks], mout_cnt[kSlabMaxRanks];   // atoms taken over from / given away to every rank since then
-  int n_min = 0, n_mout = 0;
-  int64_t imp_cnt[kSlabMaxRanks], exp_cnt[kSlabMaxRanks];     // atoms imported from / exported to every rank
-  int n_home = 0, n_act = 0, n_imp = 0, n_exp = 0;
-  bool tracked = false;         // the last decomposition compared its owners with the previous one's (mig_in / mig_out are lists)
-  const int* home = nullptr;    // home atoms, ascending
-  const int* rows = nullptr;    // home rows in the pair kernels' order (the table's class-grouped order, filtered)
-  const int* act = nullptr;     // polarizable home atoms, ascending
 };
 
 template <class T>
@@ -348,185 +338,33 @@ struct Engine : EngineBase {
   // ---- slab bounds: rank s owns mesh planes [X0, X1) along x, plus kGhost overhang planes above X1 (MeshConv::update_slab) ----
   static constexpr int kGhost = MeshConv<T>::kGhost;
   void update_slab() { mc.update_slab(K); }
-  // ---- decomposition state of one evaluation (snranks > 1; slab_kernels.hip) ------------------------------------------
-  SlabState sl;
-  static constexpr int real_dtype() { return sizeof(T) == 4 ? ADMP_T_F32 : ADMP_T_F64; }
-  // Who owns what in this evaluation, derived by every rank from the replicated inputs (no communication): home atoms, home
-  // rows in pair-kernel order, polarizable home atoms, imports per owner, exports per reader.  One host read (the counts).
-  void decompose() { decompose(K[0], mc.X0, mc.X1, pl.table().order, lpol != 0); }
-  // K0v / X0v / X1v: the planes the ownership rule works on (the PME mesh's; a handle without a mesh takes a virtual one);
-  // order: the row order of the table to filter (nullptr: natural order); with_dipoles: the evaluation carries induced
-  // dipoles from call to call (atoms that change hands take theirs along)
-  void decompose(int K0v, int X0v, int X1v, const int* order, bool with_dipoles = false) {
-    const int na = top.na, N = snranks, me = srank;
-    ARG_CHECK(N <= kSlabMaxRanks, "at most 28 slab ranks");
-    sl.owner.need(sizeof(int) * (size_t)na);
-    sl.bits.need(sizeof(int) * (size_t)na);
-    // Atoms that changed hands since the previous evaluation (the home rule follows the positions): their dipoles are valid on
-    // the PREVIOUS owner only when the caller keeps home rows (outputs of a decomposed call), so they travel with the atom.
-    const bool track = with_dipoles && sl.prev_na == na && sl.owner_prev.p;
-    sl.owner_prev.need(sizeof(int) * (size_t)na);
-    if (track) sl.mig.need(sizeof(int) * (size_t)na);
-    // Columns of the ordered compaction.  Only `rows` (the home rows in the table's order: a different sequence) takes a pass
-    // of its own; home / polarizable home / the per-peer import, export and migrant columns are bins of ONE pass over the atoms
-    // (slab_kernels.hip k_slab_bins; ADMP_SLAB_BINS=0: a pass per column as in round 3, for A/B and tests).
-    static const bool bins_on = env_flag("ADMP_SLAB_BINS", true);
-    SlabCols cs;
-    SlabBins sb;
-    sb.N = bins_on ? N : 0; sb.me = me;
-    auto col = [&](const int* seq, int len, int mask, int want, const int* src = nullptr, bool binned = false) {
-      cs.seq[cs.ncols] = seq; cs.len[cs.ncols] = len; cs.mask[cs.ncols] = mask; cs.want[cs.ncols] = want; cs.src[cs.ncols] = src;
-      cs.binned[cs.ncols] = binned && bins_on ? 1 : 0;
-      return cs.ncols++;
-    };
-    const int c_home = col(nullptr, na, kSlabHome, kSlabHome, nullptr, true);
-    const int c_rows = col(order, na, kSlabHome, kSlabHome);
-    const int c_act = col(nullptr, na, kSlabHome | kSlabPolar, kSlabHome | kSlabPolar, nullptr, true);
-    sb.c_home = c_home; sb.c_act = c_act;
-    int c_imp[kSlabMaxRanks], c_exp[kSlabMaxRanks], c_min[kSlabMaxRanks], c_mout[kSlabMaxRanks];
-    for (int t = 0; t < kSlabMaxRanks; ++t) sb.c_imp[t] = sb.c_exp[t] = sb.c_min[t] = sb.c_mout[t] = -1;
-    for (int t = 0; t < N; ++t) {
-      c_imp[t] = c_exp[t] = c_min[t] = c_mout[t] = -1;
-      if (t == me) continue;
-      c_imp[t] = col(nullptr, na, kSlabHome | (1 << t), 1 << t, nullptr, true);
-      c_exp[t] = col(nullptr, na, kSlabHome | (1 << t), kSlabHome | (1 << t), nullptr, true);
-      if (track) {
-        c_min[t] = col(nullptr, na, kSlabHome | (1 << t), 1 << t, sl.mig.as<int>(), true);
-        c_mout[t] = col(nullptr, na, kSlabHome | (1 << t), kSlabHome | (1 << t), sl.mig.as<int>(), true);
-      }
-      sb.c_imp[t] = c_imp[t]; sb.c_exp[t] = c_exp[t]; sb.c_min[t] = c_min[t]; sb.c_mout[t] = c_mout[t];
-    }
-    sl.counts.need(sizeof(int) * (size_t)cs.ncols * (size_t)std::max(1, slab_compact_blocks(na)));
-    sl.totals.need(sizeof(int) * (kSlabMaxCols + 1));
-    sl.lists.need(sizeof(int) * (size_t)cs.ncols * (size_t)na);
-    {
-      TIMED("slab_decompose");
-      int rc = launch_slab_decompose(stream, na, pl.table(), top, ev.bases, ev.pol, (int)sizeof(T), X1v - X0v, K0v, X0v, N, me,
-                                     sl.owner.as<int>(), sl.bits.as<int>(), cs, sb, sl.counts.as<int>(), sl.totals.as<int>(),
-                                     sl.lists.as<int>(), track ? sl.owner_prev.as<int>() : nullptr, track ? sl.mig.as<int>() : nullptr);
-      if (rc != 0) throw Err{ADMP_E_HIP, std::string("slab decomposition: ") + hipGetErrorString((hipError_t)rc)};
-    }
-    int tot[kSlabMaxCols + 1];
-    HIP_TRY(hipMemcpyAsync(tot, sl.totals.p, sizeof(int) * (cs.ncols + 1), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (tot[cs.ncols])
-      throw Err{ADMP_E_STATE, "an atom entered this rank's slab whose row the neighbour table does not hold: the table of a slab "
-                              "rank covers its slab plus a margin of half the list cutoff (admp_set_pairs_from_positions) -- "
-                              "rebuild the pair list"};
-    const int* L = sl.lists.as<int>();
-    sl.n_home = tot[c_home]; sl.home = L + (size_t)c_home * na;
-    sl.rows = L + (size_t)c_rows * na;
-    sl.n_act = tot[c_act]; sl.act = L + (size_t)c_act * na;
-    if (tot[c_rows] != sl.n_home) throw Err{ADMP_E_STATE, "slab decomposition: row order and home list disagree"};
-    SlabSegs si, se;
-    si.off[0] = se.off[0] = 0;
-    for (int t = 0; t < N; ++t) {
-      sl.imp_cnt[t] = t == me ? 0 : tot[c_imp[t]];
-      sl.exp_cnt[t] = t == me ? 0 : tot[c_exp[t]];
-      if (t == me) continue;
-      si.col[si.n] = c_imp[t]; si.off[si.n + 1] = si.off[si.n] + tot[c_imp[t]]; ++si.n;
-      se.col[se.n] = c_exp[t]; se.off[se.n + 1] = se.off[se.n] + tot[c_exp[t]]; ++se.n;
-    }
-    sl.n_imp = si.off[si.n]; sl.n_exp = se.off[se.n];
-    sl.imp.need(sizeof(int) * (size_t)std::max(1, sl.n_imp));
-    sl.exp.need(sizeof(int) * (size_t)std::max(1, sl.n_exp));
-    launch_slab_concat(stream, si, L, (long)na, sl.imp.as<int>());
-    launch_slab_concat(stream, se, L, (long)na, sl.exp.as<int>());
-    sl.n_min = sl.n_mout = 0;
-    sl.tracked = track;
-    if (track) {
-      SlabSegs mi, mo;
-      mi.off[0] = mo.off[0] = 0;
-      for (int t = 0; t < N; ++t) {
-        sl.min_cnt[t] = t == me ? 0 : tot[c_min[t]];
-        sl.mout_cnt[t] = t == me ? 0 : tot[c_mout[t]];
-        if (t == me) continue;
-        mi.col[mi.n] = c_min[t]; mi.off[mi.n + 1] = mi.off[mi.n] + tot[c_min[t]]; ++mi.n;
-        mo.col[mo.n] = c_mout[t]; mo.off[mo.n + 1] = mo.off[mo.n] + tot[c_mout[t]]; ++mo.n;
-      }
-      sl.n_min = mi.off[mi.n]; sl.n_mout = mo.off[mo.n];
-      sl.mig_in.need(sizeof(int) * (size_t)std::max(1, sl.n_min));
-      sl.mig_out.need(sizeof(int) * (size_t)std::max(1, sl.n_mout));
-      launch_slab_concat(stream, mi, L, (long)na, sl.mig_in.as<int>());
-      launch_slab_concat(stream, mo, L, (long)na, sl.mig_out.as<int>());
-    }
-    // the owners of this evaluation are the "previous owners" of the next one
-    HIP_TRY(hipMemcpyAsync(sl.owner_prev.p, sl.owner.p, sizeof(int) * (size_t)na, hipMemcpyDeviceToDevice, stream));
-    sl.prev_na = with_dipoles ? na : -1;
-    const size_t w = 9 * sizeof(T) * (size_t)std::max(1, std::max(std::max(sl.n_imp, sl.n_exp), std::max(sl.n_min, sl.n_mout)));
-    sl.sendb.need(w); sl.recvb.need(w);
-    ev.n_home = sl.n_home;
-    ev.home = sl.home;
+  // ---- the decomposition of one evaluation and its halo exchanges (snranks > 1): sl, slab_decomp.h -------------------------
+  SlabDecomp<T> sl{this, &comm};
+  void topology_gone() override { sl.forget(); }
+  // K0v / X0v / X1v: the planes the ownership rule works on (the PME mesh's; a handle without a mesh takes a virtual one)
+  typename SlabDecomp<T>::In slab_in(const int4* bases, const T* pol, int K0v, int X0v, int X1v, const int* order, bool with_dipoles) {
+    typename SlabDecomp<T>::In in;
+    in.na = top.na; in.nbr = &pl.table(); in.top = &top; in.bases = bases; in.pol = pol;
+    in.K0v = K0v; in.X0v = X0v; in.X1v = X1v; in.order = order; in.with_dipoles = with_dipoles;
+    return in;
   }
-  // the dipoles of the atoms that changed hands: previous owner -> new owner
-  void exchange_migrants() {
-    TIMED("comm_halo_dipoles");                            // (every rank takes part: the caller's condition is rank-uniform)
-    int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
-    for (int t = 0; t < snranks; ++t) { sc[t] = 3 * sl.mout_cnt[t]; rc[t] = 3 * sl.min_cnt[t]; }
-    launch_halo_u_pack<T>(stream, sl.n_mout, 0, sl.mig_out.as<int>(), ev.U, sites.as<Site<T>>(), sl.sendb.as<T>());
-    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
-    launch_halo_u_unpack<T>(stream, sl.n_min, 0, sl.mig_in.as<int>(), sl.recvb.as<T>(), ev.U, sites.as<Site<T>>());
+  // the decomposition of an electrostatics evaluation on the PME mesh: its home atoms become the evaluation's, the dipoles of
+  // the atoms that changed hands go to their new owners and every rank gets the dipoles of the atoms it reads
+  // (prepare: what the caller still has to do to the site rows once the lists are known, ahead of the exchanges that write them)
+  template <class F>
+  void decompose_eval(F&& prepare) {
+    const bool tracked = sl.will_track(top.na, lpol != 0);      // (decompose() then lists the atoms that changed hands)
+    sl.decompose(slab_in(ev.bases, ev.pol, K[0], mc.X0, mc.X1, pl.table().order, lpol != 0));
+    ev.n_home = sl.n_home();
+    ev.home = sl.home();
+    prepare();
+    if (tracked) sl.exchange_migrants(ev.U, sites.as<Site<T>>());
+    if (lpol) sl.exchange_dipoles(0, ev.U, sites.as<Site<T>>());
   }
-  // rows of width w of the halo atoms: owners -> readers (to_readers: exports out, imports in) or back (gradient contributions)
-  void halo_counts(int w, bool to_readers, int64_t* sc, int64_t* rc) const {
-    for (int t = 0; t < snranks; ++t) {
-      sc[t] = (to_readers ? sl.exp_cnt[t] : sl.imp_cnt[t]) * w;
-      rc[t] = (to_readers ? sl.imp_cnt[t] : sl.exp_cnt[t]) * w;
-    }
-  }
-  // what 0: the Cartesian dipoles of the atoms this rank reads <- their owners' values (start of an evaluation: the result
-  // must not depend on rows of U the rank does not own); what 1: the last Jacobi step's change of those dipoles
-  void exchange_U(int what) {
-    TIMED("comm_halo_dipoles");
-    int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
-    halo_counts(3, true, sc, rc);
-    launch_halo_u_pack<T>(stream, sl.n_exp, what, sl.exp.as<int>(), ev.U, sites.as<Site<T>>(), sl.sendb.as<T>());
-    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_DIPOLES);
-    launch_halo_u_unpack<T>(stream, sl.n_imp, what, sl.imp.as<int>(), sl.recvb.as<T>(), ev.U, sites.as<Site<T>>());
-  }
-  // what the closing kernel added to atoms of other ranks (frame adjoint of molecules across a slab face) goes to the owners
-  void exchange_grad(T* grad_p) {
-    TIMED("comm_halo_gradient");
-    int64_t sc[kSlabMaxRanks], rc[kSlabMaxRanks];
-    halo_counts(3, false, sc, rc);
-    launch_rows_gather<T>(stream, sl.n_imp, 3, sl.imp.as<int>(), grad_p, sl.sendb.as<T>());
-    comm.all_to_all_v(stream, sl.sendb.p, sc, sl.recvb.p, rc, real_dtype(), ADMP_TAG_HALO_GRADIENT);
-    launch_rows_scatter<T>(stream, 1, sl.n_exp, 3, sl.exp.as<int>(), sl.recvb.as<T>(), grad_p);
-  }
-  void slab_home(int32_t* out, int* n_home, int* n_import) override {
-    ARG_CHECK(snranks > 1 && sl.home, "no decomposed evaluation has run on this handle");
-    if (out) HIP_TRY(hipMemcpyAsync(out, sl.home, sizeof(int) * (size_t)sl.n_home, hipMemcpyDeviceToDevice, stream));
-    if (n_home) *n_home = sl.n_home;
-    if (n_import) *n_import = sl.n_imp;
-  }
-  // admp_slab_lists: what decompose() left on the device, copied to the host as it stands (no kernel runs)
+  void slab_home(int32_t* out, int* n_home, int* n_import) override { sl.home_to(out, n_home, n_import); }
   void slab_lists(int na, int nranks, int32_t* owner, int32_t* bits, int32_t* home, int32_t* rows, int32_t* act, int32_t* imp,
                   int32_t* exp, int32_t* mig_in, int32_t* mig_out, int64_t* counts) override {
-    ARG_CHECK(snranks > 1, "admp_slab_lists works on a slab-decomposed handle only");
-    ARG_CHECK(sl.home, "no decomposed evaluation has run on this handle");
-    ARG_CHECK(na == top.na && nranks == snranks, "n_atoms / nranks are not those of the handle");
-    ARG_CHECK(owner && bits && home && rows && act && imp && exp && mig_in && mig_out && counts, "null argument");
-    auto back = [&](int32_t* dst, const void* src, int n) {
-      if (n > 0) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    };
-    back(owner, sl.owner.p, na);
-    back(bits, sl.bits.p, na);
-    back(home, sl.home, sl.n_home);
-    back(rows, sl.rows, sl.n_home);
-    back(act, sl.act, sl.n_act);
-    back(imp, sl.imp.p, sl.n_imp);
-    back(exp, sl.exp.p, sl.n_exp);
-    back(mig_in, sl.mig_in.p, sl.n_min);
-    back(mig_out, sl.mig_out.p, sl.n_mout);
-    HIP_TRY(hipStreamSynchronize(stream));
-    counts[0] = sl.n_home; counts[1] = sl.n_act; counts[2] = sl.n_imp; counts[3] = sl.n_exp;
-    counts[4] = sl.tracked ? 1 : 0; counts[5] = sl.n_min; counts[6] = sl.n_mout; counts[7] = 0;
-    for (int t = 0; t < snranks; ++t) {
-      counts[8 + t] = sl.imp_cnt[t];
-      counts[8 + snranks + t] = sl.exp_cnt[t];
-      counts[8 + 2 * snranks + t] = sl.tracked ? sl.min_cnt[t] : 0;
-      counts[8 + 3 * snranks + t] = sl.tracked ? sl.mout_cnt[t] : 0;
-    }
+    sl.lists_to_host(na, top.na, nranks, owner, bits, home, rows, act, imp, exp, mig_in, mig_out, counts);
   }
   // the residual word of an SCF check: maximum over the ranks (bit patterns of non-negative doubles are doubles)
   void reduce_check_word(unsigned long long* word) {
@@ -675,7 +513,7 @@ struct Engine : EngineBase {
     const int4* bases = nullptr;                 // stencil base indices per atom (written by prepare_sites)
     bool active = false;
   } ev;
-  const int* pair_rows() const { return snranks > 1 ? sl.rows : pl.table().order; }      // row order of the pair kernels
+  const int* pair_rows() const { return snranks > 1 ? sl.rows() : pl.table().order; }      // row order of the pair kernels
 
   int stage_begin(const void* pos_, const double* box, const void* Ql_, const void* pol_, const void* thole_, int ns,
                   const double* mS, const double* pS, void* U_) {
@@ -730,21 +568,17 @@ struct Engine : EngineBase {
       ev.bases = bases_d.as<int4>();
       cls_sites_na = na;
       pl.evaluation_begins();
-      const bool tracked = lpol && sl.prev_na == na;
-      decompose();
-      {
+      decompose_eval([&] {
         TIMED("prepare_sites");
-        const int* lists[2] = {sl.home, sl.imp.as<int>()};
-        const int counts[2] = {sl.n_home, sl.n_imp};
+        const int* lists[2] = {sl.home(), sl.imports()};
+        const int counts[2] = {sl.n_home(), sl.n_imp()};
         for (int k = 0; k < 2; ++k)
           launch_prepare_sites<T>(stream, top, ev.pos, ev.Ql, U_first, ev.pol, ev.thole, ev.bx, sites.as<Site<T>>(),
                                   k == 0 ? energies_d.as<double>() + (size_t)(ehalf ^ 1) * E_WORDS : nullptr, ev.g, nullptr,
                                   nullptr, nullptr, pl.table().cls, cls_flags_dev(), rq_p(), U_first != ev.U ? ev.U : nullptr, lists[k],
                                   counts[k]);
-      }
-      other_clean = true;
-      if (tracked) exchange_migrants();
-      if (lpol) exchange_U(0);
+        other_clean = true;
+      });
       ev.active = true;
       cut_pass();
       return ev.n_home;
@@ -782,10 +616,7 @@ struct Engine : EngineBase {
     other_clean = true;
     if (snranks > 1) {
       slab_sites_na = na; slab_sites_ptr = sites.p;        // every row of `sites` is valid from here on
-      const bool tracked = lpol && sl.prev_na == na;       // (decompose() then lists the atoms that changed hands)
-      decompose();
-      if (tracked) exchange_migrants();
-      if (lpol) exchange_U(0);
+      decompose_eval([] {});
     } else {
       ev.n_home = na;
       ev.home = nullptr;
@@ -925,7 +756,7 @@ struct Engine : EngineBase {
   void stage_pair_full(T* grad_p, T* fld_out = nullptr) {
     need_eval();
     if (snranks > 1)   // the closing kernel ADDS frame-adjoint contributions to atoms of other ranks: those rows start at zero
-      launch_rows_scatter<T>(stream, 2, sl.n_imp, 3, sl.imp.as<int>(), nullptr, grad_p);
+      launch_rows_scatter<T>(stream, 2, sl.n_imp(), 3, sl.imports(), nullptr, grad_p);
     pair_full_prologue();
     if (lpol) ++pair_rider_stats[1];
     TIMED("pair_full");
@@ -992,8 +823,8 @@ struct Engine : EngineBase {
     }
     { TIMED("finish");
       launch_finish<T>(stream, top, ev.pos, ev.bx, sites.as<Site<T>>(), ev.pol, ev.U, lpol, (T)kappa, pot.as<T>(), grad_p,
-                       dQl, Ed_cur(), ev.home, ev.n_home, ff, snranks > 1 ? sl.bits.as<int>() : nullptr); }
-    if (snranks > 1 && grad_p) exchange_grad(grad_p);
+                       dQl, Ed_cur(), ev.home, ev.n_home, ff, snranks > 1 ? sl.bits() : nullptr); }
+    if (snranks > 1 && grad_p) sl.return_gradient(grad_p);
   }
   // ---- incremental SCF ------------------------------------------------------------------------------------------
   // The field dE/dU is LINEAR in the induced dipoles and only sites with pol > 0 ever change theirs.  So after the first
@@ -1002,7 +833,7 @@ struct Engine : EngineBase {
   // polarizable sites alone, and adds it to the stored field; phi is kept current by adding the increment's mesh.  For
   // water that is 1/9 of the pairs and 1/3 of the spread / gather work per cycle; the arithmetic is the reference's
   // (admp/pme.py:130-138) regrouped, same dipoles and cycle count to round-off.  On a slab rank the rows are the polarizable
-  // HOME atoms and the dU of the imported atoms arrive by one all-to-all-v per Jacobi step (exchange_U).
+  // HOME atoms and the dU of the imported atoms arrive by one all-to-all-v per Jacobi step (sl.exchange_dipoles).
   enum { E_PARTS_SUM = -1 };   // read_energies: the reciprocal energy is the sum of the E_PARTS partial words
   int* nact_dev() { return reinterpret_cast<int*>(Ed_cur() + E_NACT); }
   DevBuf rq_d;                                      // compact (position, charge) rows: what the pair kernels read of a
@@ -1013,11 +844,11 @@ struct Engine : EngineBase {
   int* cls_flags_dev() { return nact_dev() + 1; }   // the other half of that word: CLS_* of this evaluation (k_prepare_sites)
   int cls_sites_na = -1;                            // `sites` holds an evaluation of this many atoms
   // the polarizable rows of this evaluation: all polarizable atoms (one rank), or the rank's polarizable home atoms
-  const int* act_list() const { return snranks > 1 ? sl.act : act_d.as<int>(); }
+  const int* act_list() const { return snranks > 1 ? sl.act() : act_d.as<int>(); }
   // device-side count for the kernels of the first cycle when the list is fresh (nullptr: the host knows it)
   const int* nact_arg() { return snranks == 1 && act_fresh ? nact_dev() : nullptr; }
-  int nact_rows() const { return snranks > 1 ? sl.n_act : (act_fresh ? top.na : act_n); }      // grid bound of those kernels
-  int nact_known() const { return snranks > 1 ? sl.n_act : act_n; }
+  int nact_rows() const { return snranks > 1 ? sl.n_act() : (act_fresh ? top.na : act_n); }      // grid bound of those kernels
+  int nact_known() const { return snranks > 1 ? sl.n_act() : act_n; }
   void nact_seen() {                                                 // after a read_energies of this evaluation
     if (snranks > 1 || !act_fresh) return;
     int n = 0;
@@ -1080,7 +911,7 @@ struct Engine : EngineBase {
       launch_jacobi_delta<T>(stream, n_act, act_list(), ev.pol, field.as<T>(), ev.U, sites.as<Site<T>>(),
                              isites.as<Site<T>>(), gate, gate_min, relax);
     }
-    if (snranks > 1) exchange_U(1);       // every rank takes part, whatever its own count
+    if (snranks > 1) sl.exchange_dipoles(1, ev.U, sites.as<Site<T>>());      // every rank takes part, whatever its own count
   }
   // Small systems are dispatch-bound: the SCF residual rides in the epilogue of the field gather that precedes a check
   // (field_epilogue(word) describes it; the check's own kernel is then skipped).  word: a zero word of the energy block.
@@ -1183,16 +1014,18 @@ struct Engine : EngineBase {
     return full_rides;
   }
 
+  // (real, recip[slot], self, penalty) of the energy block Ed, packed at Ed + E_RED and summed over the ranks
+  void sum_energy_words(double* Ed, int recip_slot) {
+    TIMED("comm_energies");
+    launch_energy_pack(stream, Ed, recip_slot, Ed + E_RED);
+    comm.all_reduce(stream, Ed + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
+  }
   // one device->host copy + sync: energies (and the max|field| word, returned).  On a slab rank the four parts are first
   // summed over the ranks (want_sum; the SCF checks only need the residual word, which is already the global maximum).
   double read_energies(int recip_slot, double* E, bool want_sum = true) {
     if (!Eh) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&Eh), E_WORDS * sizeof(double), hipHostMallocDefault));
     const bool summed = snranks > 1 && want_sum;
-    if (summed) {
-      TIMED("comm_energies");
-      launch_energy_pack(stream, Ed_cur(), recip_slot, Ed_cur() + E_RED);
-      comm.all_reduce(stream, Ed_cur() + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
-    }
+    if (summed) sum_energy_words(Ed_cur(), recip_slot);
     HIP_TRY(hipMemcpyAsync(Eh, Ed_cur(), E_WORDS * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     {
@@ -1859,11 +1692,7 @@ struct Engine : EngineBase {
   // energies of a dispersion / pair-potential call: (real, recip, self) of all ranks
   void read_scalar_energies(double* Ed, double* E, int n, bool types_checked = false) {
     double Eh2[E_WORDS];
-    if (snranks > 1) {
-      TIMED("comm_energies");
-      launch_energy_pack(stream, Ed, E_RECIP, Ed + E_RED);
-      comm.all_reduce(stream, Ed + E_RED, 4, ADMP_T_F64, ADMP_OP_SUM, ADMP_TAG_ENERGIES);
-    }
+    if (snranks > 1) sum_energy_words(Ed, E_RECIP);
     HIP_TRY(hipMemcpyAsync(Eh2, Ed, sizeof(Eh2), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const double* src = snranks > 1 ? Eh2 + E_RED : Eh2;      // (E_REAL, E_RECIP, E_SELF are words 0, 1, 2 either way)
@@ -1883,9 +1712,8 @@ struct Engine : EngineBase {
       launch_atom_bases<T>(stream, na, pos, g, bases_d.as<int4>());
     }
     if (snranks == 1) return {order, na, nullptr};
-    ev.bases = bases_d.as<int4>(); ev.pol = nullptr; ev.U = nullptr;
-    decompose(K0v, X0v, X1v, order);
-    return {sl.rows, sl.n_home, sl.home};
+    sl.decompose(slab_in(bases_d.as<int4>(), nullptr, K0v, X0v, X1v, order, false));
+    return {sl.rows(), sl.n_home(), sl.home()};
   }
   // ... of a pair potential on a slab rank: it has no mesh, so ownership goes by x-slabs of a virtual one of 64 planes per rank
   ScalarRows virtual_slab_rows(const T* pos, const double* inv) {

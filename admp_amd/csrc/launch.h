@@ -15,6 +15,7 @@
 #include "pfa_maps.h"
 #include "pme_math.h"
 #include "scf_aspc.h"
+#include "slab_plan.h"
 #include "spline_math.h"
 
 namespace admp {
@@ -615,35 +616,7 @@ int cell_build_table(hipStream_t st, const Topology& top, const T* pos, const Bo
                      double rc, CellScratch& cs, NbrTable& nb, const RowFilter& rf = RowFilter());
 
 // ---- slab_kernels.hip: x-slab decomposition (multi-GPU) ------------------------------------------------------------------
-// per-atom word of a rank's view of the decomposition (see slab_kernels.hip)
-constexpr int kSlabHome = 1 << 30, kSlabPolar = 1 << 29;
-constexpr int kSlabMaxRanks = 28, kSlabMaxCols = 3 + 4 * kSlabMaxRanks;
-// columns of the ordered compaction: column c keeps x = seq[c][p] (seq[c] == nullptr: x = p), p < len[c], where
-// (bits[x] & mask[c]) == want[c]
-struct SlabCols {
-  int ncols = 0;
-  int len[kSlabMaxCols];
-  const int* seq[kSlabMaxCols];
-  const int* src[kSlabMaxCols];    // the flag words this column tests (nullptr: the `bits` array of the decomposition)
-  int mask[kSlabMaxCols];
-  int want[kSlabMaxCols];
-  int binned[kSlabMaxCols];        // 1: the column is filled by the one-pass bin compaction (SlabBins), not by its own pass
-};
-// The per-peer columns of a decomposition -- imports from / exports to / atoms taken over from / given away to every rank --
-// plus the home and polarizable-home columns, as BINS of one ordered compaction pass over the atoms (round 3 ran one pass over
-// all atoms per column: 7 passes on 2 ranks, 31 on 8 -- the part of a rank's step that GREW with the rank count).  c_*: the
-// column (index into SlabCols / totals / lists) a bin writes, -1 = absent.
-struct SlabBins {
-  int N = 0, me = 0;
-  int c_home = -1, c_act = -1;
-  int c_imp[kSlabMaxRanks], c_exp[kSlabMaxRanks], c_min[kSlabMaxRanks], c_mout[kSlabMaxRanks];
-};
-// segments of a joined per-peer list: segment s = column col[s] of the compaction, entries off[s] .. off[s+1]-1 of the result
-struct SlabSegs {
-  int n = 0;
-  int off[kSlabMaxRanks + 1];
-  int col[kSlabMaxRanks];
-};
+// (the plain constants and records of the decomposition -- kSlabHome, SlabCols, SlabBins, SlabSegs -- are slab_plan.h's)
 // owner[na] / bits[na] of this evaluation and the compacted columns lists[c * na ..]; totals[ncols] stay on the device
 // (the caller reads them once).  counts: ncols * slab_compact_blocks(max len) ints of scratch.  hipError_t as int.
 // owner_prev (optional): the owners of the previous evaluation; mig[na] then receives, for the atoms that changed hands,

@@ -1,4 +1,4 @@
-"""The decomposition of a slab rank (admp_amd/csrc/slab_kernels.hip, Engine::decompose) restated in plain numpy, float64, from
+"""The decomposition of a slab rank (admp_amd/csrc/slab_kernels.hip, SlabDecomp::decompose) restated in plain numpy, float64, from
 the RULE and not from the kernels, and the systems the list tests run on (tests/test_slab_ref_cpu.py checks this module on
 the CPU, tests/test_gpu_slab_lists.py compares the device's arrays with it word by word).
 

@@ -1,5 +1,5 @@
 """The decomposition of the slab ranks, word by word: owner and bits of every atom, the home / rows / act lists, the per-peer
-import and export lists and the migrant lists of Engine::decompose (k_slab_owner, k_slab_marks, k_slab_bins, k_compact_*,
+import and export lists and the migrant lists of SlabDecomp::decompose (k_slab_owner, k_slab_marks, k_slab_bins, k_compact_*,
 k_slab_concat; read back by admp_slab_lists) against the plain float64 restatement of the rule in tests/slab_ref.py.
 
 Why: this is integer work whose outputs nothing looked at -- only admp_slab_home exposes the home list and the import count.
@@ -28,6 +28,11 @@ Measured on an MI355X: 0 differences in 764 460 words per child setting, 0 atoms
 about 5.5 s are the child's start, its transform plans and a handle's first evaluation.  Detection:
 k_slab_marks without its inverse-frame loop fails the general-frame cases alone, k_slab_bins ranking by the higher lanes of a
 bin fails every `bins` test and no `columns` test; the existing slab tests pass under both.
+
+A new topology forgets the previous owners (test_a_new_topology_forgets_the_previous_owners): 192 atoms on 2 ranks, double
+precision, an evaluation at pos, one 5.5 planes further (tracked, 8 migrants each way), admp_set_topology again with the same
+arrays, an evaluation at pos -- not tracked, no migrants, every list that of pos.  5.7 s on the MI355X.  Against the library of
+the commit before SlabDecomp::forget the third evaluation came back tracked with 8 + 8 migrants (observed).
 """
 import ctypes
 import hashlib
@@ -233,5 +238,100 @@ def test_slab_lists_refuses_handles_without_a_decomposition():
     L.admp_destroy(h)
 
 
+def retopology_case():
+    """the smallest polarizable water box of slab_ref (192 atoms, 2 ranks) with a second configuration 5.5 planes along x: 8 atoms
+    change hands in each direction"""
+    if 'retopology_n2' not in R._BUILT:
+        R._BUILT['retopology_n2'] = R.water_case('retopology_n2', 64, 59, 2, shift_planes=5.5)
+    return R._BUILT['retopology_n2']
+
+
+def child_retopology(outdir):
+    """pos, pos2, then admp_set_topology again with the same arrays, then pos: the lists after each evaluation"""
+    import torch                             # before the library, as everywhere else
+    torch.cuda.init()
+    from admp_amd import _lib, settings
+    from admp_amd._device import covalent_to_csr
+    from admp_amd.parallel import SlabPme, ThreadComm
+    settings.REFERENCE_KPOINT_ORDER = False
+    settings.MAX_N_POL = 2
+    settings.PRECISION = 'double'
+    c = retopology_case()
+    N, na, par = c['N'], c['na'], c['par']
+    world = ThreadComm.World(N)
+    errors = []
+
+    def work(rank):
+        try:
+            torch.cuda.set_device(0)
+            f = SlabPme(ThreadComm(world, rank), c['box'], c['at'], c['ai'], c['cov'], c['rc'], 1e-4, 2, lpol=True, outputs='home')
+            f.K1 = c['K0']
+            f.refresh_calculators()
+            for e, pos in enumerate((c['pos'], c['pos2'], c['pos'])):
+                if e == 2:
+                    at = np.ascontiguousarray(c['at'], dtype=np.int32)
+                    ai = np.ascontiguousarray(c['ai'], dtype=np.int32)
+                    csr = covalent_to_csr(c['cov'], na)
+                    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+                    _lib.check(f._h, f._L.admp_set_topology(f._h, na, p(at), p(ai), p(csr[0]), p(csr[1]), p(csr[2])),
+                               'admp_set_topology')
+                    f._pairs_key = None              # the handle dropped its table with the topology
+                f.get_forces(pos, c['box'], c['pairs'], par['Q_local'], par['pol'], par['tholes'], par['mScales'], par['pScales'],
+                             par['dScales'])
+                a = read_lists(f, na, N)
+                a['slab_home'] = np.array([f.n_home, f.n_import], dtype=np.int64)
+                a['home_atoms'] = f.home_atoms.cpu().numpy().astype(np.int64)
+                np.savez(os.path.join(outdir, 'retopology.r%d.e%d.npz' % (rank, e)), **a)
+        except BaseException as ex:      # noqa: BLE001
+            errors.append((rank, repr(ex)))
+            try:
+                world.barrier.abort()
+            except Exception:      # noqa: BLE001
+                pass
+
+    threads = [threading.Thread(target=work, args=(r,), daemon=True) for r in range(N)]
+    for t in threads:
+        t.start()
+    deadline = time.time() + 120
+    for t in threads:
+        t.join(timeout=max(1.0, deadline - time.time()))
+    alive = [r for r, t in enumerate(threads) if t.is_alive()]
+    if errors or alive:
+        print('LISTS-CHILD-FAILED errors=%r alive=%r' % (errors, alive))
+        sys.stdout.flush()
+        os._exit(3)
+    print('LISTS-CHILD-OK retopology')
+
+
+@pytest.mark.gpu
+def test_a_new_topology_forgets_the_previous_owners(tmp_path):
+    """admp_set_topology between two evaluations of the same atom count: the next decomposition is a first one -- not tracked,
+    no migrants -- and its lists are those of its positions.  (Before SlabDecomp::forget the owners of the system that is gone
+    stayed on record: counts[4] came back 1 and the dipoles of the "migrants" were shipped between the ranks.)"""
+    t0 = time.time()
+    clean = {k: v for k, v in os.environ.items() if not k.startswith('ADMP_') or k == 'ADMP_HIP_LIB'}
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), 'retopology', str(tmp_path)], capture_output=True, text=True,
+                       env=clean, timeout=600, cwd=ROOT)
+    assert r.returncode == 0 and 'LISTS-CHILD-OK' in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    c = retopology_case()
+    N, par = c['N'], c['par']
+    assert (c['na'], N, c['lpol']) == (192, 2, True)
+    table, axes = R.pair_table(c['pairs'], c['na']), R.axis_atoms(c['at'], c['ai'])
+    own, own2 = R.owners(c['pos'], c['box'], c['K0'], N), R.owners(c['pos2'], c['box'], c['K0'], N)
+    ranks, ranks2 = (R.decomposition(o, table, axes, par['pol'], True, N) for o in (own, own2))
+    mig = [R.migrants(own, own2, rk, N) for rk in range(N)]
+    assert all(sum(map(len, m[0])) == 8 and sum(map(len, m[1])) == 8 for m in mig)      # atoms change hands in both directions
+    for e, (owner, want, tracked) in enumerate(((own, ranks, False), (own2, ranks2, True), (own, ranks, False))):
+        for rk in range(N):
+            a = dict(np.load(tmp_path / ('retopology.r%d.e%d.npz' % (rk, e))))
+            print('evaluation %d rank %d counts[:8] = %s' % (e, rk, a['counts'][:8].tolist()))
+            assert int(a['counts'][4]) == (1 if tracked else 0), ('evaluation', e, 'rank', rk, 'tracked', a['counts'][:8])
+            check_rank('retopology rank %d evaluation %d' % (rk, e), a, want[rk], owner, N, rk, True, tracked,
+                       mig[rk] if tracked else None)
+    print('wall time retopology: %.1f s' % (time.time() - t0))
+
+
 if __name__ == '__main__' and len(sys.argv) == 4 and sys.argv[1] == 'child':
     child_main(sys.argv[2], sys.argv[3])
+if __name__ == '__main__' and len(sys.argv) == 3 and sys.argv[1] == 'retopology':
+    child_retopology(sys.argv[2])
