@@ -94,6 +94,8 @@ PROTOTYPES = {
     'admp_pair_rider_stats': (_i32, [_vp, _c.POINTER(_i64), _i32]),
     'admp_mesh_spread': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _ip]),
     'admp_mesh_gather': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _dp, _vp, _vp, _vp, _ip]),
+    'admp_disp_mesh_spread': (_i32, [_vp, _vp, _dp, _vp, _i32, _i32, _vp, _dp, _ip]),
+    'admp_disp_mesh_gather': (_i32, [_vp, _vp, _dp, _vp, _i32, _vp, _i32, _i32, _dp, _vp, _ip]),
     'admp_site_table': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _ip]),
     'admp_site_close': (_i32, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _dp, _vp, _vp, _dp, _ip]),
     'admp_set_comm': (_i32, [_vp, _vp]),
@@ -143,6 +145,9 @@ MESH_PATHS = ('rocfft', 'fused_x', 'direct_lines', 'direct_planes', 'two_level')
 
 # admp_mesh_spread: values of info[0]
 SPREAD_FORMS = ('scan', 'planes', 'bricks', 'plane_kernel')
+
+# admp_disp_mesh_spread / admp_disp_mesh_gather: values of info[0] (DispPath of csrc/disp_plan.h)
+DISP_PATHS = ('BricksTyped', 'BricksBatched', 'BricksPerPower', 'DftTyped', 'DftBatched', 'PerPower')
 
 # admp_site_close: values of info[0]
 FINISH_FORMS = ('pull4', 'pull1', 'groups', 'rows', 'gather_epilogue', 'list')

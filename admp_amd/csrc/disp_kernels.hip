@@ -11,6 +11,7 @@
 // (round 2 ran spread / gather_field / scale_add once per channel over 80-byte site rows: 0.65 + 0.39 + 0.21 ms of the
 // 2.5 ms dispersion call at 1M atoms).  The meshes themselves still take one transform pair each.
 #include "launch.h"
+#include "disp_math.h"
 #include "reduce.h"
 
 namespace admp {
@@ -90,18 +91,7 @@ __global__ __launch_bounds__(256) void k_spread_bricks_scalar(const T* __restric
   double inv_scale[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const double bmax = (double)__uint_as_float(s_bmax[c]), bound = 0.17 * bmax * (double)(cnt > 0 ? cnt : 1);
-    int ex = 20;
-    if (bmax > 0.0) {
-      if (sizeof(T) == 4) {
-        ex = 29 - ilogb(bound);                            // 2^ex bound < 2^30: no 32-bit word can overflow
-      } else {
-        ex = 61 - ilogb(bound);                            // 2^ex bound < 2^62 ...
-        const int e1 = 49 - ilogb(bmax);                   // ... and every term below 2^50 (mantissa trick of scalar_fixed)
-        ex = ex < e1 ? ex : e1;
-        ex = ex > 60 ? 60 : ex;
-      }
-    }
+    const int ex = scalar_spread_exponent(sizeof(T) == 4, (double)__uint_as_float(s_bmax[c]), cnt);      // (disp_math.h)
     scale[c] = (T)ldexp(1.0, ex);
     inv_scale[c] = ldexp(1.0, -ex);
   }
@@ -206,11 +196,7 @@ __global__ __launch_bounds__(256) void k_spread_bricks_typed(const T* __restrict
   __syncthreads();
   const int beg = brick_start[blockIdx.x], cnt = brick_start[blockIdx.x + 1] - beg;
   // unit sources: a word receives at most cnt * 0.17 (the largest product of three order-6 spline values)
-  int ex;
-  {
-    const double bound = 0.17 * (double)(cnt > 0 ? cnt : 1);
-    ex = sizeof(T) == 4 ? 29 - ilogb(bound) : 49;
-  }
+  const int ex = typed_spread_exponent(sizeof(T) == 4, cnt);      // (disp_math.h)
   const T scale = (T)ldexp(1.0, ex);
   const double inv_scale = ldexp(1.0, -ex);
   const int rows = (cnt + 63) >> 6, lane = threadIdx.x & 63;
@@ -328,12 +314,14 @@ template <class T>
 void launch_onehot(hipStream_t st, int na, int nt, const int* types, T* w) {
   if (na > 0) k_onehot<T><<<(na + 255) / 256, 256, 0, st>>>(na, nt, types, w);
 }
+int disp_spread_groups(const int dims[3]) { return make_bricks(dims).ncell; }      // one workgroup per brick
 // nt = 1..3 type meshes (single precision: three 17 KB tiles per workgroup)
 template <class T>
 int launch_spread_typed(hipStream_t st, int nt, const T* pos, const int* types, const RecipGeom<T>& g, const BinScratch& bs,
                         T* mesh, long mesh_stride) {
   const int dims[3] = {g.nloc0, g.K[1], g.K[2]};
-  const BrickGrid bg = make_bricks(dims);
+  BrickGrid bg = make_bricks(dims);
+  bg.ncell = disp_spread_groups(dims);
   using W = typename ScalarWord<T>::type;
   const size_t sh = (size_t)nt * kScalarTile * sizeof(W);
   if (sh > 64 * 1024 || nt < 1 || nt > 3) return (int)hipErrorInvalidValue;
@@ -350,7 +338,8 @@ template <class T>
 int launch_spread_scalar(hipStream_t st, int nch, const T* pos, const T* vals, int stride, const RecipGeom<T>& g,
                          const BinScratch& bs, T* mesh, long mesh_stride) {
   const int dims[3] = {g.nloc0, g.K[1], g.K[2]};
-  const BrickGrid bg = make_bricks(dims);
+  BrickGrid bg = make_bricks(dims);
+  bg.ncell = disp_spread_groups(dims);
   using W = typename ScalarWord<T>::type;
   if (sizeof(T) == 4 && nch == 3) {
     k_spread_bricks_scalar<T, 3><<<bg.ncell, 256, 3 * kScalarTile * sizeof(W), st>>>(pos, vals, stride, 0, g, bg, bs.cell_start,
@@ -371,6 +360,8 @@ int launch_spread_scalar(hipStream_t st, int nch, const T* pos, const T* vals, i
 // The staged form of recip_kernels.hip (32 atoms per workgroup of 192 threads: wave d evaluates the dimension-d spline of the
 // 32 atoms once into LDS, six lanes per atom sum their z-index over the 36 (x, y) points) over NCH meshes at once.
 constexpr int kSgAtoms = 32, kSgBlock = 6 * kSgAtoms, kSgRow = 19;
+unsigned disp_gather_groups(int na) { return xcd_grid((unsigned)((na + kSgAtoms - 1) / kSgAtoms)); }
+int disp_value_groups(int na) { return (na + 127) / 128; }
 
 template <class T, int NCH> struct ChanVec { T v[NCH]; };
 
@@ -494,7 +485,7 @@ template <class T>
 void launch_gather_scalar(hipStream_t st, int nch, int na, const T* pos, const T* vals, int stride, const RecipGeom<T>& g,
                           const T* phi, long mesh_stride, T* grad, const int* list, int interleaved, const int* types) {
   if (na <= 0) return;
-  const unsigned grid = xcd_grid((unsigned)((na + kSgAtoms - 1) / kSgAtoms));
+  const unsigned grid = disp_gather_groups(na);
   if (types) {      // one mesh per atom, chosen by its type
     k_gather_scalar<T, 1, false><<<grid, kSgBlock, 0, st>>>(na, pos, vals, stride, g, phi, mesh_stride, grad, list, types);
     return;
@@ -555,7 +546,7 @@ __global__ __launch_bounds__(128) void k_gather_value(int na, const T* __restric
 template <class T>
 void launch_gather_value(hipStream_t st, int na, const T* pos, const T* vals, int stride, int chan, const RecipGeom<T>& g,
                          const T* phi, double extra, T* out, const int* list) {
-  if (na > 0) k_gather_value<T><<<(na + 127) / 128, 128, 0, st>>>(na, pos, vals, stride, chan, g, phi, (T)extra, out, list);
+  if (na > 0) k_gather_value<T><<<disp_value_groups(na), 128, 0, st>>>(na, pos, vals, stride, chan, g, phi, (T)extra, out, list);
 }
 
 #define INST(T)                                                                                                          \

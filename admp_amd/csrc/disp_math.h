@@ -123,6 +123,33 @@ ADMP_HD void tt_pair_dparams(const Box<T>& box, const T ri[3], const T rj[3], co
   out[3] += m * fc.v * pj[3];
 }
 
+// Fixed-point exponents of the brick spreads of disp_kernels.hip: a tile word holds 2^ex times its mesh word.  A mesh word
+// receives at most ONE term per entry of the brick's list and a term is c M(x) M(y) M(z) with M <= 0.55, so
+// |word| <= 0.17 cnt max|c|.  bmax: the float maximum of |c| over the brick's entries times 1.0001, 0 for a brick (or a
+// channel of it) without a coefficient.  f32 tiles: 32-bit words, 2^ex bound < 2^30.  f64 tiles: 64-bit words, 2^ex bound
+// < 2^62, and every term below 2^50 (the mantissa trick of scalar_fixed).  tests/hostshim/disp_scale_shim.cpp compiles these
+// for the host and tests/test_disp_scale_cpu.py walks them over cnt and bmax.
+ADMP_HD int scalar_spread_exponent(bool single, double bmax, int cnt) {
+  const double bound = 0.17 * bmax * (double)(cnt > 0 ? cnt : 1);
+  int ex = 20;
+  if (bmax > 0.0) {
+    if (single) {
+      ex = 29 - ilogb(bound);                            // 2^ex bound < 2^30: no 32-bit word can overflow
+    } else {
+      ex = 61 - ilogb(bound);                            // 2^ex bound < 2^62 ...
+      const int e1 = 49 - ilogb(bmax);                   // ... and every term below 2^50 (mantissa trick of scalar_fixed)
+      ex = ex < e1 ? ex : e1;
+      ex = ex > 60 ? 60 : ex;
+    }
+  }
+  return ex;
+}
+// ... of the typed form: unit sources, a word receives at most 0.17 cnt
+ADMP_HD int typed_spread_exponent(bool single, int cnt) {
+  const double bound = 0.17 * (double)(cnt > 0 ? cnt : 1);
+  return single ? 29 - ilogb(bound) : 49;
+}
+
 // k-space dispersion kernels Ck_6/8/10 (recip.py:437-462); which = 6, 8, 10.
 ADMP_HD double disp_ck(int which, double ksq, double kappa, double V) {
   const double sqrt_pi = 1.7724538509055159, pi = 3.141592653589793;

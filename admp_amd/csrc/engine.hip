@@ -170,6 +170,10 @@ struct EngineBase : HandleCtx {      // device, prec, stream, own_stream, prof, 
                     void* dpos, int on_device) = 0;
   virtual void tt(const void* pos, const double* box, const void* abqc, int ns, const double* mS, double* E, void* dpos,
                   int on_device) = 0;
+  virtual void disp_mesh_spread(const void* pos, const double* box, const void* clist, int pmax, int on_device, void* mesh_out,
+                                double* E_self_out, int32_t* info8) = 0;
+  virtual void disp_mesh_gather(const void* pos, const double* box, const void* clist, int pmax, const void* phi, int which,
+                                int on_device, double* E_self_out, void* out, int32_t* info8) = 0;
   virtual void disp_param_grad(const void* pos, const double* box, const void* clist, int pmax, int ns, const double* mS,
                                void* out) = 0;
   virtual void tt_param_grad(const void* pos, const double* box, const void* abqc, int ns, const double* mS, void* out) = 0;
@@ -1820,7 +1824,10 @@ struct Engine : EngineBase {
     }
     double e = 0.0;
     for (int p = 0; p < nch; ++p)
-      for (int t = 0; t < disp_nt; ++t) e += kp[p] * disp_counts[t] * disp_ctab[t][p] * disp_ctab[t][p];
+      for (int t = 0; t < disp_nt; ++t) {      // (the coefficient as the atoms carry it: rounded to the handle's type)
+        const double c = (double)(T)disp_ctab[t][p];
+        e += kp[p] * disp_counts[t] * c * c;
+      }
     return e;
   }
   double disp_ctab[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
@@ -1837,22 +1844,67 @@ struct Engine : EngineBase {
   static bool disp_types_on() { static const bool on = env_flag("ADMP_DISP_TYPES", true); return on; }
   static bool disp_batch_on() { static const bool on = env_flag("ADMP_DISP_BATCH", true); return on; }
   // ---- dispersion PME (admp/disp_pme.py:80-123): real-space pairs + the reciprocal space of every power, by one of the paths
-  // of disp_plan.h.  A path function holds the launches between the pair kernel and the energy read of its path.
+  // of disp_plan.h.  Every path is three legs -- spread, convolve, gather -- with one part function per path and leg;
+  // disp_legs is the one place that holds their order, for Engine::disp (all legs) and for the test entries
+  // admp_disp_mesh_spread / admp_disp_mesh_gather (one leg, around meshes of the caller's).
+  enum { LEG_SPREAD = 1, LEG_CONVOLVE = 2, LEG_GATHER = 4, LEG_ALL = 7 };
+  struct DispRun {
+    DispPath path = DispPath::PerPower;
+    int nch = 1, nmesh = 1, legs = LEG_ALL;
+    bool bricks = false, typed = false;
+    // the entries' meshes (nmesh x K1 K2 K3 words): written after the spread, read before the gather
+    T* mesh_out = nullptr;
+    const T* phi_in = nullptr;
+    hipMemcpyKind copy = hipMemcpyDeviceToDevice;
+  };
+  DispRun disp_choose(int pmax, const RecipGeom<T>& g) {
+    DispRun run;
+    run.nch = (pmax - 4) / 2;
+    DispPathIn in;
+    in.snranks = snranks; in.use_dft = mc.direct(); in.use_pfa = mc.path() == MeshPath::TwoLevel; in.use_fx = mc.fused_x();
+    in.bricks = spread_uses_bricks(top.na, g);
+    in.single_precision = sizeof(T) == 4;
+    in.nch = run.nch; in.disp_nt = disp_nt; in.have_types = disp_types != nullptr;
+    in.types_on = disp_types_on(); in.batch_on = disp_batch_on();
+    run.path = disp_path(in);
+    run.bricks = run.path == DispPath::BricksTyped || run.path == DispPath::BricksBatched || run.path == DispPath::BricksPerPower;
+    run.typed = run.path == DispPath::BricksTyped || run.path == DispPath::DftTyped;
+    run.nmesh = run.typed ? disp_nt : run.nch;
+    return run;
+  }
+  size_t disp_nreal() const { return (size_t)K[0] * K[1] * K[2]; }
+  void disp_mesh_out(const DispRun& run, int first, int n) {
+    if (run.mesh_out)
+      HIP_TRY(hipMemcpyAsync(run.mesh_out + first * disp_nreal(), mesh.as<T>() + (run.path == DispPath::PerPower ? 0 : first * disp_nreal()),
+                             n * disp_nreal() * sizeof(T), run.copy, stream));
+  }
+  void disp_phi_in(const DispRun& run, int first, int n) {
+    if (run.phi_in)
+      HIP_TRY(hipMemcpyAsync(mesh.as<T>() + (run.path == DispPath::PerPower ? 0 : first * disp_nreal()), run.phi_in + first * disp_nreal(),
+                             n * disp_nreal() * sizeof(T), run.copy, stream));
+  }
   // Brick regime, typed meshes (disp_kernels.hip): nt type meshes through the batched y-z plans, combined per k in the x pass,
   // ONE gather per atom
-  void disp_bricks_typed(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
+  void disp_types_check(const ScalarCall& sc, int nch) {
+    launch_types_check<T>(stream, top.na, sc.par, 3, disp_types, disp_mix(nch), sc.Ed + E_FMAX);
+  }
+  void disp_bricks_typed_spread(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
     const int nt = disp_nt;
-    const size_t nreal = nreal_local(), nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
     ensure_bins(std::max(sr.n, 1));
-    const MixTab mix = disp_mix(nch);
-    launch_types_check<T>(stream, top.na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
-    mesh.need((size_t)std::max(nt, nch) * nreal * sizeof(T));
-    mc.need_spectrum((size_t)nt * nspec * sizeof(T));
+    disp_types_check(sc, nch);
+    mesh.need((size_t)std::max(nt, nch) * nreal_local() * sizeof(T));
     { TIMED("spread"); spread_bricks(sr, g, nt, sc.pos, nullptr, disp_types); }
+  }
+  void disp_bricks_typed_convolve(const ScalarCall& sc, int nch) {
+    const int nt = disp_nt;
+    const size_t nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
+    mc.need_spectrum((size_t)nt * nspec * sizeof(T));
     const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
-    mc.convolve_mix(mesh.as<T>(), tabs, mix, nt, nspec, sc.Ed, E_RECIP);
-    { TIMED("gather_field");
-      launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par, 3, g, mesh.as<T>(), (long)nreal, sc.dpos, sr.home, 0, disp_types); }
+    mc.convolve_mix(mesh.as<T>(), tabs, disp_mix(nch), nt, nspec, sc.Ed, E_RECIP);
+  }
+  void disp_bricks_typed_gather(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr) {
+    TIMED("gather_field");
+    launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par, 3, g, mesh.as<T>(), (long)nreal_local(), sc.dpos, sr.home, 0, disp_types);
   }
   // Brick regime (at scale, and every slab rank): ONE binning and ONE spread of the nch meshes straight from the caller's
   // arrays, no site rows and no scale-add pass.  batched (one rank on a fused-x mesh, round 4): the meshes go through ONE
@@ -1862,28 +1914,36 @@ struct Engine : EngineBase {
   // its transform: that gather is bound by the cache-line rate of its 36 mesh loads per lane, whatever it sums (0.175 ms per
   // power at 1M atoms in every form tried: one pass over the three meshes 0.52-0.61 ms; one pass per power from its own or
   // from a shared, cache-resident phi buffer 0.525; round 2's k_gather_field_staged on site rows 0.525).
-  void disp_bricks(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch, bool batched) {
-    const size_t nreal = nreal_local();
-    mesh.need(nch * nreal * sizeof(T));
+  void disp_bricks_spread(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
+    mesh.need(nch * nreal_local() * sizeof(T));
     ensure_bins(std::max(sr.n, 1));
     { TIMED("spread"); spread_bricks(sr, g, nch, sc.pos, sc.par, nullptr); }
-    if (batched) {
-      const size_t nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
-      mc.need_spectrum(nch * nspec * sizeof(T));
-      mesh2.need(nch * nreal * sizeof(T));
-      const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
-      mc.convolve_batch(mesh.as<T>(), tabs, nch, nspec, Ed_cur(), E_RECIP);
-      { TIMED("interleave"); launch_interleave<T>(stream, nch, (long)nreal, mesh.as<T>(), (long)nreal, mesh2.as<T>()); }
-      { TIMED("gather_field");
-        launch_gather_scalar<T>(stream, nch, sr.n, sc.pos, sc.par, 3, g, mesh2.as<T>(), (long)nreal, sc.dpos, sr.home, 1); }
-    } else
-    for (int c = 0; c < nch; ++c) {
-      ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
-      mc.convolve(mesh.as<T>() + c * nreal, mc.gtab_cur, Ed_cur(), E_RECIP);
-      TIMED("gather_field");
-      launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par + c, 3, g, mesh.as<T>() + c * nreal, (long)nreal, sc.dpos, sr.home);
-    }
-    { TIMED("scalar_self"); launch_scalar_self<T>(stream, nch, sr.n, sc.par, 3, sr.home, disp_kp().data(), sc.Ed); }
+  }
+  void disp_bricks_batched_convolve(const ScalarCall& sc, int nch) {
+    const size_t nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_pitch();
+    mc.need_spectrum(nch * nspec * sizeof(T));
+    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+    mc.convolve_batch(mesh.as<T>(), tabs, nch, nspec, Ed_cur(), E_RECIP);
+  }
+  void disp_bricks_batched_gather(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int nch) {
+    const size_t nreal = nreal_local();
+    mesh2.need(nch * nreal * sizeof(T));
+    { TIMED("interleave"); launch_interleave<T>(stream, nch, (long)nreal, mesh.as<T>(), (long)nreal, mesh2.as<T>()); }
+    { TIMED("gather_field");
+      launch_gather_scalar<T>(stream, nch, sr.n, sc.pos, sc.par, 3, g, mesh2.as<T>(), (long)nreal, sc.dpos, sr.home, 1); }
+  }
+  void disp_bricks_power_convolve(const ScalarCall& sc, int c) {
+    ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
+    mc.convolve(mesh.as<T>() + c * nreal_local(), mc.gtab_cur, Ed_cur(), E_RECIP);
+  }
+  void disp_bricks_power_gather(const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr, int c) {
+    const size_t nreal = nreal_local();
+    TIMED("gather_field");
+    launch_gather_scalar<T>(stream, 1, sr.n, sc.pos, sc.par + c, 3, g, mesh.as<T>() + c * nreal, (long)nreal, sc.dpos, sr.home);
+  }
+  void disp_bricks_self(const ScalarCall& sc, const ScalarRows& sr, int nch) {
+    TIMED("scalar_self");
+    launch_scalar_self<T>(stream, nch, sr.n, sc.par, 3, sr.home, disp_kp().data(), sc.Ed);
   }
   // The other paths go through the spread / gather kernels of the electrostatics: nb batches of charge-only site rows (which
   // also accumulate the self term, disp_pme.py:254-279), their fields, the bins; returns the geometry of their gather
@@ -1896,74 +1956,152 @@ struct Engine : EngineBase {
     for (int k = 0; k < 9; ++k) gj.Aop[k] = g.Jac[k];
     return gj;
   }
+  // the self factors of the site rows: the self term belongs to the spread leg (a gather alone builds its rows without it)
+  std::array<double, 3> disp_site_kp(const DispRun& run) const {
+    return (run.legs & LEG_SPREAD) ? disp_kp() : std::array<double, 3>{0.0, 0.0, 0.0};
+  }
   // Typed meshes on a direct-DFT mesh (small systems; see admp_disp_set_types): the types take the place of the powers in the
   // batch -- one-hot weights through the same site / spread / gather kernels, the x pass combines (dft_kernels.hip k_dft_x_mix)
-  void disp_dft_typed(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
+  void disp_dft_typed_sites(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
     const int na = top.na, nt = disp_nt;
-    const RecipGeom<T> gj = disp_site_rows(g, nt);
-    const MixTab mix = disp_mix(nch);
-    launch_types_check<T>(stream, na, sc.par, 3, disp_types, mix, sc.Ed + E_FMAX);
-    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * (K[2] / 2 + 1);
-    mesh.need(nt * nreal * sizeof(T));
-    mc.need_spectrum(nt * nspec * sizeof(T));
+    launch_types_check<T>(stream, na, sc.par, 3, disp_types, disp_mix(nch), sc.Ed + E_FMAX);
+    mesh.need(nt * disp_nreal() * sizeof(T));
     onehot_d.need((size_t)na * nt * sizeof(T));
     bases_d.need(sizeof(int4) * (size_t)na);
-    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
     const double no_self[3] = {0.0, 0.0, 0.0};
-    { TIMED("scalar_sites");
-      if (!disp_onehot_ok || onehot_for != onehot_d.p) {
-        launch_onehot<T>(stream, na, nt, disp_types, onehot_d.as<T>());
-        disp_onehot_ok = true; onehot_for = onehot_d.p;
-      }
-      launch_scalar_sites_batch<T>(stream, na, sc.pos, onehot_d.as<T>(), nt, nt, no_self, sites.as<Site<T>>(), sc.Ed, &g,
-                                   bases_d.as<int4>()); }
-    { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), nt); }
-    mc.convolve_dft_batch(mesh.as<T>(), tabs, nt, nreal, nspec, Ed_cur(), E_RECIP, &mix);
+    TIMED("scalar_sites");
+    if (!disp_onehot_ok || onehot_for != onehot_d.p) {
+      launch_onehot<T>(stream, na, nt, disp_types, onehot_d.as<T>());
+      disp_onehot_ok = true; onehot_for = onehot_d.p;
+    }
+    launch_scalar_sites_batch<T>(stream, na, sc.pos, onehot_d.as<T>(), nt, nt, no_self, sites.as<Site<T>>(), sc.Ed, &g,
+                                 bases_d.as<int4>());
+  }
+  void disp_dft_typed_spread(const RecipGeom<T>& g) {
+    TIMED("spread");
+    spread_sites(top.na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), disp_nt);
+  }
+  void disp_dft_typed_convolve(const ScalarCall& sc, int nch) {
+    const int nt = disp_nt;
+    const size_t nspec = 2 * (size_t)K[0] * K[1] * (K[2] / 2 + 1);
+    mc.need_spectrum(nt * nspec * sizeof(T));
+    const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
+    const MixTab mix = disp_mix(nch);
+    mc.convolve_dft_batch(mesh.as<T>(), tabs, nt, disp_nreal(), nspec, Ed_cur(), E_RECIP, &mix);
+  }
+  void disp_dft_typed_gather(const ScalarCall& sc, const RecipGeom<T>& gj) {
+    const int na = top.na, nt = disp_nt;
     { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nt); }
     { TIMED("scale_add"); launch_scale_add<T>(stream, na, onehot_d.as<T>(), nt, 0, fld_recip.as<T>(), sc.dpos, nt); }
   }
   // direct-DFT meshes are small and dispatch bound: the powers are spread into separate meshes and transformed as ONE batch
-  // (5 launches instead of 5 per power), then one gather over the batch of meshes
-  void disp_dft_batched(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
-    const int na = top.na;
-    const std::array<double, 3> kp = disp_kp();
-    const RecipGeom<T> gj = disp_site_rows(g, nch);
-    const size_t nreal = (size_t)K[0] * K[1] * K[2], nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_columns();
-    mesh.need(nch * nreal * sizeof(T));
+  // (5 launches instead of 5 per power), then one gather over the batch of meshes.  The scan-spread regime takes the powers
+  // as a batch: the stencil records ride along, every (brick, power) workgroup of the scan spread reads them instead of
+  // redoing three grid_ref per atom (3072 atoms x 1029 workgroups at 97^3); the brick regime spreads power by power.
+  void disp_dft_batched_sites(const DispRun& run, const ScalarCall& sc, const RecipGeom<T>& g) {
+    bases_d.need(sizeof(int4) * (size_t)top.na);
+    TIMED("scalar_sites");
+    launch_scalar_sites_batch<T>(stream, top.na, sc.pos, sc.par, 3, run.nch, disp_site_kp(run).data(), sites.as<Site<T>>(), sc.Ed, &g,
+                                 bases_d.as<int4>());
+  }
+  void disp_dft_batched_spread(const DispRun& run, const RecipGeom<T>& g) {
+    TIMED("spread");
+    spread_sites(top.na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), run.nch);
+  }
+  void disp_dft_batched_convolve(const ScalarCall& sc, int nch) {
+    const size_t nspec = 2 * (size_t)K[0] * K[1] * mc.spectrum_columns();
     mc.need_spectrum(nch * nspec * sizeof(T));
     const DftTabs<T> tabs = disp_tabs(sc.h, sc.inv, sc.vol, nch);
-    if (!spread_uses_bricks(na, g)) {        // the scan-spread regime takes the powers as a batch
-      // the stencil records ride along: every (brick, power) workgroup of the scan spread reads them instead of
-      // redoing three grid_ref per atom (3072 atoms x 1029 workgroups at 97^3)
-      bases_d.need(sizeof(int4) * (size_t)na);
-      { TIMED("scalar_sites"); launch_scalar_sites_batch<T>(stream, na, sc.pos, sc.par, 3, nch, kp.data(), sites.as<Site<T>>(), sc.Ed,
-                                                            &g, bases_d.as<int4>()); }
-      TIMED("spread");
-      spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), bases_d.as<int4>(), nch);
-    } else {
-      for (int c = 0; c < nch; ++c) {
-        { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, sc.pos, sc.par, 3, c, kp[c], sites.as<Site<T>>(), sc.Ed); }
-        TIMED("spread");
-        spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>() + c * nreal, nullptr, 1, c > 0);
-      }
-    }
-    mc.convolve_dft_batch(mesh.as<T>(), tabs, nch, nreal, nspec, Ed_cur(), E_RECIP);
-    // the site rows hold the positions (only the charge slot differs per power): one gather over the batch of meshes
+    mc.convolve_dft_batch(mesh.as<T>(), tabs, nch, disp_nreal(), nspec, Ed_cur(), E_RECIP);
+  }
+  // the site rows hold the positions (only the charge slot differs per power): one gather over the batch of meshes
+  void disp_dft_batched_gather(const ScalarCall& sc, const RecipGeom<T>& gj, int nch) {
+    const int na = top.na;
     { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr, nch); }
     { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, 0, fld_recip.as<T>(), sc.dpos, nch); }
   }
   // one scalar reciprocal pass per power: the power is packed into site rows, spread, convolved, gathered, scaled
-  void disp_per_power(const ScalarCall& sc, const RecipGeom<T>& g, int nch) {
+  void disp_power_sites(const DispRun& run, const ScalarCall& sc, int c) {
+    TIMED("scalar_sites");
+    launch_scalar_sites<T>(stream, top.na, sc.pos, sc.par, 3, c, disp_site_kp(run)[c], sites.as<Site<T>>(), sc.Ed);
+  }
+  void disp_power_spread(const RecipGeom<T>& g, T* mesh_p, int c) {
+    TIMED("spread");
+    spread_sites(top.na, sites.as<Site<T>>(), 0, g, mesh_p, nullptr, 1, c > 0);
+  }
+  void disp_power_convolve(const ScalarCall& sc, int c) {
+    ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
+    mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), E_RECIP);
+  }
+  void disp_power_gather(const ScalarCall& sc, const RecipGeom<T>& gj, int c) {
     const int na = top.na;
-    const std::array<double, 3> kp = disp_kp();
-    const RecipGeom<T> gj = disp_site_rows(g, 1);
-    for (int c = 0; c < nch; ++c) {
-      ensure_gtab(sc.h, sc.inv, sc.vol, 6 + 2 * c);
-      { TIMED("scalar_sites"); launch_scalar_sites<T>(stream, na, sc.pos, sc.par, 3, c, kp[c], sites.as<Site<T>>(), sc.Ed); }
-      { TIMED("spread"); spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0); }
-      mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), E_RECIP);
-      { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr); }
-      { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, c, fld_recip.as<T>(), sc.dpos); }
+    { TIMED("gather_field"); launch_gather_field<T>(stream, na, sites.as<Site<T>>(), gj, mesh.as<T>(), fld_recip.as<T>(), nullptr); }
+    { TIMED("scale_add"); launch_scale_add<T>(stream, na, sc.par, 3, c, fld_recip.as<T>(), sc.dpos); }
+  }
+  // the legs of run.legs in the order of the path.  The site rows of the site-row paths belong to both outer legs (the gather
+  // reads the positions from them).
+  void disp_legs(const DispRun& run, const ScalarCall& sc, const RecipGeom<T>& g, const ScalarRows& sr) {
+    const int nch = run.nch;
+    const bool S = run.legs & LEG_SPREAD, C = run.legs & LEG_CONVOLVE, G = run.legs & LEG_GATHER;
+    switch (run.path) {
+      case DispPath::BricksTyped:
+        if (S) { disp_bricks_typed_spread(sc, g, sr, nch); disp_mesh_out(run, 0, run.nmesh); }
+        if (C) disp_bricks_typed_convolve(sc, nch);
+        if (G) {
+          // a gather alone: the kernel picks its mesh by the type index, so the table is checked, and refused, before it runs
+          if (!S) { disp_types_check(sc, nch); double E3[3]; read_scalar_energies(sc.Ed, E3, 3, true); }
+          disp_phi_in(run, 0, run.nmesh); disp_bricks_typed_gather(sc, g, sr);
+        }
+        break;
+      case DispPath::BricksBatched:
+        if (S) { disp_bricks_spread(sc, g, sr, nch); disp_mesh_out(run, 0, nch); }
+        if (C) disp_bricks_batched_convolve(sc, nch);
+        if (G) { disp_phi_in(run, 0, nch); disp_bricks_batched_gather(sc, g, sr, nch); disp_bricks_self(sc, sr, nch); }
+        break;
+      case DispPath::BricksPerPower:
+        if (S) { disp_bricks_spread(sc, g, sr, nch); disp_mesh_out(run, 0, nch); }
+        if (G) disp_phi_in(run, 0, nch);
+        for (int c = 0; c < nch; ++c) {
+          if (C) disp_bricks_power_convolve(sc, c);
+          if (G) disp_bricks_power_gather(sc, g, sr, c);
+        }
+        if (G) disp_bricks_self(sc, sr, nch);
+        break;
+      case DispPath::DftTyped: {
+        const RecipGeom<T> gj = disp_site_rows(g, disp_nt);
+        if (S || G) disp_dft_typed_sites(sc, g, nch);
+        if (S) { disp_dft_typed_spread(g); disp_mesh_out(run, 0, run.nmesh); }
+        if (C) disp_dft_typed_convolve(sc, nch);
+        if (G) { disp_phi_in(run, 0, run.nmesh); disp_dft_typed_gather(sc, gj); }
+        break;
+      }
+      case DispPath::DftBatched: {
+        const RecipGeom<T> gj = disp_site_rows(g, nch);
+        mesh.need(nch * disp_nreal() * sizeof(T));
+        if (!spread_uses_bricks(top.na, g)) {
+          if (S || G) disp_dft_batched_sites(run, sc, g);
+          if (S) disp_dft_batched_spread(run, g);
+        } else {
+          for (int c = 0; c < nch; ++c) {      // (the rows of the last power stay: the gather reads their positions)
+            if (S || (G && c == nch - 1)) disp_power_sites(run, sc, c);
+            if (S) disp_power_spread(g, mesh.as<T>() + c * disp_nreal(), c);
+          }
+        }
+        if (S) disp_mesh_out(run, 0, nch);
+        if (C) disp_dft_batched_convolve(sc, nch);
+        if (G) { disp_phi_in(run, 0, nch); disp_dft_batched_gather(sc, gj, nch); }
+        break;
+      }
+      case DispPath::PerPower: {
+        const RecipGeom<T> gj = disp_site_rows(g, 1);
+        for (int c = 0; c < nch; ++c) {
+          if (S || G) disp_power_sites(run, sc, c);
+          if (S) { disp_power_spread(g, mesh.as<T>(), c); disp_mesh_out(run, c, 1); }
+          if (C) disp_power_convolve(sc, c);
+          if (G) { disp_phi_in(run, c, 1); disp_power_gather(sc, gj, c); }
+        }
+        break;
+      }
     }
   }
   void disp(const void* pos_, const double* box, const void* clist_, int pmax, int ns, const double* mS, double* E,
@@ -1976,34 +2114,18 @@ struct Engine : EngineBase {
     HIP_TRY(hipSetDevice(device));
     RecipGeom<T> g;
     const ScalarCall sc = scalar_begin(box, ns, mS, pos_, clist_, 3, dpos_, on_device, E_WORDS, &g);
-    const int nch = (pmax - 4) / 2;
     cls_sites_na = slab_sites_na = -1;   // other rows than an electrostatics evaluation's
-    DispPathIn in;
-    in.snranks = snranks; in.use_dft = mc.direct(); in.use_pfa = mc.path() == MeshPath::TwoLevel; in.use_fx = mc.fused_x();
-    in.bricks = spread_uses_bricks(na, g);
-    in.single_precision = sizeof(T) == 4;
-    in.nch = nch; in.disp_nt = disp_nt; in.have_types = disp_types != nullptr;
-    in.types_on = disp_types_on(); in.batch_on = disp_batch_on();
-    const DispPath path = disp_path(in);
-    const bool bricks = path == DispPath::BricksTyped || path == DispPath::BricksBatched || path == DispPath::BricksPerPower;
-    const bool typed = path == DispPath::BricksTyped || path == DispPath::DftTyped;
+    const DispRun run = disp_choose(pmax, g);
     if (snranks > 1) ARG_CHECK(spread_uses_bricks(1 << 30, g), "slab-decomposed dispersion PME needs at least 17 local mesh planes and K2, K3 >= 17");
-    const ScalarRows sr = scalar_rows(sc.pos, g, K[0], mc.X0, mc.X1, bricks);
+    const ScalarRows sr = scalar_rows(sc.pos, g, K[0], mc.X0, mc.X1, run.bricks);
     { TIMED("disp_pair"); launch_disp_pair<T>(stream, na, pl.table(), pack_srows(sc.pos, sc.par, 3), sc.bx, sc.tab, (T)kappa, pmax, sc.dpos, sc.Ed, sr.rows, sr.n, cutoff); }
-    switch (path) {
-      case DispPath::BricksTyped: disp_bricks_typed(sc, g, sr, nch); break;
-      case DispPath::BricksBatched: disp_bricks(sc, g, sr, nch, true); break;
-      case DispPath::BricksPerPower: disp_bricks(sc, g, sr, nch, false); break;
-      case DispPath::DftTyped: disp_dft_typed(sc, g, nch); break;
-      case DispPath::DftBatched: disp_dft_batched(sc, g, nch); break;
-      case DispPath::PerPower: disp_per_power(sc, g, nch); break;
-    }
+    disp_legs(run, sc, g, sr);
     // the energies: a typed path takes its self term from the type table, and its read refuses a table that does not describe
     // c_list; the brick paths and the typed ones read through the sum over the ranks
-    if (bricks || typed) {
-      const double e_self = typed ? typed_self_energy(na, nch, disp_kp().data()) : 0.0;
-      read_scalar_energies(sc.Ed, E, 3, typed);
-      if (typed) E[2] = e_self;
+    if (run.bricks || run.typed) {
+      const double e_self = run.typed ? typed_self_energy(na, run.nch, disp_kp().data()) : 0.0;
+      read_scalar_energies(sc.Ed, E, 3, run.typed);
+      if (run.typed) E[2] = e_self;
       scalar_return_grad(sc, dpos_, on_device);
     } else {
       double Eh[E_SLOTS];
@@ -2012,6 +2134,96 @@ struct Engine : EngineBase {
       HIP_TRY(hipStreamSynchronize(stream));
       E[0] = Eh[E_REAL]; E[1] = Eh[E_RECIP]; E[2] = Eh[E_SELF];
     }
+  }
+  // admp_disp_mesh_spread / admp_disp_mesh_gather: one leg of a dispersion call alone, on the path the call would take
+  // (tests compare the mesh words and the gradient rows with a float64 reference).  Nothing of the real-space chain runs.
+  struct DispLegCall { ScalarCall sc; RecipGeom<T> g; DispRun run; ScalarRows sr; };
+  DispLegCall disp_leg_begin(const void* pos_, const double* box, const void* clist_, int pmax, int on_device,
+                             int legs) {
+    ARG_CHECK(K[0] >= 6 && K[1] >= 6 && K[2] >= 6, "PME mesh must be at least 6 points per dimension (order-6 splines)");
+    HIP_TRY(hipSetDevice(device));
+    static const double one[1] = {1.0};
+    DispLegCall lc;
+    lc.sc = scalar_begin(box, 1, one, pos_, clist_, 3, nullptr, on_device, E_WORDS, &lc.g);
+    cls_sites_na = slab_sites_na = -1;
+    lc.run = disp_choose(pmax, lc.g);
+    lc.run.legs = legs;
+    lc.run.copy = on_device ? hipMemcpyDeviceToDevice : (legs == LEG_SPREAD ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
+    lc.sr = scalar_rows(lc.sc.pos, lc.g, K[0], mc.X0, mc.X1, lc.run.bricks && legs == LEG_SPREAD);
+    return lc;
+  }
+  void disp_leg_info(const DispLegCall& lc, int32_t* info, int main_groups) {
+    const int dims[3] = {nloc0(), K[1], K[2]};
+    int c[4];
+    spread_launch_choice(top.na, dims, c);
+    info[0] = (int)lc.run.path; info[1] = lc.run.nmesh; info[2] = lc.run.typed ? 1 : 0;
+    for (int d = 0; d < 3; ++d) info[3 + d] = c[1 + d];
+    info[6] = main_groups;
+    info[7] = lc.run.bricks ? -1 : c[0];
+  }
+  void disp_mesh_spread(const void* pos_, const double* box, const void* clist_, int pmax, int on_device, void* mesh_out,
+                        double* E_self_out, int32_t* info) override {
+    if (snranks != 1) throw Err{ADMP_E_ARG, "admp_disp_mesh_spread works on a single rank only (slab-decomposed handle)"};
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(pos_ && box && clist_ && mesh_out && E_self_out && info, "null argument");
+    ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
+    DispLegCall lc = disp_leg_begin(pos_, box, clist_, pmax, on_device, LEG_SPREAD);
+    lc.run.mesh_out = reinterpret_cast<T*>(mesh_out);
+    disp_legs(lc.run, lc.sc, lc.g, lc.sr);
+    double E[3];
+    read_scalar_energies(lc.sc.Ed, E, 3, lc.run.typed);
+    *E_self_out = E[2];
+    // workgroups of the spread: the brick paths' launcher says; the site-row paths go through the electrostatics launcher
+    const int dims[3] = {nloc0(), K[1], K[2]};
+    const int groups = lc.run.bricks ? disp_spread_groups(dims) : -1;
+    disp_leg_info(lc, info, groups);
+  }
+  void disp_mesh_gather(const void* pos_, const double* box, const void* clist_, int pmax, const void* phi_, int which,
+                        int on_device, double* E_self_out, void* out_, int32_t* info) override {
+    if (snranks != 1) throw Err{ADMP_E_ARG, "admp_disp_mesh_gather works on a single rank only (slab-decomposed handle)"};
+    ARG_CHECK(have_top && have_ewald && pl.have(), "topology, ewald parameters and pairs must be set first");
+    ARG_CHECK(pos_ && box && clist_ && phi_ && E_self_out && out_ && info, "null argument");
+    ARG_CHECK(pmax == 6 || pmax == 8 || pmax == 10, "pmax must be 6, 8 or 10");
+    ARG_CHECK(which == 0 || which == 1, "which must be 0 (the gradient gather) or 1 (the value gather of the parameter gradient)");
+    DispLegCall lc = disp_leg_begin(pos_, box, clist_, pmax, on_device, LEG_GATHER);
+    const size_t na = (size_t)top.na, nreal = disp_nreal();
+    const T* phi = reinterpret_cast<const T*>(phi_);
+    s_out.need(3 * na * sizeof(T));
+    T* out = on_device ? reinterpret_cast<T*>(out_) : s_out.as<T>();
+    HIP_TRY(hipMemsetAsync(out, 0, 3 * na * sizeof(T), stream));
+    double E[3] = {0.0, 0.0, 0.0};
+    int groups;
+    if (which == 0) {
+      lc.sc.dpos = out;
+      lc.run.phi_in = phi;
+      mesh.need((size_t)std::max(lc.run.nmesh, lc.run.nch) * nreal * sizeof(T));
+      disp_legs(lc.run, lc.sc, lc.g, lc.sr);
+      const double e_self = lc.run.typed ? typed_self_energy(top.na, lc.run.nch, disp_kp().data()) : 0.0;
+      read_scalar_energies(lc.sc.Ed, E, 3, lc.run.typed);
+      *E_self_out = lc.run.typed ? e_self : E[2];
+      groups = lc.run.bricks ? (int)disp_gather_groups(top.na) : -1;
+    } else {
+      const std::array<double, 3> kp = disp_kp();
+      if (!on_device) {
+        mesh.need((size_t)lc.run.nch * nreal * sizeof(T));
+        HIP_TRY(hipMemcpyAsync(mesh.p, phi_, (size_t)lc.run.nch * nreal * sizeof(T), hipMemcpyHostToDevice, stream));
+        phi = mesh.as<T>();
+      }
+      for (int c = 0; c < lc.run.nch; ++c) disp_pgrad_gather(lc.sc.pos, lc.sc.par, lc.g, phi + c * nreal, c, kp[c], out);
+      HIP_TRY(hipStreamSynchronize(stream));
+      *E_self_out = 0.0;
+      groups = disp_value_groups(top.na);
+    }
+    if (!on_device) {
+      HIP_TRY(hipMemcpyAsync(out_, out, 3 * na * sizeof(T), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    disp_leg_info(lc, info, groups);
+    if (which == 1) info[1] = lc.run.nch, info[2] = 0;
+  }
+  // the mesh part of the parameter gradient of power c: the potential of its mesh at the atoms + the self term's 2 kp c
+  void disp_pgrad_gather(const T* pos, const T* cl, const RecipGeom<T>& g, const T* phi, int c, double kp, T* out) {
+    launch_gather_value<T>(stream, top.na, pos, cl, 3, c, g, phi, 2.0 * kp, out);
   }
 
   void tt(const void* pos_, const double* box, const void* abqc_, int ns, const double* mS, double* E, void* dpos_,
@@ -2079,7 +2291,7 @@ struct Engine : EngineBase {
       launch_scalar_sites<T>(stream, na, pos, cl, 3, c, kp[c], sites.as<Site<T>>(), Ed);
       spread_sites(na, sites.as<Site<T>>(), 0, g, mesh.as<T>(), nullptr, 1, c > 0);
       mc.convolve(mesh.as<T>(), mc.gtab_cur, Ed_cur(), E_RECIP);
-      launch_gather_value<T>(stream, na, pos, cl, 3, c, g, mesh.as<T>(), 2.0 * kp[c], out);
+      disp_pgrad_gather(pos, cl, g, mesh.as<T>(), c, kp[c], out);
     }
     HIP_TRY(hipStreamSynchronize(stream));
   }
@@ -2730,6 +2942,16 @@ int admp_mscale_grad(admp_handle* h, int kind, const void* positions, const doub
   return guarded(h, [&](EngineBase& e) { e.mscale_grad(kind, positions, box, params, pmax, n_scales, dE_dmScales, on_device); });
 }
 
+int admp_disp_mesh_spread(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax, int on_device,
+                          void* mesh_out, double* E_self_out, int32_t* info8) {
+  return guarded(h, [&](EngineBase& e) { e.disp_mesh_spread(positions, box, c_list, pmax, on_device, mesh_out, E_self_out, info8); });
+}
+int admp_disp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax,
+                          const void* phi_in, int which, int on_device, double* E_self_out, void* out, int32_t* info8) {
+  return guarded(h, [&](EngineBase& e) {
+    e.disp_mesh_gather(positions, box, c_list, pmax, phi_in, which, on_device, E_self_out, out, info8);
+  });
+}
 int admp_disp_param_grad(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax, int n_scales,
                          const double* mScales, void* dE_dc) {
   return guarded(h, [&](EngineBase& e) { e.disp_param_grad(positions, box, c_list, pmax, n_scales, mScales, dE_dc); });

@@ -558,6 +558,11 @@ template <class T>
 void launch_scalar_self(hipStream_t st, int nch, int na, const T* vals, int stride, const int* list, const double* self_coefs,
                         double* energies);
 // out[i * stride + chan] += phi(r_i) + extra * vals[i * stride + chan]  (mesh potential at the atoms: dE_recip/dc_i)
+// workgroups the dispersion launchers of disp_kernels.hip use (they call these themselves; the test entries report them):
+// brick spreads of a local mesh, k_gather_scalar over na rows, k_gather_value over na rows
+int disp_spread_groups(const int dims[3]);
+unsigned disp_gather_groups(int na);
+int disp_value_groups(int na);
 template <class T>
 void launch_gather_value(hipStream_t st, int na, const T* pos, const T* vals, int stride, int chan, const RecipGeom<T>& g,
                          const T* phi, double extra, T* out, const int* list = nullptr /* the na atoms (nullptr: 0 .. na-1) */);

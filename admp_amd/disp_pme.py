@@ -156,6 +156,52 @@ class ADMPDispPmeForce(HipForceBase):
             _lib.check(self._h, rc, 'admp_disp_param_grad')
         return self._like(out[:, :(self.pmax - 4) // 2], positions)
 
+    def _leg_info(self, info):
+        v = [int(x) for x in info]
+        return {'path': _lib.DISP_PATHS[v[0]], 'nmesh': v[1], 'per_type': bool(v[2]), 'bricks': tuple(v[3:6]), 'groups': v[6],
+                'form': _lib.SPREAD_FORMS[v[7]] if v[7] >= 0 else None}
+
+    def mesh_spread(self, positions, box, pairs, c_list):
+        """The spread leg of the reciprocal part alone (admp_disp_mesh_spread), on the path an evaluation would take.  Returns
+        (device tensor (nmesh, K1, K2, K3): one mesh per power, or per type on the typed paths; what the leg added to the self
+        word; info dict).  A diagnostic for tests."""
+        with self._on_stream():
+            na = self.n_atoms
+            self.set_pairs(pairs)
+            pos = self._real(positions, (na, 3))
+            c3 = self._packed_c(c_list)
+            out = torch.empty((3, self.K1, self.K2, self.K3), dtype=self._dtype, device=self._device)
+            E = ctypes.c_double(0.0)
+            info = (ctypes.c_int * 8)()
+            rc = self._L.admp_disp_mesh_spread(self._h, self._ptr(pos), _lib.darr(self._host64(box, 9)), self._ptr(c3), self.pmax,
+                                               1, self._ptr(out), ctypes.byref(E), info)
+            _lib.check(self._h, rc, 'admp_disp_mesh_spread')
+        d = self._leg_info(info)
+        return out[:d['nmesh']], E.value, d
+
+    def mesh_gather(self, positions, box, pairs, c_list, phi, which=0):
+        """The gather leg alone on meshes `phi` (nmesh, K1, K2, K3) of the caller's (admp_disp_mesh_gather): which = 0 the
+        path's gather into a zeroed gradient, and its self term where the path forms it after the convolution; which = 1 the
+        value gather of the parameter gradient's mesh part (one mesh per power).  Returns (device tensor (Na, 3), self word,
+        info dict).  A diagnostic for tests."""
+        with self._on_stream():
+            na = self.n_atoms
+            self.set_pairs(pairs)
+            pos = self._real(positions, (na, 3))
+            c3 = self._packed_c(c_list)
+            phi_in = self._real(phi)
+            if phi_in.dim() != 4 or tuple(phi_in.shape[1:]) != (self.K1, self.K2, self.K3) or not 1 <= phi_in.shape[0] <= 3:
+                raise ValueError('phi must be (nmesh <= 3, K1, K2, K3)')
+            phi_t = torch.zeros((3, self.K1, self.K2, self.K3), dtype=self._dtype, device=self._device)      # (never read short)
+            phi_t[:phi_in.shape[0]] = phi_in
+            out = torch.empty((na, 3), dtype=self._dtype, device=self._device)
+            E = ctypes.c_double(0.0)
+            info = (ctypes.c_int * 8)()
+            rc = self._L.admp_disp_mesh_gather(self._h, self._ptr(pos), _lib.darr(self._host64(box, 9)), self._ptr(c3), self.pmax,
+                                               self._ptr(phi_t), int(which), 1, ctypes.byref(E), self._ptr(out), info)
+            _lib.check(self._h, rc, 'admp_disp_mesh_gather')
+        return out, E.value, self._leg_info(info)
+
     def generate_get_energy(self):
         def get_energy(positions, box, pairs, c_list, mScales):
             return self._evaluate(positions, box, pairs, c_list, mScales, False)[0]

@@ -749,6 +749,32 @@ int admp_mesh_spread(admp_handle* h, const void* positions, const double* box, c
 int admp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* Q_local, const void* pol,
                      const void* tholes, const void* U, const void* phi_in, int which, int on_device, double* E_out, void* pot,
                      void* grad, void* fld, int32_t* info4);
+/* One leg of the reciprocal part of a dispersion PME call alone (test entries; single rank: a slab-decomposed handle returns
+ * ADMP_E_ARG).  Needs topology, Ewald parameters and pairs (an empty pair list will do).  Both choose the path exactly as
+ * admp_disp_energy_grad does (the handle's mesh plans, the brick rule of the spread, the precision, pmax, the type table of
+ * admp_disp_set_types) and run that path's own part functions; nothing of the real-space chain runs.  c_list (Na,3).
+ * A path keeps nmesh meshes of K1 K2 K3 words: one per power (C6, C8, C10 up to pmax), or one per type on the typed paths.
+ *   admp_disp_mesh_spread: what the path launches between the pair kernel and the convolution (brick paths: stencil bases,
+ *     binning, brick spread; site-row paths: scalar site rows, spread; typed paths: the type check and the one-hot weights as
+ *     well).  mesh_out receives the nmesh meshes, the powers of a per-power loop in consecutive meshes.  *E_self_out: what the
+ *     leg added to the self word (the site-row paths sum the self term with their rows; the brick paths add nothing here).
+ *   admp_disp_mesh_gather, which = 0: phi_in holds nmesh meshes as the path's convolution leaves them (phi_p per power, or
+ *     psi_t = sum_p c_p,t phi_p per type on the typed paths); out (Na,3) = the path's gather into a gradient that starts from
+ *     zero; *E_self_out: the self term where the path forms it after the convolution (the brick paths' sum on the device, the
+ *     typed paths' sum over the type counts), else 0.
+ *   which = 1: the value gather of admp_disp_param_grad's mesh part: out (Na,3)[:, p] = phi_p(r_i) + 2 kp_p c_p,i, phi_in one
+ *     mesh per power; *E_self_out = 0.
+ * On a typed path a type table that does not describe c_list is refused as by admp_disp_energy_grad.
+ * Words of the handle's type on the device (on_device != 0) or on the host, inputs and outputs alike.
+ * info8 = {path (index of DispPath in csrc/disp_plan.h: 0 BricksTyped, 1 BricksBatched, 2 BricksPerPower, 3 DftTyped,
+ * 4 DftBatched, 5 PerPower), nmesh, 1 if the meshes are per type, bricks along x, y, z, workgroups the launcher of the leg's main
+ * kernel used, as that launcher reports them, for the kernels of disp_kernels.hip (brick spread, k_gather_scalar,
+ * k_gather_value); -1 on the site-row paths, whose legs run the electrostatics launchers, the site-row paths' spread form
+ * (ADMP_SPREAD_FORM_*; -1 on the brick paths)}. */
+int admp_disp_mesh_spread(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax, int on_device,
+                          void* mesh_out, double* E_self_out, int32_t* info8);
+int admp_disp_mesh_gather(admp_handle* h, const void* positions, const double* box, const void* c_list, int pmax,
+                          const void* phi_in, int which, int on_device, double* E_self_out, void* out, int32_t* info8);
 /* The site table alone (test entry, single rank, prerequisites as admp_mesh_spread): what an evaluation does up to the end of
  * its site pass (k_prepare_sites), at the dipoles U as given.
  *   sites_out (Na,20)  the site rows as the handle's type lays them out: r (3), Q global (9), U in harmonic order z, x, y (3),
