@@ -75,6 +75,8 @@ PROTOTYPES = {
     'admp_md_fire_step': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _dp, _dbl, _u64, _vp]),
     'admp_md_vrescale': (_i32, [_vp, _i32, _vp, _vp, _vp, _dbl, _i64, _dbl, _dbl, _u64, _u64, _u64, _vp]),
     'admp_md_rdf': (_i32, [_vp, _i32, _vp, _dp, _vp, _i32, _dbl, _i32, _vp, _i32, _c.POINTER(_i64)]),
+    'admp_md_tcf': (_i32, [_vp, _i32, _vp, _vp, _dp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                          _c.POINTER(_i64)]),
     'admp_neighbor_count': (_i32, [_vp, _i32, _vp, _dp, _dbl, _c.POINTER(_i64)]),
     'admp_neighbor_fill': (_i32, [_vp, _vp]),
     'admp_set_pairs_from_positions': (_i32, [_vp, _vp, _dp, _dbl]),

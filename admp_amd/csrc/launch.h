@@ -604,6 +604,15 @@ struct RdfPlan;
 template <class T>
 int launch_rdf(hipStream_t st, const RdfPlan& plan, int n_atoms, const T* pos, const int* tags, const Box<T>& box, int n_types,
                double r_max, int n_bins, CellScratch& cs, unsigned long long* out);
+// (tcf_kernels.hip) one frame of the time correlation functions by the plan of tcf_plan.h: the frame goes into the caller's ring
+// (n_lags, 2, 3, n_slots), the sums of |d(t) - d(t - k)|^2 and v(t) . v(t - k) per type and lag are ADDED to acc (2, n_types,
+// n_lags); partial: plan.scratch_bytes of scratch.  The box is double whatever T: the unwrap runs in double (tcf_math.h).  No float
+// atomics, no host synchronisation.  Returns hipError_t as int.
+struct TcfPlan;
+template <class T>
+int launch_tcf(hipStream_t st, const TcfPlan& plan, int n_atoms, const T* pos, const T* vel, const Box<double>& box, int n_slots,
+               const int* slot_atom, int n_tiles, const int* tile_type, int tile_atoms, int n_types, int n_lags, int64_t frame,
+               T* ring, double* unwrapped, T* last, unsigned long long* jumps, double* partial, double* acc);
 template <class T>
 int cell_count_pairs(hipStream_t st, int na, const T* pos, const Box<T>& box, const double* heights, double rc,
                      CellScratch& cs, long long* n_pairs);

@@ -1,5 +1,5 @@
 // The MD-driver helpers behind the admp_md_* entries of include/admp_hip.h (md_kernels.hip, mts_kernels.hip, con_kernels.hip,
-// mol_kernels.hip, fire_kernels.hip, vrescale_kernels.hip, rdf_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
+// mol_kernels.hip, fire_kernels.hip, vrescale_kernels.hip, rdf_kernels.hip, tcf_kernels.hip): device pointers in, nothing read back.  Of a handle they use its device, its stream, its
 // profiler and its rank count (handle.h HandleCtx), nothing of the engine.  The driver of a handle is created by its first
 // admp_md_* call, in the handle's precision, and dies with the handle.
 //
@@ -15,7 +15,7 @@
 //   * admp_md_mts_step checks n_inner before it looks for null pointers; the launches of the other two plans look for null
 //     inv_mass / box first (MdDriver::planned).
 //   * The profiler labels: md_bonded, md_kick_drift, md_langevin, md_random, md_bonded_box, md_virial, md_scale, md_mts,
-//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire, md_vrescale, md_rdf.
+//     md_con_step, md_con_kick, md_con_project, md_mol_sums, md_mol_scale, md_fire, md_vrescale, md_rdf, md_tcf.
 //   * The three *_info layouts differ (see the three functions); in each, words 0-6 are zero while no plan is held and word 7,
 //     the launch count, is always reported.
 //   * Tests match on the error texts: they stay byte for byte.
@@ -33,6 +33,7 @@
 #include "launch.h"
 #include "md_fire_math.h"
 #include "rdf_plan.h"
+#include "tcf_plan.h"
 
 using namespace admp;
 
@@ -406,6 +407,35 @@ struct MdDriver : HandleExt {
                                  reinterpret_cast<unsigned long long*>(hist_dev));
     if (rc != 0) throw Err{ADMP_E_HIP, std::string("radial distribution: ") + hipGetErrorString((hipError_t)rc)};
   }
+
+  // time correlation functions (tcf_kernels.hip, tcf_math.h, tcf_plan.h; admp_amd/md.py CorrelationRecorder): the caller owns the
+  // ring, the state and the accumulators, the driver the partial sums of one call; every argument is checked before anything is
+  // launched or written, the slab refusal first.  Growing tcf_rows is the one host synchronisation.
+  DevBuf tcf_rows;
+  void tcf(int n, const void* pos, const void* vel, const double* box, int n_slots, const int32_t* slot_atom, int n_tiles,
+           const int32_t* tile_type, int tile_atoms, int n_types, int n_lags, int64_t frame, void* ring, double* unwrapped, void* last,
+           uint64_t* jumps, double* acc, int64_t* info4) {
+    single_rank();
+    ARG_CHECK(box && acc && ring && unwrapped && last && jumps, "bad argument (null pointer)");
+    ARG_CHECK(n_slots <= 0 || (pos && vel && slot_atom && tile_type), "bad argument (null pointer)");
+    const TcfPlan p = tcf_make_plan(n, n_slots, n_tiles, tile_atoms, n_types, n_lags, frame);
+    if (p.error) throw Err{ADMP_E_ARG, p.error};
+    (void)finite_box(box);
+    double inv[9], vol;
+    const Box<double> bx = make_box<double>(box, inv, &vol);
+    const bool launch = n_slots > 0 && p.workgroups > 0;
+    if (info4) {
+      info4[0] = launch ? p.workgroups : 0; info4[1] = kTcfLagsPerWg; info4[2] = launch ? p.lags_now : 0;
+      info4[3] = launch ? (int64_t)p.scratch_bytes : 0;
+    }
+    if (!launch) return;
+    tcf_rows.need(p.scratch_bytes);
+    TIMED("md_tcf");
+    const int rc = launch_tcf<T>(stream, p, n, reinterpret_cast<const T*>(pos), reinterpret_cast<const T*>(vel), bx, n_slots, slot_atom,
+                                 n_tiles, tile_type, tile_atoms, n_types, n_lags, frame, reinterpret_cast<T*>(ring), unwrapped,
+                                 reinterpret_cast<T*>(last), reinterpret_cast<unsigned long long*>(jumps), tcf_rows.as<double>(), acc);
+    if (rc != 0) throw Err{ADMP_E_HIP, std::string("time correlation functions: ") + hipGetErrorString((hipError_t)rc)};
+  }
 };
 
 template <class T>
@@ -529,6 +559,15 @@ int admp_md_vrescale(admp_handle* h, int n_atoms, void* velocities, const void* 
 int admp_md_rdf(admp_handle* h, int n_atoms, const void* positions_dev, const double* box, const int32_t* tags_dev, int n_types,
                 double r_max, int n_bins, uint64_t* hist_dev, int force, int64_t* info4) {
   return md_call(h, [&](auto& md) { md.rdf(n_atoms, positions_dev, box, tags_dev, n_types, r_max, n_bins, hist_dev, force, info4); });
+}
+int admp_md_tcf(admp_handle* h, int n_atoms, const void* positions_dev, const void* velocities_dev, const double* box, int n_slots,
+                const int32_t* slot_atom_dev, int n_tiles, const int32_t* tile_type_dev, int tile_atoms, int n_types, int n_lags,
+                int64_t frame, void* ring_dev, double* unwrapped_dev, void* last_dev, uint64_t* jumps_dev, double* acc_dev,
+                int64_t* info4) {
+  return md_call(h, [&](auto& md) {
+    md.tcf(n_atoms, positions_dev, velocities_dev, box, n_slots, slot_atom_dev, n_tiles, tile_type_dev, tile_atoms, n_types, n_lags,
+           frame, ring_dev, unwrapped_dev, last_dev, jumps_dev, acc_dev, info4);
+  });
 }
 
 }  // extern "C"

@@ -53,6 +53,13 @@ device histogram of 64-bit counters by one C call (admp_md_rdf: pairs of 256-ato
 integer atomics only, so the counts are bit-identical from run to run; csrc/rdf_math.h, rdf_plan.h, rdf_kernels.hip) and read
 when the run ends; `rdf_normalise` turns counts into g_ab(r) and running coordination numbers, `rdf_tags` types and group labels
 into the per-atom tags.  Used by every driver in examples/md with --rdf N.
+
+`CorrelationRecorder` accumulates mean-square displacements and velocity autocorrelations per type along a run: a ring of the last
+L frames lives on the device, and one C call per recorded frame (admp_md_tcf: csrc/tcf_math.h, tcf_plan.h, tcf_kernels.hip)
+unwraps the frame in double, stores it and correlates it with every frame of the ring -- sums in double, fixed order, no float
+atomics, nothing read back until the run ends.  `tcf_layout` sorts the counted atoms into single-type tiles, `tcf_normalise` turns
+the sums into MSD(t) and VACF(t), `diffusion_einstein` and `diffusion_green_kubo` into self-diffusion coefficients, `vdos` into the
+vibrational density of states.  Used by every driver in examples/md with --msd N.
 """
 import ctypes
 
@@ -1287,3 +1294,192 @@ class RdfRecorder:
     def rdf(self):
         """(host read) r, g[(a, b)], n[(a, b)] of `rdf_normalise` over the frames recorded so far"""
         return rdf_normalise(self.counts(), self.type_counts, self.r_max, self.frames, self.sum_inv_volume)
+
+
+# ---- time correlation functions (include/admp_hip.h admp_md_tcf; csrc/tcf_math.h, tcf_plan.h) -----------------------------------
+TCF_MAX_TYPES, TCF_LAGS_PER_WORKGROUP = 8, 16
+DIFFUSION_1E5_CM2_S = 1.0e4          # 1 A^2/fs = 1e-16 cm^2 / 1e-15 s = 0.1 cm^2/s = 1e4 x 1e-5 cm^2/s
+LIGHT_CM_PER_FS = 2.99792458e-5      # a frequency in 1/fs divided by this is a wavenumber in 1/cm
+
+
+def tcf_layout(types, tile_atoms=256):
+    """per-atom types (ints; negative: not counted; at most 0..7) -> (slot_atom int32 (n_slots), tile_type int32 (n_tiles), n_types,
+    atoms per type): the counted atoms sorted by type (a stable sort: inside a type in atom order), every type's run padded with
+    -1 to a whole number of tiles of `tile_atoms` slots, so that every tile holds one type; a type without atoms has no tile.
+    Pure numpy."""
+    t = np.asarray(types)
+    if t.ndim != 1 or (t.size and not np.issubdtype(t.dtype, np.integer)):
+        raise ValueError('types must be a one-dimensional array of integers')
+    if int(tile_atoms) != tile_atoms or tile_atoms < 64 or tile_atoms > 1024 or tile_atoms % 64:
+        raise ValueError('tile_atoms must be a multiple of 64 in 64..1024')
+    tile_atoms = int(tile_atoms)
+    t = t.astype(np.int64)
+    if t.size and t.max() >= TCF_MAX_TYPES:
+        raise ValueError('at most %d types (0..%d), got type %d' % (TCF_MAX_TYPES, TCF_MAX_TYPES - 1, t.max()))
+    n_types = max(int(t.max()) + 1, 1) if t.size else 1
+    counts = np.bincount(t[t >= 0], minlength=n_types).astype(np.int64)
+    counted = np.nonzero(t >= 0)[0]
+    order = counted[np.argsort(t[counted], kind='stable')]
+    slot_atom, tile_type, at = [], [], 0
+    for a in range(n_types):
+        n_a = int(counts[a])
+        tiles = (n_a + tile_atoms - 1) // tile_atoms
+        run = np.full(tiles * tile_atoms, -1, dtype=np.int32)
+        run[:n_a] = order[at:at + n_a]
+        at += n_a
+        slot_atom.append(run)
+        tile_type += [a] * tiles
+    slot_atom = np.concatenate(slot_atom) if slot_atom else np.zeros(0, dtype=np.int32)
+    return slot_atom.astype(np.int32), np.array(tile_type, dtype=np.int32), n_types, counts
+
+
+def tcf_normalise(sums, type_counts, dt_fs):
+    """sums: {'msd': (n_types, L), 'vacf': (n_types, L), 'origins': (L,)} of `CorrelationRecorder.sums`; type_counts: the atoms N_a
+    of every type -> (t, msd, vacf): t = k dt_fs, msd[a] (A^2) and vacf[a] (A^2/fs^2) the sums over N_a origins[k]; a lag without
+    origins and a type without atoms give zeros.  Pure numpy."""
+    m, v = np.asarray(sums['msd'], dtype=np.float64), np.asarray(sums['vacf'], dtype=np.float64)
+    org = np.asarray(sums['origins'], dtype=np.float64).reshape(-1)
+    N = np.asarray(type_counts, dtype=np.float64).reshape(-1)
+    if m.ndim != 2 or m.shape != v.shape or m.shape != (len(N), len(org)):
+        raise ValueError('msd and vacf must be (%d, %d), got %s and %s' % (len(N), len(org), m.shape, v.shape))
+    t = np.arange(len(org)) * float(dt_fs)
+    msd, vacf = {}, {}
+    for a in range(len(N)):
+        norm = N[a] * org
+        ok = norm > 0
+        msd[a] = np.where(ok, m[a] / np.where(ok, norm, 1.0), 0.0)
+        vacf[a] = np.where(ok, v[a] / np.where(ok, norm, 1.0), 0.0)
+    return t, msd, vacf
+
+
+def diffusion_einstein(t, msd, t_min, t_max):
+    """D = slope / 6 of the least-squares line through msd(t) over t_min <= t <= t_max (A^2/fs; x DIFFUSION_1E5_CM2_S for
+    1e-5 cm^2/s).  Needs two points."""
+    t, msd = np.asarray(t, dtype=np.float64), np.asarray(msd, dtype=np.float64)
+    sel = (t >= t_min) & (t <= t_max)
+    if sel.sum() < 2:
+        raise ValueError('the fit needs at least two lags in [t_min, t_max]')
+    x, y = t[sel] - t[sel].mean(), msd[sel] - msd[sel].mean()
+    return float((x * y).sum() / (x * x).sum()) / 6.0
+
+
+def diffusion_green_kubo(t, vacf, t_max=None):
+    """D = 1/3 of the trapezoid integral of vacf from 0 to t_max (None: all of t), A^2/fs -> (D, running): running[k] is the integral
+    up to t[k] over 3, for judging the plateau."""
+    t, vacf = np.asarray(t, dtype=np.float64), np.asarray(vacf, dtype=np.float64)
+    running = np.concatenate([[0.0], np.cumsum(0.5 * (vacf[1:] + vacf[:-1]) * np.diff(t))]) / 3.0
+    k = len(t) - 1 if t_max is None else int(np.nonzero(t <= t_max)[0][-1])
+    return float(running[k]), running
+
+
+def vdos(t, vacf, window='hann'):
+    """the vibrational density of states of a velocity autocorrelation function on the lags t = k dt (fs): the cosine transform
+    S_j = dt [c_0 + 2 sum_{k >= 1} w_k c_k cos(2 pi nu_j t_k)] of c = vacf / vacf[0] at nu_j = j / (2 L dt), j = 0 .. L - 1, with
+    w_k = (1 + cos(pi k / L)) / 2 (window='hann': the decaying half of a Hann window) or 1 (window=None) -> (wavenumbers in 1/cm,
+    S in fs)."""
+    t, vacf = np.asarray(t, dtype=np.float64), np.asarray(vacf, dtype=np.float64)
+    L = len(t)
+    if L < 2 or vacf.shape != t.shape or vacf[0] == 0:
+        raise ValueError('vdos needs at least two lags and vacf[0] != 0')
+    dt = float(t[1] - t[0])
+    k = np.arange(L)
+    if window == 'hann':
+        w = 0.5 * (1.0 + np.cos(np.pi * k / L))
+    elif window is None:
+        w = np.ones(L)
+    else:
+        raise ValueError('window must be \'hann\' or None')
+    c = w * vacf / vacf[0]
+    c[1:] *= 2.0
+    S = dt * (np.cos(np.pi * np.outer(k, k) / L) @ c)
+    return k / (2.0 * L * dt) / LIGHT_CM_PER_FS, S
+
+
+class CorrelationRecorder:
+    """Accumulates mean-square displacements and velocity autocorrelations per type along a run on the device, without a host read
+    per frame.  `handle_owner` is any object with a handle; `types` (ints, negative: not counted, at most 8 types) and `n_lags` = L
+    are fixed at construction, `dt_fs` is the time between two records (the recorder does not know the driver's step).  The object
+    owns a ring (L, 2, 3, n_slots) with d and v of the last L frames in the handle's precision -- `ValueError` above
+    `max_ring_bytes` -- the unwrapped displacement of every counted atom in double, its last position, one word counting large
+    jumps and the accumulators (2, n_types, L) in double.  `record` is one C call (admp_md_tcf): it unwraps the frame against the
+    last one (the minimum image of pos - last in the cell GIVEN, in double: wrapped and unwrapped trajectories give the same d;
+    under a changing cell the displacement between two frames is the minimum image in the newer cell), stores it, and adds
+    sum |d(t) - d(t - k)|^2 and sum v(t) . v(t - k) for every lag k the ring holds, in double without float atomics: a run
+    repeats bit for bit.  Atoms should move less than a quarter of a cell height between two records; `info()['large_jumps']` counts
+    the moves that did not.  The centre-of-mass drift is not removed."""
+
+    def __init__(self, handle_owner, types, n_lags, dt_fs, tile_atoms=256, max_ring_bytes=2 ** 31):
+        self._o = o = handle_owner
+        if int(n_lags) != n_lags or n_lags < 1:
+            raise ValueError('n_lags must be a positive integer')
+        self.n_lags, self.dt_fs = int(n_lags), float(dt_fs)
+        if not (np.isfinite(self.dt_fs) and self.dt_fs > 0):
+            raise ValueError('dt_fs must be positive and finite')
+        slot_atom, tile_type, self.n_types, self.type_counts = tcf_layout(types, tile_atoms)
+        self.n_atoms, self.tile_atoms = len(np.asarray(types)), int(tile_atoms)
+        self.n_slots, self.n_tiles = len(slot_atom), len(tile_type)
+        item = torch.empty(0, dtype=o._dtype).element_size()
+        self.ring_bytes = self.n_lags * 6 * self.n_slots * item
+        if self.ring_bytes > max_ring_bytes:
+            raise ValueError('the ring of %d lags x %d slots needs %d bytes (%.2f GiB), above max_ring_bytes = %d'
+                             % (self.n_lags, self.n_slots, self.ring_bytes, self.ring_bytes / 2.0 ** 30, max_ring_bytes))
+        dev = o._device
+        self._slot_atom = torch.as_tensor(slot_atom).to(dev)
+        self._tile_type = torch.as_tensor(tile_type).to(dev)
+        # (one element at least: an empty device array has no address, and the library refuses a NULL ring or state)
+        self._ring = torch.zeros(max(self.n_lags * 6 * self.n_slots, 1), dtype=o._dtype, device=dev)
+        self._unwrapped = torch.zeros(max(3 * self.n_slots, 1), dtype=torch.float64, device=dev)
+        self._last = torch.zeros(max(3 * self.n_slots, 1), dtype=o._dtype, device=dev)
+        self._jumps = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._acc = torch.zeros(2 * self.n_types * self.n_lags, dtype=torch.float64, device=dev)
+        self._info = (ctypes.c_int64 * 4)()
+        self.frames = 0
+
+    def record(self, positions, velocities, box):
+        """one frame (positions, velocities: (n, 3) device tensors of the handle's precision; box: 9 host values, rows): one C
+        call, no host read.  ValueError for what the library refuses as an argument (a singular box): nothing is recorded then."""
+        o = self._o
+        _checked_as(o, (self.n_atoms, 3), positions=positions, velocities=velocities)
+        boxa, _ = o._harr('tcf_box', box, 9)
+        o._use_current_stream()
+        P = o._ptr
+        rc = o._L.admp_md_tcf(o._h, self.n_atoms, P(positions), P(velocities), boxa, self.n_slots, P(self._slot_atom), self.n_tiles,
+                              P(self._tile_type), self.tile_atoms, self.n_types, self.n_lags, self.frames, P(self._ring),
+                              P(self._unwrapped), P(self._last), P(self._jumps), P(self._acc), self._info)
+        if rc == _lib.E_ARG:
+            msg = o._L.admp_last_error(o._h)
+            raise ValueError('admp_md_tcf: %s' % (msg.decode() if msg else ''))
+        _lib.check(o._h, rc, 'admp_md_tcf')
+        self.frames += 1
+
+    def origins(self):
+        """the time origins behind every lag: max(0, frames - k)"""
+        return np.maximum(0, self.frames - np.arange(self.n_lags)).astype(np.int64)
+
+    def sums(self):
+        """(host read) {'msd': (n_types, L) sums of |d(t) - d(t - k)|^2, 'vacf': (n_types, L) sums of v(t) . v(t - k), 'origins': (L,)}"""
+        a = self._acc.cpu().numpy().reshape(2, self.n_types, self.n_lags)
+        return {'msd': a[0].copy(), 'vacf': a[1].copy(), 'origins': self.origins()}
+
+    def msd(self):
+        """(host read) t (fs), {type: mean-square displacement in A^2}"""
+        t, m, _ = tcf_normalise(self.sums(), self.type_counts, self.dt_fs)
+        return t, m
+
+    def vacf(self):
+        """(host read) t (fs), {type: velocity autocorrelation in A^2/fs^2}"""
+        t, _, v = tcf_normalise(self.sums(), self.type_counts, self.dt_fs)
+        return t, v
+
+    def reset(self):
+        """zero accumulators and jump word (memsets on the current stream), no frames: the next record re-initialises the state"""
+        self._acc.zero_()
+        self._jumps.zero_()
+        self.frames = 0
+
+    def info(self):
+        """what the last record launched (workgroups of the lag kernel, lags per workgroup, lags correlated, scratch bytes), the
+        ring's bytes and (host read) the large jumps counted so far"""
+        w = [int(x) for x in self._info]
+        return {'workgroups': w[0], 'lags_per_workgroup': w[1], 'lags': w[2], 'scratch_bytes': w[3], 'ring_bytes': self.ring_bytes,
+                'large_jumps': int(self._jumps.cpu().numpy().view(np.uint64)[0])}

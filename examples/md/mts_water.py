@@ -64,6 +64,7 @@ def main():
         e123, grad = forces(pos, pairs, bonded=False)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
+        w.record_msd(step, pos, vel)                                   # --msd: one C call, sums in double on the device, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         if vr:
             vr.kick(vel, grad)                                         # v(t + h), then the thermostat: one call
@@ -85,7 +86,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines() + w.rdf_lines():
+    for line in w.dipole_lines() + w.rdf_lines() + w.msd_lines():
         print(line)
     info = mts.plan_info()
     print('# multiple time steps: %d tiles of at most %d atoms, %d B of LDS per workgroup' % (info['tiles'], info['tile_atoms'],

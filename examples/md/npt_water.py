@@ -11,6 +11,7 @@ the thermostat's generator): a run restarted at any step repeats it.
                                     [--pressure 1] [--tau-p 1000] [--compress 4.5e-5] [--nbaro 10] [--pol] [--single] [--mesh K]
                                     [--molecular | --rigid [--bonds-only] [--tol T]]
                                     [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N] [--rdf N [--rdf-out FILE]]
+                                    [--msd N [--msd-lags L] [--msd-out FILE]]
 
 The other arguments are those of nve_water.py.  Without --molecular or --rigid: isotropic scaling of the atoms only (one rank).
 --molecular: the same flexible water, but whole molecules are scaled about their centres of mass and the pressure is the
@@ -107,6 +108,7 @@ def main():
         e123, grad = forces(pos, pairs)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
+        w.record_msd(step, pos, vel)                                   # --msd: one C call, sums in double on the device, nothing read back
         baro_now = (step + 1) % opt.nbaro == 0
         rec = baro_now and (step // opt.nbaro % max(opt.log // opt.nbaro, 1) == 0 or step + opt.nbaro >= opt.steps)
         if con is not None:
@@ -152,7 +154,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines() + w.rdf_lines():
+    for line in w.dipole_lines() + w.rdf_lines() + w.msd_lines():
         print(line)
     if con is not None or opt.molecular:
         info = baro.plan_info()

@@ -9,6 +9,7 @@ themselves do (each returns its energy as a number, like the reference's get_for
 stay on the device until a line is logged.
 
     python examples/md/nve_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--pol] [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]] [--dipoles N] [--rdf N [--rdf-out FILE]]
+                                    [--msd N [--msd-lags L] [--msd-out FILE]]
 
 --dipoles N records the molecular and cell dipoles every N steps on the device (admp_amd.md.DipoleRecorder) and prints, when the
 run ends, the mean molecular dipole in Debye, its permanent and induced shares, and the dielectric constant of the run.
@@ -58,6 +59,7 @@ def main():
         e123, grad = forces(pos, pairs)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
+        w.record_msd(step, pos, vel)                                   # --msd: one C call, sums in double on the device, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         vv.kick(pos, vel, grad, want_ekin=rec)                         # v(t + h)
         if rec:
@@ -73,7 +75,7 @@ def main():
         print('\n'.join(w.scf_lines()))
         # which form the library chose for every polarizable call (residual history, engine.hip pme()) and what wrong guesses cost
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines() + w.rdf_lines():
+    for line in w.dipole_lines() + w.rdf_lines() + w.msd_lines():
         print(line)
     print('# %d waters, %s, %s, dt %.2f fs: %.3f ms/step, %.2f ns/day (all terms, list rebuilt every %d steps); '
           'relative energy drift %.2e, T_final %.1f K' % (n_mol, 'polarizable' if opt.pol else 'fixed multipoles',

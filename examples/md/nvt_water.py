@@ -10,6 +10,7 @@ is the kick of velocity Verlet.  The velocities start from a Maxwell-Boltzmann d
     python examples/md/nvt_water.py [--waters 1024] [--steps 200] [--dt 0.5] [--temp 300] [--friction 0.05] [--seed 1] [--pol]
                                     [--single] [--mesh K] [--log 10] [--prune M] [--predict k | --aspc K [--aspc-corr N]]
                                     [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N] [--rdf N [--rdf-out FILE]]
+                                    [--msd N [--msd-lags L] [--msd-out FILE]]
 
 --thermostat vrescale runs velocity Verlet (the same first-half kernel at friction 0) under stochastic velocity rescaling
 (admp_amd.md.VRescale, relaxation time --tau-t fs): the closing half kick and the thermostat are one C call, and the log gains
@@ -58,6 +59,7 @@ def main():
         e123, grad = forces(pos, pairs)
         w.record_dipoles(step, pos)                                    # --dipoles: two small kernels, nothing read back
         w.record_rdf(step, pos)                                        # --rdf: one C call, integer counters, nothing read back
+        w.record_msd(step, pos, vel)                                   # --msd: one C call, sums in double on the device, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         if vr:
             vr.kick(vel, grad)                                         # B: v(t + h), then the thermostat: one call
@@ -77,7 +79,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines() + w.rdf_lines():
+    for line in w.dipole_lines() + w.rdf_lines() + w.msd_lines():
         print(line)
     tk = np.array([r[3] for r in log if r[0] >= opt.steps // 2])
     if vr:

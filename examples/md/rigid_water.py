@@ -9,6 +9,7 @@ the noise of --seed.  --bonds-only constrains the two O-H bonds only and keeps t
 
     python examples/md/rigid_water.py [--dt 2] [--bonds-only] [--friction 0] [--seed 1] [--tol T] [the arguments of nve_water.py]
                                       [--thermostat {langevin,vrescale}] [--tau-t 100] [--dipoles N] [--rdf N [--rdf-out FILE]]
+                                    [--msd N [--msd-lags L] [--msd-out FILE]]
 
 --thermostat vrescale keeps the friction at 0 and applies stochastic velocity rescaling (admp_amd.md.VRescale over the constrained
 degrees of freedom) after the RATTLE kick of every step: one factor for all velocities leaves them on the constraints.  The log
@@ -65,6 +66,7 @@ def main():
         e123, grad = gradient(pos, pairs_l)
         w.record_dipoles(step, pos)                                        # --dipoles: two small kernels, nothing read back
         w.record_rdf(step, pos)                                            # --rdf: one C call, integer counters, nothing read back
+        w.record_msd(step, pos, vel)                                       # --msd: one C call, sums in double on the device, nothing read back
         rec = step % opt.log == 0 or step == opt.steps - 1
         integ.kick(pos, vel, grad, box, want_ekin=rec and not vr)          # B, RATTLE: one kernel
         if vr:
@@ -85,7 +87,7 @@ def main():
     if opt.pol:
         print('\n'.join(w.scf_lines()))
         print('# SCF forms over the run (real dynamics): %s' % pme.scf_stats())
-    for line in w.dipole_lines() + w.rdf_lines():
+    for line in w.dipole_lines() + w.rdf_lines() + w.msd_lines():
         print(line)
     info = con.plan_info()
     print('# constraints: %d tiles of at most %d atoms, %d B of LDS per workgroup, most sweeps of a cluster %d; '

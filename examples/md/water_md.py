@@ -58,6 +58,13 @@ def add_arguments(ap):
                     'ends) to r_max = min(10 A, 0.49 x the smallest cell height) in bins of 0.05 A, and print the first g_OO peak, the '
                     'minimum after it, the O-O coordination number up to there and the first intermolecular g_OH peak')
     ap.add_argument('--rdf-out', default='', metavar='FILE', help='write r, g_OO, g_OH, g_HH of --rdf as text')
+    ap.add_argument('--msd', type=int, default=0, metavar='N', help='record a frame of the mean-square displacements and velocity '
+                    'autocorrelations of O and H every N steps (0: off; admp_amd.md.CorrelationRecorder: a ring of the last --msd-lags '
+                    'frames on the device, one C call per frame, nothing read back until the run ends) and print the self-diffusion '
+                    'coefficient of oxygen (Einstein fit over the second half of the lags, and Green-Kubo), the large jumps counted and, '
+                    'when the lag window resolves it, the O-H stretch peak of the hydrogen density of states')
+    ap.add_argument('--msd-lags', type=int, default=512, metavar='L', help='lags of --msd: the correlation window is L x N x dt')
+    ap.add_argument('--msd-out', default='', metavar='FILE', help='write t, msd_O, msd_H, vacf_O, vacf_H of --msd as text')
     start = ap.add_mutually_exclusive_group()
     start.add_argument('--aspc', type=int, default=-1, choices=(0, 1, 2, 3, 4), metavar='K', help='always-stable predictor-corrector dipoles '
                        'of order K in the library (ADMPPmeForce.set_aspc, switched on after the minimiser): after K + 2 warm-up steps '
@@ -294,11 +301,53 @@ def setup(opt):
             out.append('# g_OH: first intermolecular maximum %.3f at %.3f A' % (smh[kh], r[kh]))
         return out
 
+    tcf = {}
+
+    def record_msd(step, p, v):
+        """--msd N: every N steps positions and velocities into the device ring and the frame's correlations with every frame
+        of the ring into the sums: one C call on the calculator's stream; no host read.  The velocities are those the driver holds
+        where it records (after the force evaluation: v of the half step in the Verlet drivers)"""
+        n_rec = getattr(opt, 'msd', 0)
+        if not n_rec or step % n_rec:
+            return
+        if not tcf:
+            from admp_amd.md import CorrelationRecorder
+            tcf['rec'] = CorrelationRecorder(pme, np.tile([0, 1, 1], n_mol), opt.msd_lags, n_rec * opt.dt)
+        tcf['rec'].record(p, v, box)
+
+    def msd_lines():
+        """the lines a --msd run prints when it ends (the host reads of the recorder); writes --msd-out"""
+        if not tcf:
+            return []
+        from admp_amd.md import DIFFUSION_1E5_CM2_S, diffusion_einstein, diffusion_green_kubo, tcf_normalise, vdos
+        rec = tcf['rec']
+        t, msd, vacf = tcf_normalise(rec.sums(), rec.type_counts, rec.dt_fs)
+        if getattr(opt, 'msd_out', ''):
+            np.savetxt(opt.msd_out, np.stack([t, msd[0], msd[1], vacf[0], vacf[1]], axis=1),
+                       header='t/fs msd_O/A^2 msd_H/A^2 vacf_O/(A/fs)^2 vacf_H/(A/fs)^2 (%d frames)' % rec.frames)
+        info = rec.info()
+        out = ['# msd over %d frames every %.2f fs: %d lags, %d workgroups, large_jumps %d'
+               % (rec.frames, rec.dt_fs, rec.n_lags, info['workgroups'], info['large_jumps'])]
+        have = int(min(rec.frames, rec.n_lags))      # lags with at least one origin
+        if have >= 3:
+            lo, hi = t[have // 2], t[have - 1]
+            d_e = diffusion_einstein(t[:have], msd[0][:have], lo, hi) * DIFFUSION_1E5_CM2_S
+            d_gk = diffusion_green_kubo(t[:have], vacf[0][:have])[0] * DIFFUSION_1E5_CM2_S
+            out.append('# D_O: Einstein %.4f (fit over %.1f..%.1f fs), Green-Kubo %.4f, in 1e-5 cm^2/s' % (d_e, lo, hi, d_gk))
+            # the O-H stretch: resolved when the bins are finer than 250 1/cm and reach beyond 2500 1/cm
+            if vacf[1][0] > 0:
+                w, S = vdos(t[:have], vacf[1][:have])
+                if w[1] - w[0] <= 250.0 and w[-1] > 2500.0:
+                    k = int(np.argmax(np.where(w > 2500.0, S, -np.inf)))
+                    out.append('# vdos_H: highest peak above 2500 cm^-1 at %.0f cm^-1 (bins of %.0f cm^-1)' % (w[k], w[1] - w[0]))
+        return out
+
     par_t = types.SimpleNamespace(Q=Q, pol=pol, thole=thole, c_list=cl, a=a_, b=b_, q=q_, c6=c6, mS=mS, pS=pS, dS=dS)
     return types.SimpleNamespace(n_mol=n_mol, box=box, pos=pos, dtype=dt, mass=mass, pme=pme, disp=disp, bond=bond, nbl=nbl,
                                  forces=forces, epot_now=epot_now, state=state, tt=tt_obj, par=par_t, box_gradient=box_gradient,
                                  start_aspc=start_aspc, aspc_jump=aspc_jump, scf_lines=scf_lines, record_dipoles=record_dipoles,
-                                 dipole_lines=dipole_lines, record_rdf=record_rdf, rdf_lines=rdf_lines)
+                                 dipole_lines=dipole_lines, record_rdf=record_rdf, rdf_lines=rdf_lines, record_msd=record_msd,
+                                 msd_lines=msd_lines)
 
 
 def minimize_fire(w, opt, pos, gradient=None, epot=None, constraints=None, label='minimize'):

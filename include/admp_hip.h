@@ -527,6 +527,50 @@ int admp_md_rdf(admp_handle* h, int n_atoms, const void* positions_dev, const do
                 int n_types, double r_max, int n_bins, uint64_t* hist_dev /* channels * n_bins, ADDED to */,
                 int force /* 0 auto, 1 tiles, 2 cells */, int64_t* info4 /* host, may be NULL */);
 
+/* No counterpart in the reference: time correlation functions -- one recorded frame correlated with the last n_lags - 1 frames
+ * of a caller-owned device ring (admp_amd/csrc/tcf_math.h, tcf_plan.h, tcf_kernels.hip).  For every counted type a and every lag
+ * k = 0 .. min(frame, n_lags - 1) the call ADDS
+ *     acc[0][a][k] += sum_{i of type a} |d_i(t) - d_i(t - k)|^2        (A^2;      mean-square displacement x N_a x origins)
+ *     acc[1][a][k] += sum_{i of type a} v_i(t) . v_i(t - k)            (A^2/fs^2; velocity autocorrelation x N_a x origins)
+ * where t is this frame and t - k the frame recorded k calls earlier; lag 0 is included (acc[0][a][0] stays 0, acc[1][a][0] sums
+ * v^2).  The number of time origins behind lag k after `frames` calls is max(0, frames - k); the caller keeps it.
+ *   positions_dev, velocities_dev  (n_atoms,3) real of the handle's precision, DEVICE pointers; atoms may lie outside the cell
+ *   box            9 HOST doubles, lattice vectors in rows
+ *   slot_atom_dev  (n_slots) int32, DEVICE pointer: the atom of a slot, or anything outside 0 .. n_atoms - 1 for padding.  The
+ *                  counted atoms sorted by type, every type's run padded to a whole number of tiles of tile_atoms slots, so
+ *                  that a tile holds one type (admp_amd/md.py tcf_layout).  n_slots = n_tiles * tile_atoms.
+ *   tile_type_dev  (n_tiles) int32, DEVICE pointer: the type 0 .. n_types - 1 of a tile; anything else: the tile is not counted
+ *   tile_atoms     a multiple of 64 in 64 .. 1024;  n_types 1 .. 8;  n_lags >= 1
+ *   frame          the index of this frame, 0, 1, 2, ...: 0 initialises the state (d = 0, last = positions) and counts no jump;
+ *                  frame f is stored in ring slot f mod n_lags and reaches the lags 0 .. min(f, n_lags - 1)
+ *   ring_dev       (n_lags, 2, 3, n_slots) real of the handle's precision, DEVICE pointer: d and v of the last n_lags frames, one
+ *                  component per row.  d is rounded once from the double accumulator, v is copied unchanged.
+ *   unwrapped_dev  (n_slots,3) double: d_i, the unwrapped displacement since frame 0.  Every call adds the minimum image of
+ *                  positions - last, taken in THIS call's cell, in double whatever the handle's precision: the result is the
+ *                  same whether or not the caller wraps atoms into the cell, on a triclinic cell too.  Under a changing cell
+ *                  (NPT) the displacement between two frames is therefore the minimum image in the newer cell.
+ *   last_dev       (n_slots,3) real of the handle's precision: the position of the slot's atom at the previous call
+ *   jumps_dev      one uint64 word, integer atomicAdd: the number of (slot, call) whose minimum-image move had a fractional
+ *                  component |s| >= 0.25 (whole lattice vectors, which a caller who wraps atoms adds, are removed first) -- a
+ *                  quarter of a cell height or more between two frames cannot be unwrapped safely.  The move is applied all the
+ *                  same and nothing is refused.
+ *   acc_dev        (2, n_types, n_lags) double, DEVICE pointer: ADDED to; the caller zeroes it and reads it
+ *   info4          HOST, may be NULL: workgroups of the lag kernel, lags per workgroup, lags correlated in this call, scratch bytes
+ * The sums are in double (the conversion of a float is exact) without float atomics: a lane sums its slots, a wave its lanes, a
+ * workgroup its waves and one lane per (quantity, type, lag) the tiles of its type, all in an order that is a function of the
+ * layout alone, so a run repeats bit for bit.  A call reads every ring word of the lags it reaches once: lags * n_slots * 6
+ * words.  Runs on the handle's stream and makes no host synchronisation (growing the driver's scratch, 2 n_tiles n_lags doubles,
+ * excepted).  n_slots = 0 launches nothing.
+ * ADMP_E_STATE on a slab-decomposed handle.  ADMP_E_ARG, before anything is launched or written, for a NULL box, acc, ring,
+ * unwrapped, last or jumps pointer, NULL positions, velocities, slot_atom or tile_type (unless n_slots = 0), a negative count,
+ * n_slots != n_tiles * tile_atoms, tile_atoms not a multiple of 64 in 64 .. 1024, n_types outside 1 .. 8, n_lags < 1, frame < 0, a
+ * singular or non-finite box. */
+int admp_md_tcf(admp_handle* h, int n_atoms, const void* positions_dev, const void* velocities_dev, const double* box /* 9 host */,
+                int n_slots, const int32_t* slot_atom_dev, int n_tiles, const int32_t* tile_type_dev, int tile_atoms,
+                int n_types, int n_lags, int64_t frame /* 0: first frame, initialises the state */,
+                void* ring_dev, double* unwrapped_dev, void* last_dev, uint64_t* jumps_dev,
+                double* acc_dev /* (2, n_types, n_lags), ADDED to */, int64_t* info4 /* host, may be NULL */);
+
 /* ---- multi-GPU: x-slab decomposition ---------------------------------------------------------------------
  * (no counterpart in the reference, which is single-device)  One process per GPU, SPMD: every rank makes
  * the same admp_pme_energy_grad / admp_disp_energy_grad / admp_tt_energy_grad call with the same full input arrays.  Rank s
